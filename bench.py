@@ -19,12 +19,16 @@ the synthetic speakers.  They are produced by the CPU oracle's torch modules (or
 saved in the reference checkpoint format and loaded by the product through `Pipeline.from_pretrained`;
 the oracle takes no part in the measured path.  The same oracle models run the `cpu_baseline` leg.
 
-Output: ONE JSON line on rank 0 (contract in the task statement) with `roofline` (dominant kernel,
-HIP events on the launch stream via the library's built-in profiler) and `cpu_baseline`; since round 4 the default
-N = 1 line also carries `roofline_others` (the other matrix-pipe kernels above 2 % of a step), `configs` (BASELINE.json
-configs[1] and configs[2] -- `--config seg5s` / `emb3s` -- timed by the same run, a few steps each) and `ingest` (one
+Output: ONE JSON line on rank 0 (contract in the task statement).  A plain run sets up, warms up, times the
+`--steps` steps and prints the line (`metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step` and what
+the timed steps themselves recorded); nothing else runs.  `--dump-outputs DIR` then also writes what the last timed
+step returned as DIR/<name>.npy.  `--full` adds every other leg, each after the timed region: `roofline` (dominant
+kernel, HIP events on the launch stream via the library's built-in profiler, one extra profiled step),
+`roofline_others` (the other matrix-pipe kernels above 2 % of a step), `sequential_stages_ms`, `cpu_baseline`,
+`configs` (BASELINE.json configs[1] and configs[2] -- `--config seg5s` / `emb3s` -- a few steps each), `ingest` (one
 file that starts in HOST memory through `pipeline(file)`, one call at a time: what the reference's own speed metric,
-__main__.py:684-744, measures and `value` leaves out).  None of these extra legs is inside the timed region of `value`.
+__main__.py:684-744, measures and `value` leaves out), `reference_metric`, `sparse_speech` and, at N > 1, the other
+clustering mode.  None of these is inside the timed region of `value`.
 """
 from __future__ import annotations
 
@@ -241,6 +245,33 @@ def roofline_entry(name: str, r: dict, config: str = "pipeline") -> dict:
     return roof
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def annotation_rows(annotation) -> np.ndarray:
+    """(turns, 3) float64 [start, end, index of the label in annotation.labels()], in `itertracks` order."""
+    labels = {label: i for i, label in enumerate(annotation.labels())}
+    return np.array([(start, end, labels[label]) for start, end, _, label in annotation.flat_rows()],
+                    dtype=np.float64).reshape(-1, 3)
+
+
+def dump_outputs(directory: str, arrays: dict) -> None:
+    """`--dump-outputs DIR`: every array as DIR/<name>.npy, float64 kept, the rest as float32.  Above
+    DUMP_LIMIT_BYTES in all, each array keeps a fixed seeded sample of its leading-axis rows, and the indices of
+    those rows go to DIR/<name>_rows.npy."""
+    arrays = {k: np.asarray(v.detach().cpu() if torch.is_tensor(v) else v) for k, v in arrays.items()}
+    arrays = {k: v if v.dtype == np.float64 else v.astype(np.float32) for k, v in arrays.items()}
+    total = sum(v.nbytes for v in arrays.values())
+    os.makedirs(directory, exist_ok=True)
+    for name, a in arrays.items():
+        if total > DUMP_LIMIT_BYTES and a.ndim > 0 and a.shape[0] > 1:
+            keep = max(1, int(a.shape[0] * (DUMP_LIMIT_BYTES // 2) / total))
+            rows = np.sort(np.random.default_rng(0).choice(a.shape[0], keep, replace=False))
+            a = a[rows]
+            np.save(os.path.join(directory, f"{name}_rows.npy"), rows.astype(np.float64))
+        np.save(os.path.join(directory, f"{name}.npy"), a)
+
+
 def bench_stage(args, pipeline, device, rank, config=None, steps=None, warmup=None):
     """BASELINE.json configs[1] / configs[2]: one model stage alone, inputs resident in HBM.
     A step = one pass over the whole synthetic input.  Returns the JSON line as a dict."""
@@ -260,7 +291,8 @@ def bench_stage(args, pipeline, device, rank, config=None, steps=None, warmup=No
         metric, unit, units_per_step = "segmentation chunks/s (5 s chunks)", "chunks/s", num
 
         def step():
-            engine.forward_strided(wav, stride, num, window, want_logp=True, want_multilabel=True)
+            logp, ml = engine.forward_strided(wav, stride, num, window, want_logp=True, want_multilabel=True)
+            return {"logp": logp, "multilabel": ml}
     else:
         num, window = 10000, 48000
         wav = (0.1 * torch.randn(num * window, device=device, generator=g)).clamp_(-1, 1)
@@ -272,22 +304,18 @@ def bench_stage(args, pipeline, device, rank, config=None, steps=None, warmup=No
         metric, unit, units_per_step = "embedding segments/s (3 s segments)", "segments/s", num
 
         def step():
-            engine.forward_strided(wav, window, num, window, masks)
+            return {"embeddings": engine.forward_strided(wav, window, num, window, masks)}
 
     for _ in range(warmup):
         step()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(steps):
-        step()
+        outputs = step()
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
-    ffi.prof_enable(True)
-    step()
-    torch.cuda.synchronize()
-    prof = ffi.prof_report()
-    ffi.prof_enable(False)
-    dom = max(prof, key=lambda k: prof[k]["ms"])
+    if args.dump_outputs and rank == 0 and config == args.config:
+        dump_outputs(args.dump_outputs, outputs)
     rate = units_per_step * steps / elapsed
     stage_tflops = rate * per_unit_gflop / 1e3
     line = {"metric": metric, "value": round(rate, 1), "unit": unit, "n_gpus": 1, "steps": steps,
@@ -299,12 +327,19 @@ def bench_stage(args, pipeline, device, rank, config=None, steps=None, warmup=No
             "stage_algorithmic": {"tflops": round(stage_tflops, 2),
                                   "frac_of_f32_mfma_peak": round(stage_tflops / PEAK_MFMA_F32_TFLOPS, 4),
                                   "gflop_per_unit": per_unit_gflop},
-            "roofline": roofline_entry(dom, prof[dom], config),
-            "kernels": {k: {"launches": r["launches"], "ms": round(r["ms"], 3),
-                            "tflops": round(r["flops"] / r["ms"] / 1e9, 2) if r["ms"] > 0 else None,
-                            "gbs": round(r["bytes"] / r["ms"] / 1e6, 1) if r["ms"] > 0 else None}
-                        for k, r in prof.items()},
             "cpu_baseline": None}
+    if args.full:   # per-kernel figures: one extra profiled step
+        ffi.prof_enable(True)
+        step()
+        torch.cuda.synchronize()
+        prof = ffi.prof_report()
+        ffi.prof_enable(False)
+        dom = max(prof, key=lambda k: prof[k]["ms"])
+        line["roofline"] = roofline_entry(dom, prof[dom], config)
+        line["kernels"] = {k: {"launches": r["launches"], "ms": round(r["ms"], 3),
+                               "tflops": round(r["flops"] / r["ms"] / 1e9, 2) if r["ms"] > 0 else None,
+                               "gbs": round(r["bytes"] / r["ms"] / 1e6, 1) if r["ms"] > 0 else None}
+                           for k, r in prof.items()}
     return line
 
 
@@ -476,7 +511,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--hours", type=float, default=1.0, help="audio hours per GPU and step")
     ap.add_argument("--cpu-seconds", type=float, default=60.0, help="audio seconds of the CPU baseline")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--config", choices=["pipeline", "seg5s", "emb3s"], default="pipeline",
                     help="pipeline = BASELINE.json configs[3] (the headline metric; configs[4] at N > 1); "
                          "seg5s = configs[1] (PyanNet 5 s / 0.5 s over 1 h); emb3s = configs[2] (ResNet34 on "
@@ -489,9 +524,17 @@ def main():
     ap.add_argument("--sequential", action="store_true",
                     help="one pipeline(file) call per step instead of the pipelined apply_batch")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the (untimed for `value`) extra legs of the default line: BASELINE.json configs[1] / "
+                    help="--full without its (untimed for `value`) extra legs: BASELINE.json configs[1] / "
                          "configs[2] (`configs`) and the host-resident single file (`ingest`)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure everything that is not the headline: per-kernel "
+                         "roofline, stage split, CPU baseline, the other configurations and, at N > 1, the other "
+                         "clustering mode")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step returned as DIR/<name>.npy (float32 / float64)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if args.gpus > 1 and "RANK" not in os.environ and "WORLD_SIZE" not in os.environ:
         # plain `python bench.py --gpus N` (no launcher): start the N ranks ourselves, one process per GPU
@@ -579,38 +622,40 @@ def main():
         return result, dt
 
     out, elapsed = timed(joint, "")
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"speaker_diarization": annotation_rows(out.speaker_diarization),
+                                         "exclusive_speaker_diarization":
+                                             annotation_rows(out.exclusive_speaker_diarization),
+                                         "speaker_embeddings": out.speaker_embeddings})
     joint_info = None
     if joint:
         joint_info = {"points": int(getattr(pipeline.clustering, "timings", {}).get("num_embeddings", 0)),
                       "clustering_s": {k: (round(v, 4) if isinstance(v, float) else v)
                                        for k, v in pipeline.clustering.timings.items()}}
     other = None
-    if world > 1:            # the other N > 1 mode, measured in the same run (second key, never `value`)
+    if world > 1 and args.full:   # the other N > 1 mode, measured in the same run (second key, never `value`)
         _, other_elapsed = timed(not joint, "o")
         other = {"value": round(args.hours * world * args.steps / other_elapsed, 5),
                  "ms_per_step": round(1e3 * other_elapsed / args.steps, 2)}
 
-    # ---- stage split of ONE sequential (un-pipelined, untimed) pass: host clock + device sync per stage
-    artifacts = {}
+    artifacts, stage_sum, prof = {}, {}, {}
 
     def collecting(step_name, artifact, file=None, total=None, completed=None):
         timer(step_name, artifact, file=file, total=total, completed=completed)
         if artifact is not None and total is None and step_name in ("segmentation", "embeddings"):
             artifacts[step_name] = artifact
 
-    timer.start()
-    pipeline(file, hook=collecting)
-    stage_sum = dict(timer.t)
-
-    def step():
-        return pipeline(file)
-
-    # ---- per-kernel timing of one extra (untimed) step: HIP events on the launch stream
-    ffi.prof_enable(True)
-    step()
-    torch.cuda.synchronize()
-    prof = ffi.prof_report()
-    ffi.prof_enable(False)
+    if args.full:
+        # ---- stage split of ONE sequential (un-pipelined, untimed) pass: host clock + device sync per stage
+        timer.start()
+        pipeline(file, hook=collecting)
+        stage_sum = dict(timer.t)
+        # ---- per-kernel timing of one extra (untimed) step: HIP events on the launch stream
+        ffi.prof_enable(True)
+        pipeline(file)
+        torch.cuda.synchronize()
+        prof = ffi.prof_report()
+        ffi.prof_enable(False)
 
     if rank == 0 and os.environ.get("PA_BENCH_DUMP_EMB"):
         hooked = {}
@@ -620,18 +665,6 @@ def main():
         os.makedirs(os.path.join(ROOT, "gpurun_out"), exist_ok=True)
         np.save(os.path.join(ROOT, "gpurun_out", "bench_train_emb.npy"), tr.astype(np.float32))
     if rank == 0:
-        kernels = {}
-        for name, r in prof.items():
-            ms = r["ms"]
-            kernels[name] = {"launches": r["launches"], "ms": round(ms, 3),
-                             "tflops": round(r["flops"] / ms / 1e9, 2) if ms > 0 else None,
-                             "gbs": round(r["bytes"] / ms / 1e6, 1) if ms > 0 else None}
-        dom = max(prof, key=lambda k: prof[k]["ms"])
-        roof = roofline_entry(dom, prof[dom])
-        # the other matrix-pipe kernels that take more than 2 % of the step, same accounting (never `roofline`)
-        step_ms = sum(r["ms"] for r in prof.values())
-        others = [roofline_entry(n, r) for n, r in sorted(prof.items(), key=lambda kv: -kv[1]["ms"])
-                  if n != dom and n in MFMA_KERNELS and r["ms"] > 0.02 * step_ms]
         total_hours = args.hours * world * args.steps
         line = {
             "metric": "audio-hours/sec (real-time factor) for speaker-diarization-3.1 pipeline",
@@ -655,15 +688,24 @@ def main():
                     ("sequential pipeline(file) calls" if args.sequential else
                      "pipeline([files]) = apply_batch: clustering/back end of file i overlap the front end "
                      "of file i+1" + (" (N independent per-file pipelines, no exchange)" if world > 1 else "")),
-            "sequential_stages_ms": {k: round(1e3 * v, 1) for k, v in stage_sum.items()},
             "speakers": len(out.speaker_diarization.labels()),
             "apply_marks_s": {k: round(v, 4) for k, v in getattr(pipeline, "timings", {}).items()},
             "clustering_s": {k: (round(v, 4) if isinstance(v, float) else v)
                              for k, v in pipeline.clustering.timings.items()},
-            "roofline": roof,
-            "roofline_others": others,
-            "kernels": kernels,
         }
+        if args.full:
+            line["sequential_stages_ms"] = {k: round(1e3 * v, 1) for k, v in stage_sum.items()}
+            line["kernels"] = {name: {"launches": r["launches"], "ms": round(r["ms"], 3),
+                                      "tflops": round(r["flops"] / r["ms"] / 1e9, 2) if r["ms"] > 0 else None,
+                                      "gbs": round(r["bytes"] / r["ms"] / 1e6, 1) if r["ms"] > 0 else None}
+                               for name, r in prof.items()}
+            dom = max(prof, key=lambda k: prof[k]["ms"])
+            line["roofline"] = roofline_entry(dom, prof[dom])
+            # the other matrix-pipe kernels that take more than 2 % of the step, same accounting (never `roofline`)
+            step_ms = sum(r["ms"] for r in prof.values())
+            line["roofline_others"] = [roofline_entry(n, r)
+                                       for n, r in sorted(prof.items(), key=lambda kv: -kv[1]["ms"])
+                                       if n != dom and n in MFMA_KERNELS and r["ms"] > 0.02 * step_ms]
         # the numerical guard's decisions (weights.EmbeddingPack): a convolution demoted from F(4x4) to a slower
         # kernel changes the numbers above -- it has to be visible next to them
         guard = pipeline._embedding.model_.engine.pack.winograd_guard
@@ -678,7 +720,7 @@ def main():
             line["joint_clustering_rate" if not joint else "per_file_clustering"] = other
         if getattr(pipeline, "batch_timeline", None) and not joint:   # host-clock stage boundaries of the timed files
             line["batch_timeline_s"] = [{k: round(v, 4) for k, v in f.items()} for f in pipeline.batch_timeline]
-        if world == 1 and not args.no_extras:
+        if args.full and world == 1 and not args.no_extras:
             # the other single-GPU configurations of BASELINE.json, timed by the same run (never `value`), and
             # what a file that starts on the host costs
             line["ingest"] = bench_ingest(pipeline, wav, device, args.hours)
@@ -690,7 +732,7 @@ def main():
                 line["configs"][name] = {k: d[k] for k in ("metric", "value", "unit", "steps", "warmup", "ms_per_step",
                                                            "config", "audio_hours_per_s", "stage_algorithmic",
                                                            "roofline")}
-        if not args.no_cpu_baseline and world == 1:   # rank 0 at N = 1 only
+        if args.full and not args.no_cpu_baseline and world == 1:   # rank 0 at N = 1 only
             hour = None
             if "embeddings" in artifacts and "segmentation" in artifacts:
                 hour = (artifacts["embeddings"], artifacts["segmentation"].data)

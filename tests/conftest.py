@@ -54,6 +54,37 @@ def north_star_ratio(name, got, want, rtol=1e-4, atol=1e-5):
     return ratio
 
 
+#: host threads of torch in the tests that compare with tests/golden/reference_cpu_v1.npz and in its generator
+#: (tests/golden/make_reference_cpu_golden.py): the same float32 sums on both sides
+GOLDEN_THREADS = 4
+
+
+def digest(array) -> str:
+    """dtype, shape and SHA-256 of the bytes: a bit-for-bit fingerprint of an array too large to store as a fixture"""
+    import hashlib
+
+    import numpy as np
+    import torch
+    if isinstance(array, torch.Tensor):
+        array = array.detach().cpu().numpy()
+    a = np.ascontiguousarray(array)
+    return f"{a.dtype.str}{a.shape}:{hashlib.sha256(a.tobytes()).hexdigest()}"
+
+
+def turn_strings(turns) -> list:
+    """(start, end, label) turns as exact strings (float repr round-trips), comparable across processes"""
+    return [repr((float(start), float(end), str(label))) for start, end, label in turns]
+
+
+@pytest.fixture(scope="module")
+def golden_threads():
+    import torch
+    saved = torch.get_num_threads()
+    torch.set_num_threads(GOLDEN_THREADS)
+    yield
+    torch.set_num_threads(saved)
+
+
 PYANNET_HPARAMS = {
     "sincnet": {"stride": 10, "sample_rate": 16000},
     "lstm": {"hidden_size": 128, "num_layers": 4, "bidirectional": True, "monolithic": True,

@@ -10,7 +10,7 @@ mkdir -p $out
 cd /tmp && export TMPDIR=/tmp && cd - >/dev/null
 export PA_WINOGRAD_GUARD=0      # (the load-time guard's tiny launches would dilute the per-launch averages)
 for cfg in emb3s seg5s; do
-  CMD="python bench.py --config $cfg --steps 1 --warmup 0 --no-cpu-baseline"
+  CMD="python bench.py --config $cfg --steps 1 --warmup 0 --full --no-cpu-baseline"
   rocprofv3 --pmc FETCH_SIZE --output-format csv -d $out/fetch_$cfg -- $CMD > /dev/null 2> $out/fetch_$cfg.err
   rocprofv3 --pmc WRITE_SIZE --output-format csv -d $out/write_$cfg -- $CMD > $out/bench_$cfg.json 2> $out/write_$cfg.err
   python tools/pmc_traffic.py $out/fetch_$cfg $out/write_$cfg $out/traffic_$cfg.json > /dev/null

@@ -9,12 +9,12 @@ tag=${1:-r3}
 O=gpurun_out/final_$tag; mkdir -p $O
 timeout 900 python -m pytest tests -m gpu -q > $O/gpu_tests.txt 2>&1
 tail -4 $O/gpu_tests.txt
-timeout 300 python bench.py > $O/bench_default.json 2> $O/bench_default.err
+timeout 300 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err
 timeout 120 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $O/smoke.txt 2>&1
 tail -2 $O/smoke.txt
 timeout 200 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29513 \
-    bench.py --gpus 1 --steps 5 --no-cpu-baseline > $O/bench_torchrun_n1.json 2> $O/torchrun.err
-timeout 200 python bench.py --sequential --steps 3 --no-cpu-baseline > $O/bench_sequential.json 2>/dev/null
+    bench.py --gpus 1 --steps 5 --full --no-cpu-baseline > $O/bench_torchrun_n1.json 2> $O/torchrun.err
+timeout 200 python bench.py --sequential --steps 3 --full --no-cpu-baseline > $O/bench_sequential.json 2>/dev/null
 timeout 700 sh tools/capture_profiles.sh $tag > $O/capture.log 2>&1
 python - <<PY
 import json

@@ -3,7 +3,7 @@ cd ${GRAFT_REPO_ROOT:-/root/repo}
 export TMPDIR=/tmp
 O=gpurun_out/r4_mid; mkdir -p $O
 for w in "" 3 34 234; do
-  PA_WINOGRAD4=$w timeout 200 python bench.py --steps 6 --no-cpu-baseline --no-extras > $O/bench_w4_$w.json 2>/dev/null
+  PA_WINOGRAD4=$w timeout 200 python bench.py --steps 6 --full --no-cpu-baseline --no-extras > $O/bench_w4_$w.json 2>/dev/null
 done
 python - <<PY
 import json
