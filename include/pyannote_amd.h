@@ -196,6 +196,17 @@ int pa_emb_forward(const pa_emb_weights* w, const float* wav, int64_t wav_len, i
                    const int32_t* nearest_idx, float* emb, void* workspace, size_t workspace_bytes,
                    void* stream);
 
+/* Ragged batch: utterance b = wav[offsets[b] : offsets[b] + lengths[b]] (device int64 / int32 arrays, lengths[b] >= 400,
+ * max_samples = max lengths[b]).  The maps are padded to max_samples and zeroed past each utterance's valid columns
+ * (see emb_forward.cpp), so emb[b] is what pa_emb_forward computes for that utterance alone (up to rounding).
+ * masks: (num_utterances, pa_emb_num_pool_frames(w, max_samples)) fp32 weights at pool resolution, or NULL (unweighted);
+ * columns past an utterance's own pool frames are ignored.  emb: (num_utterances, embed_dim).
+ * Checkpoints with fbank_centering_span are refused (return 3): run them one length at a time. */
+size_t pa_emb_ragged_workspace_bytes(const pa_emb_weights* w, int num_utterances, int max_samples);
+int pa_emb_forward_ragged(const pa_emb_weights* w, const float* wav, int64_t wav_len, const int64_t* offsets,
+                          const int32_t* lengths, int num_utterances, int max_samples, const float* masks, float* emb,
+                          void* workspace, size_t workspace_bytes, void* stream);
+
 /* Numerical guard of the Winograd paths (weights.EmbeddingPack runs it once per loaded checkpoint; the reference has
  * no counterpart: its convolutions are torch's direct fp32 ones, resnet.py:92-107).  The chunks go through a
  * BasicBlock network in which every stride-1 3x3 convolution is evaluated by the DIRECT kernel (whose output feeds
@@ -250,6 +261,18 @@ int pa_conv3x3_wino_rows(const float* X, int B, int H, int W, int cin, const flo
                          const float* R, float* Y, int cout, int relu, int y_first, void* stream);
 int pa_stats_pool(const float* feat, int B, int Fh, int Tp, int C, const float* masks, int S, int Fm,
                   const int* nearest_idx, float* stats, void* stream);
+/* Pieces of pa_emb_forward_ragged.  Valid width of utterance b at a map with `halvings` stride-2 stages behind it:
+ * Wv_b = 1 + (lengths[b] - 400) / 160, then (Wv - 1) / 2 + 1 per stage.
+ * pa_fbank_ragged: (B, T, nmel) out, T = frames of max_samples; each utterance centred on its own mean, frames past
+ *   its own zero.  pa_zero_tail_cols: x (B, H, W, C) NHWC, C % 4 == 0, 16-byte aligned: columns [Wv_b, W) <- 0.
+ *   pa_stats_pool_ragged: pa_stats_pool with S = 1 over columns [0, Wv_b) of utterance b; masks (B, ld_masks) at
+ *   pool resolution or NULL. */
+int pa_fbank_ragged(const float* wav, long wav_len, const int64_t* offsets, const int32_t* lengths, int B,
+                    int max_samples, const float* window, const float* tw256, const float* tw512, const float* mel_w,
+                    const int* mel_lo, const int* mel_hi, int nmel, float* out, void* stream);
+int pa_zero_tail_cols(float* x, int B, int H, int W, int C, const int32_t* lengths, int halvings, void* stream);
+int pa_stats_pool_ragged(const float* feat, int B, int Fh, int W, int C, const int32_t* lengths, int halvings,
+                         const float* masks, int ld_masks, float* stats, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * SSeRiouSS segmentation model: replaces SSeRiouSS.forward (models/segmentation/SSeRiouSS.py:289-328) =

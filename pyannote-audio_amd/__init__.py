@@ -14,7 +14,7 @@ from .inference import Inference  # noqa: E402,F401
 from .clustering import (AgglomerativeClustering, Clustering, KMeansClustering, OracleClustering,  # noqa: E402,F401
                          VBxClustering)
 from .plda import PLDA  # noqa: E402,F401
-from .speaker_verification import PretrainedSpeakerEmbedding  # noqa: E402,F401
+from .speaker_verification import PretrainedSpeakerEmbedding, SpeakerEmbedding  # noqa: E402,F401
 from .speaker_diarization import SpeakerDiarization, DiarizeOutput  # noqa: E402,F401
 from .voice_activity_detection import VoiceActivityDetection  # noqa: E402,F401
 from .hook import ArtifactHook, Hooks, ProgressHook, TimingHook  # noqa: E402,F401

@@ -24,6 +24,9 @@ __device__ __forceinline__ cplx cmul(cplx a, cplx b) {
 
 // tables (device): window[400]; tw256[256] = exp(-2 pi i m / 256); tw512[257] = exp(-2 pi i k / 512);
 // mel_w[nmel][257] dense fp32 (torchaudio layout, right column zero), mel_lo/hi[nmel] non-zero range.
+// kRagged: chunk b is utterance b of a ragged batch -- it starts at sample offs[b] and has T_b = 1 + (lens[b] - 400) / 160
+// frames; frames T_b .. T - 1 are not computed (k_fbank_center_ragged writes them).  k_fbank<false> ignores offs / lens.
+template <bool kRagged>
 __global__ __launch_bounds__(256) void k_fbank(const float* __restrict__ wav, long wav_len,
                                                long chunk_stride, int T, float scale, float preemph,
                                                const float* __restrict__ window,
@@ -32,7 +35,8 @@ __global__ __launch_bounds__(256) void k_fbank(const float* __restrict__ wav, lo
                                                const float* __restrict__ mel_w,
                                                const int* __restrict__ mel_lo,
                                                const int* __restrict__ mel_hi, int nmel, float eps,
-                                               float* __restrict__ out) {
+                                               float* __restrict__ out, const int64_t* __restrict__ offs,
+                                               const int* __restrict__ lens) {
   __shared__ float2 bufA[FB_FPB][FB_HALF];
   __shared__ float2 bufB[FB_FPB][FB_HALF];
   __shared__ float2 s_tw256[FB_HALF];
@@ -40,8 +44,16 @@ __global__ __launch_bounds__(256) void k_fbank(const float* __restrict__ wav, lo
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   const int b = blockIdx.y;
   const int t = blockIdx.x * FB_FPB + wv;
+  int Tb = T;
+  long base = (long)b * chunk_stride + (long)t * FB_SHIFT;
+  if constexpr (kRagged) {
+    const int n = lens[b];
+    Tb = n < FB_WIN ? 0 : 1 + (n - FB_WIN) / FB_SHIFT;
+    if ((int)blockIdx.x * FB_FPB >= Tb) return;   // the whole block is padding (uniform: before any barrier)
+    base = offs[b] + (long)t * FB_SHIFT;
+  }
   for (int i = tid; i < FB_HALF; i += 256) s_tw256[i] = tw256[i];
-  const bool active = t < T;
+  const bool active = t < Tb;
   float2 w512[5];     // twiddles of the real unpack: fetched now, used after the FFT
 #pragma unroll
   for (int i = 0; i < 5; ++i) w512[i] = lane + 64 * i <= FB_HALF ? tw512[lane + 64 * i] : make_float2(0.f, 0.f);
@@ -49,7 +61,6 @@ __global__ __launch_bounds__(256) void k_fbank(const float* __restrict__ wav, lo
   // ---- load + scale, DC removal
   float x[7];
   float s = 0.f;
-  const long base = (long)b * chunk_stride + (long)t * FB_SHIFT;
 #pragma unroll
   for (int i = 0; i < 7; ++i) {
     const int j = lane + 64 * i;
@@ -179,6 +190,29 @@ __global__ __launch_bounds__(320) void k_fbank_center(float* __restrict__ fb, in
     for (int t = p; t < T; t += 4) x[(long)t * nmel + m] -= mean;
 }
 
+// k_fbank_center of a ragged batch: the mean over utterance b's own T_b frames is subtracted from them, and frames
+// T_b .. T - 1 are written as zero (the padding every later 3x3 convolution must see as zero, emb_forward.cpp).  The
+// sums run in the order of k_fbank_center, so each utterance is centred exactly as it is alone.
+__global__ __launch_bounds__(320) void k_fbank_center_ragged(float* __restrict__ fb, int T, int nmel,
+                                                             const int* __restrict__ lens) {
+  __shared__ float part[4][80];
+  const int b = blockIdx.x;
+  const int m = threadIdx.x % 80, p = threadIdx.x / 80;
+  const int n = lens[b];
+  const int Tb = n < FB_WIN ? 0 : 1 + (n - FB_WIN) / FB_SHIFT;
+  float* x = fb + (long)b * T * nmel;
+  float s = 0.f;
+  if (m < nmel)
+    for (int t = p; t < Tb; t += 4) s += x[(long)t * nmel + m];
+  part[p][m] = s;
+  __syncthreads();
+  const float mean = (part[0][m] + part[1][m] + part[2][m] + part[3][m]) / (float)Tb;
+  if (m < nmel) {
+    for (int t = p; t < Tb; t += 4) x[(long)t * nmel + m] -= mean;
+    for (int t = Tb + p; t < T; t += 4) x[(long)t * nmel + m] = 0.f;
+  }
+}
+
 // Running-mean centring (wespeaker/__init__.py:141-157, fbank_centering_span given): out = x - avg_pool1d(x, K, stride 1,
 // padding K / 2, count_include_pad=False) along the frames.  One workgroup per (chunk, group of 16 mel bins, tile of
 // FC_TT frames): the tile and its K / 2 frames of halo on either side go to LDS once ([frame][16 bins]: the 64 lanes of a
@@ -250,14 +284,36 @@ int pa_fbank(const float* wav, long wav_len, long chunk_stride, int B, int N, co
   hipStream_t st = (hipStream_t)stream;
   pa::ProfScope prof("k_fbank", stream, (double)B * T * (5.0 * 512 * 9 + 2.0 * 257 * 3 + 2.0 * 257 * 2),
                      4.0 * B * N + 4.0 * B * T * nmel * (center ? 3 : 1));
-  hipLaunchKernelGGL(pa::k_fbank, dim3(pa::cdiv(T, pa::FB_FPB), B), dim3(256), 0, st, wav, wav_len,
+  hipLaunchKernelGGL(pa::k_fbank<false>, dim3(pa::cdiv(T, pa::FB_FPB), B), dim3(256), 0, st, wav, wav_len,
                      chunk_stride, T, 32768.0f, 0.97f, window, (const float2*)tw256,
-                     (const float2*)tw512, mel_w, mel_lo, mel_hi, nmel, 1.1920928955078125e-07f, out);
+                     (const float2*)tw512, mel_w, mel_lo, mel_hi, nmel, 1.1920928955078125e-07f, out,
+                     (const int64_t*)nullptr, (const int*)nullptr);
   PA_CHECK_LAUNCH("pa_fbank");
   if (center) {
     hipLaunchKernelGGL(pa::k_fbank_center, dim3(B), dim3(320), 0, st, out, T, nmel);
     PA_CHECK_LAUNCH("pa_fbank_center");
   }
+  return 0;
+}
+
+// pa_fbank over a ragged batch (utterance b = wav[offsets[b], offsets[b] + lengths[b]), frames padded to those of
+// max_samples), always centred on each utterance's own mean; see include/pyannote_amd.h
+int pa_fbank_ragged(const float* wav, long wav_len, const int64_t* offsets, const int32_t* lengths, int B,
+                    int max_samples, const float* window, const float* tw256, const float* tw512, const float* mel_w,
+                    const int* mel_lo, const int* mel_hi, int nmel, float* out, void* stream) {
+  PA_REQUIRE(nmel <= 80, "pa_fbank_ragged: at most 80 mel bins are built (got %d)", nmel);
+  if (B <= 0) return 0;
+  PA_REQUIRE(max_samples >= pa::FB_WIN, "pa_fbank_ragged: %d samples is shorter than one 25 ms frame", max_samples);
+  const int T = 1 + (max_samples - pa::FB_WIN) / pa::FB_SHIFT;
+  hipStream_t st = (hipStream_t)stream;
+  pa::ProfScope prof("k_fbank_ragged", stream, (double)B * T * (5.0 * 512 * 9 + 2.0 * 257 * 3 + 2.0 * 257 * 2),
+                     4.0 * B * max_samples + 12.0 * B * T * nmel);
+  hipLaunchKernelGGL(pa::k_fbank<true>, dim3(pa::cdiv(T, pa::FB_FPB), B), dim3(256), 0, st, wav, wav_len, 0L, T,
+                     32768.0f, 0.97f, window, (const float2*)tw256, (const float2*)tw512, mel_w, mel_lo, mel_hi, nmel,
+                     1.1920928955078125e-07f, out, offsets, (const int*)lengths);
+  PA_CHECK_LAUNCH("pa_fbank_ragged");
+  hipLaunchKernelGGL(pa::k_fbank_center_ragged, dim3(B), dim3(320), 0, st, out, T, nmel, (const int*)lengths);
+  PA_CHECK_LAUNCH("pa_fbank_center_ragged");
   return 0;
 }
 

@@ -128,14 +128,28 @@ size_t pa_emb_workspace_bytes(const pa_emb_weights* w, int num_chunks, int num_s
 
 extern "C" int pa_absmax_diff(const float* got, const float* ref, long n, float* out2, void* stream);   // emb_pool.hip
 
+// Ragged batches (pa_emb_forward_ragged: `lengths` != NULL): utterance b has lengths[b] samples at wav[offsets[b]],
+// and the maps are padded to the longest utterance (T = the frames of num_samples).  THE ZERO-PADDING RULE: every
+// tensor that a 3x3 convolution reads holds zeros in the columns past its utterance's valid width Wv_b (T_b, then
+// (W - 1) / 2 + 1 per stride-2 layer).  Every valid output column then sees exactly the zero padding the reference
+// applies to that utterance alone, so the convolution kernels (F(4x4), F(2x2), direct, stem, GEMMs) stay unchanged and
+// compute over the padded map; what they write into padded columns is garbage until the next k_zero_tail.
+//   fbank       frames past T_b are zero after centring (k_fbank_center_ragged)
+//   BasicBlock  zero after the stem, after each block's first convolution and after each block output
+//   Bottleneck  zero after each first 1x1 GEMM (t1); the 1x1 convolutions and the stride-2 shortcut read only valid
+//               columns for a valid output (2 o <= Wv_in - 1), so the stem and block outputs need no zeroing
+//   pooling     over each utterance's Wv_b valid pool columns only (k_stats_pool_ragged)
+
 // `calib` (pa_emb_calibrate_winograd): every stride-1 3x3 convolution of a BasicBlock network runs through the
 // DIRECT kernel -- whose result the following layers see -- and, beside it, through each Winograd image its block
 // carries; calib[4 (2 blk + j) ...] = {max |direct|, max |F(4x4) - direct|, max |direct|, max |F(2x2) - direct|}.
 static int emb_forward_impl(const pa_emb_weights* w, const float* wav, int64_t wav_len, int64_t chunk_stride,
                             int num_chunks, int num_samples, const float* masks, int num_masks, int mask_frames,
                             const int32_t* nearest_idx, float* emb, void* workspace, size_t workspace_bytes,
-                            void* stream, float* calib) {
+                            void* stream, float* calib, const int64_t* offsets = nullptr,
+                            const int32_t* lengths = nullptr) {
   if (num_chunks <= 0) return 0;
+  const bool ragged = lengths != nullptr;
   EmbPlan p;
   if (w->num_layers != 4 || !make_plan(w, num_chunks, num_samples, masks ? num_masks : 1, &p, calib != nullptr)) {
     pa::set_error("pa_emb_forward: %d samples is too short (fbank needs >= 400) or bad layer count",
@@ -160,8 +174,20 @@ static int emb_forward_impl(const pa_emb_weights* w, const float* wav, int64_t w
   // checkpoint hyper-parameter -- the running mean of fb_center_kernel frames, out of place into the second
   // activation buffer (free until the first residual block), which the stem then reads
   const int span = w->fb_center_kernel;
-  RUN(pa_fbank(wav, wav_len, chunk_stride, B, p.N, w->fb_window, w->fb_tw256, w->fb_tw512, w->fb_mel_w,
-               w->fb_mel_lo, w->fb_mel_hi, w->num_mel, ws + p.fbank, span == 0 ? 1 : 0, stream));
+  if (ragged && span != 0) {
+    pa::set_error("pa_emb_forward_ragged: fbank_centering_span checkpoints run one launch sequence per length");
+    return 3;
+  }
+  if (ragged)
+    RUN(pa_fbank_ragged(wav, wav_len, offsets, lengths, B, p.N, w->fb_window, w->fb_tw256, w->fb_tw512, w->fb_mel_w,
+                        w->fb_mel_lo, w->fb_mel_hi, w->num_mel, ws + p.fbank, stream));
+  else
+    RUN(pa_fbank(wav, wav_len, chunk_stride, B, p.N, w->fb_window, w->fb_tw256, w->fb_tw512, w->fb_mel_w,
+                 w->fb_mel_lo, w->fb_mel_hi, w->num_mel, ws + p.fbank, span == 0 ? 1 : 0, stream));
+  // ragged batches: zero the padded columns of an H x W x C map of layer `l` (l = 0: stem / layer 1 resolution)
+  auto zero_tail = [&](float* X, int l, int C) -> int {
+    return ragged ? pa_zero_tail_cols(X, B, p.Hs[l], p.Ws[l], C, lengths, l > 0 ? l - 1 : 0, stream) : 0;
+  };
   float* cur = ws + p.act[0];
   float* f1 = ws + p.act[1];
   float* f2 = ws + p.act[2];
@@ -171,6 +197,7 @@ static int emb_forward_impl(const pa_emb_weights* w, const float* wav, int64_t w
     feats = f1;
   }
   RUN(pa_resnet_stem(feats, B, p.T, p.F, w->stem_w, w->stem_shift, cur, stream));
+  if (!w->bottleneck) RUN(zero_tail(cur, 0, w->planes[0]));
 
   // a stride-1 3x3 convolution (+ shift, residual R, ReLU) of a BasicBlock: F(4x4) where it pays, else F(2x2), else
   // the direct kernel -- as far as the block carries the images (the numerical guard of EmbeddingPack removes them)
@@ -226,6 +253,7 @@ static int emb_forward_impl(const pa_emb_weights* w, const float* wav, int64_t w
         float* t2 = tmp + p.t2_off;
         RUN(pa_gemm_tn_ex(cur, cin, w->blk_w1[blk], cin, w->blk_shift1[blk], nullptr, t1, planes, B * H * W,
                           planes, cin, 2, 0, stream));
+        RUN(zero_tail(t1, stride == 2 ? l : l + 1, planes));
         if (stride == 1 && w->blk_u2[blk] != nullptr)
           RUN(pa_conv3x3_wino(t1, B, H, W, planes, w->blk_u2[blk], w->blk_shift2[blk], nullptr, t2, planes, 1,
                               stream));
@@ -267,6 +295,7 @@ static int emb_forward_impl(const pa_emb_weights* w, const float* wav, int64_t w
         // out = relu(bn2(conv2(relu(bn1(conv1_s(x))))) + bn_sc(conv1x1_s(x)))   (resnet.py:140-145)
         RUN(pa_conv3x3(cur, B, H, W, cin, w->blk_w1[blk], w->blk_shift1[blk], nullptr, f1, cout, stride,
                        1, stream));
+        RUN(zero_tail(f1, l + 1, cout));
         const size_t q = (size_t)B * Ho * Wo * cin;
         float* R = f2 + ((q + 63) & ~(size_t)63);
         // (the 1x1 stride-2 shortcut reads its pixels in place: no gathered copy)
@@ -277,6 +306,7 @@ static int emb_forward_impl(const pa_emb_weights* w, const float* wav, int64_t w
                          stream));
         RUN(conv_s1(f1, Ho, Wo, cout, w->blk_v2[blk], w->blk_u2[blk], w->blk_w2[blk], w->blk_shift2[blk], R, cur, cout,
                     2 * blk + 1));
+        RUN(zero_tail(cur, l + 1, cout));
       } else {
         if (stride != 1 || cin != cout) {
           pa::set_error("pa_emb_forward: block %d needs a shortcut conv but none was given", blk);
@@ -284,8 +314,10 @@ static int emb_forward_impl(const pa_emb_weights* w, const float* wav, int64_t w
         }
         RUN(conv_s1(cur, H, W, cin, w->blk_v1[blk], w->blk_u1[blk], w->blk_w1[blk], w->blk_shift1[blk], nullptr, f1,
                     cout, 2 * blk));
+        RUN(zero_tail(f1, l + 1, cout));
         RUN(conv_s1(f1, H, W, cout, w->blk_v2[blk], w->blk_u2[blk], w->blk_w2[blk], w->blk_shift2[blk], cur, f2, cout,
                     2 * blk + 1));
+        RUN(zero_tail(f2, l + 1, cout));
         float* t = cur;
         cur = f2;
         f2 = t;
@@ -296,7 +328,10 @@ static int emb_forward_impl(const pa_emb_weights* w, const float* wav, int64_t w
   const int L = w->num_layers;
   const int S = p.S;
   const int cfin = w->planes[L - 1] * (w->bottleneck ? 4 : 1);
-  RUN(pa_stats_pool(cur, B, p.Hs[L], p.Ws[L], cfin, masks, S, mask_frames, nearest_idx, ws + p.stats, stream));
+  if (ragged)
+    RUN(pa_stats_pool_ragged(cur, B, p.Hs[L], p.Ws[L], cfin, lengths, L - 1, masks, p.Ws[L], ws + p.stats, stream));
+  else
+    RUN(pa_stats_pool(cur, B, p.Hs[L], p.Ws[L], cfin, masks, S, mask_frames, nearest_idx, ws + p.stats, stream));
   const int D2 = 2 * cfin * p.Hs[L];
   RUN(pa_gemm_tn(ws + p.stats, D2, w->seg1_w, D2, w->seg1_b, emb, w->embed_dim, B * S, w->embed_dim, D2,
                  0, 0, stream));
@@ -312,6 +347,23 @@ int pa_emb_forward(const pa_emb_weights* w, const float* wav, int64_t wav_len, i
                    void* stream) {
   return emb_forward_impl(w, wav, wav_len, chunk_stride, num_chunks, num_samples, masks, num_masks, mask_frames,
                           nearest_idx, emb, workspace, workspace_bytes, stream, nullptr);
+}
+
+size_t pa_emb_ragged_workspace_bytes(const pa_emb_weights* w, int num_utterances, int max_samples) {
+  EmbPlan p;
+  if (!make_plan(w, num_utterances, max_samples, 1, &p)) return 0;
+  return p.total * sizeof(float);
+}
+
+int pa_emb_forward_ragged(const pa_emb_weights* w, const float* wav, int64_t wav_len, const int64_t* offsets,
+                          const int32_t* lengths, int num_utterances, int max_samples, const float* masks, float* emb,
+                          void* workspace, size_t workspace_bytes, void* stream) {
+  if (offsets == nullptr || lengths == nullptr) {
+    pa::set_error("pa_emb_forward_ragged: offsets and lengths are required");
+    return 3;
+  }
+  return emb_forward_impl(w, wav, wav_len, 0, num_utterances, max_samples, masks, 1, 0, nullptr, emb, workspace,
+                          workspace_bytes, stream, nullptr, offsets, lengths);
 }
 
 size_t pa_emb_calibrate_workspace_bytes(const pa_emb_weights* w, int num_chunks, int num_samples) {

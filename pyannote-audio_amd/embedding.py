@@ -3,8 +3,9 @@
 from __future__ import annotations
 
 import os
-from typing import Optional
+from typing import Optional, Sequence
 
+import numpy as np
 import torch
 import torch.nn.functional as F
 
@@ -118,17 +119,141 @@ class EmbeddingEngine:
             c0 += nb
         return emb
 
+    #: most pool frames `pa_stats_pool` (and so `forward_strided`) takes; longer single-weight inputs go through the
+    #: ragged pooling, which has no such limit
+    POOL_MAX_FRAMES = 512
+    #: longest / shortest utterance of one ragged bucket (the padding stays below 1 - 1 / RAGGED_RATIO of the samples)
+    RAGGED_RATIO = 1.10
+    #: utterances per ragged launch group at most (the grids carry the batch in their y / z dimension)
+    RAGGED_MAX_GROUP = 16384
+    #: whether the front end reads samples past the end of the waveform as zeros (k_fbank does): the orphan chunk
+    #: of a sliding window is then the reference's zero-padded chunk without a copy
+    READS_PAST_END_AS_ZERO = True
+
     def forward(self, waveforms: torch.Tensor, weights: torch.Tensor | None = None) -> torch.Tensor:
         """(B,1,N) [, (B,Fm) or (B,S,Fm)] -> (B,D) or (B,S,D): the reference forward contract."""
         B, ch, N = waveforms.shape
         assert ch == 1
         x = waveforms.to(self.pack.device, torch.float32).contiguous().view(-1)
+        if self._ragged_supported() and N >= 400 and self.num_pool_frames(N) > self.POOL_MAX_FRAMES and \
+                (weights is None or weights.dim() == 2):
+            # long inputs (whole files): the ragged path with equal lengths, whose pooling takes any length
+            masks = None if weights is None else [m for m in weights.to(self.pack.device, torch.float32)]
+            return self.forward_ragged(x, [i * N for i in range(B)], [N] * B, masks)
         squeeze = weights is None or weights.dim() == 2
         m = None
         if weights is not None:
             m = weights.unsqueeze(1) if weights.dim() == 2 else weights
         emb = self.forward_strided(x, N, B, N, m)
         return emb[:, 0] if squeeze else emb
+
+
+    # ------------------------------------------------------------------------------ ragged batches
+    def _ragged_supported(self) -> bool:
+        """`pa_emb_forward_ragged` covers global fbank centring; fbank_centering_span checkpoints fall back"""
+        return self.pack.struct.fb_center_kernel == 0
+
+    def pool_weights(self, mask: torch.Tensor, num_samples: int) -> torch.Tensor:
+        """weights of any frame rate -> the pool frames of `num_samples`, by torch's own nearest mapping"""
+        mask = mask.to(self.pack.device, torch.float32).reshape(-1)
+        return mask[self.nearest_index(mask.numel(), self.num_pool_frames(num_samples)).long()]
+
+    @ffi.on_device(lambda self, *a, **k: self.pack.device)
+    def forward_ragged(self, wav: torch.Tensor, offsets: Sequence[int], lengths: Sequence[int],
+                       masks: Optional[Sequence[Optional[torch.Tensor]]] = None) -> torch.Tensor:
+        """Utterances of different lengths in one pass: utterance b = wav[offsets[b] : offsets[b] + lengths[b]] of a
+        1-D fp32 device waveform; masks: None, or one 1-D weight tensor (any frame rate, mapped to the pool frames
+        like F.interpolate(mode="nearest")) or None per utterance.  -> (B, D), in input order; row b equals the
+        embedding of utterance b on its own.
+
+        The utterances are sorted by length and bucketed so that within a bucket the longest is at most RAGGED_RATIO
+        times the shortest; each bucket runs as launch groups of `_group_size` at its longest length."""
+        offsets = np.asarray(offsets, dtype=np.int64).reshape(-1)
+        lengths = np.asarray(lengths, dtype=np.int64).reshape(-1)
+        B = lengths.size
+        if offsets.size != B or (masks is not None and len(masks) != B):
+            raise ValueError("offsets, lengths (and masks) must have one entry per utterance")
+        self._check_lengths(lengths)
+        if B and (offsets.min() < 0 or (offsets + lengths).max() > wav.numel()):
+            raise ValueError("an utterance reaches outside the waveform")
+        pooled = None
+        if masks is not None:
+            pooled = [None if m is None else self.pool_weights(m, int(n)) for m, n in zip(masks, lengths)]
+        if not self._ragged_supported():
+            return self._forward_by_length(wav, offsets, lengths, pooled)
+        lib = ffi.load()
+        w = self.pack.struct
+        dev = self.pack.device
+        order = np.argsort(lengths, kind="stable")
+        out_sorted = torch.empty((B, self.embed_dim), dtype=torch.float32, device=dev)
+        for b0, b1 in length_buckets(lengths[order], self.RAGGED_RATIO):
+            n_max = int(lengths[order[b1 - 1]])
+            per_group = min(self._group_size(b1 - b0, n_max, 1), self.RAGGED_MAX_GROUP)
+            groups = -(-(b1 - b0) // per_group)
+            per_group = -(-(b1 - b0) // groups)          # split evenly
+            for g0 in range(b0, b1, per_group):
+                g1 = min(g0 + per_group, b1)
+                sel = order[g0:g1]
+                n_max = int(lengths[sel].max())
+                off_d = torch.from_numpy(offsets[sel].copy()).to(dev)
+                len_d = torch.from_numpy(lengths[sel].astype(np.int32)).to(dev)
+                m = None
+                if pooled is not None:
+                    m = torch.ones((g1 - g0, self.num_pool_frames(n_max)), dtype=torch.float32, device=dev)
+                    for j, i in enumerate(sel):
+                        if pooled[i] is not None:
+                            m[j, :pooled[i].numel()] = pooled[i]
+                ws = self._workspace(lib.pa_emb_ragged_workspace_bytes(w, g1 - g0, n_max))
+                rc = lib.pa_emb_forward_ragged(
+                    w, ffi.c_fp(wav.data_ptr()), wav.numel(), ffi.ptr(off_d), ffi.ptr(len_d), g1 - g0, n_max,
+                    ffi.ptr(m) if m is not None else None, ffi.ptr(out_sorted[g0:g1]), ffi.ptr(ws), ws.numel(),
+                    ffi.stream())
+                ffi.check(rc, "pa_emb_forward_ragged")
+        out = torch.empty_like(out_sorted)
+        out[torch.from_numpy(order).to(dev)] = out_sorted
+        return out
+
+    @property
+    def embed_dim(self) -> int:
+        return self.pack.struct.embed_dim
+
+    @staticmethod
+    def _check_lengths(lengths: np.ndarray, minimum: int = 400):
+        short = np.flatnonzero(lengths < minimum)
+        if short.size:
+            i = int(short[0])
+            raise ValueError(f"utterance {i} has {int(lengths[i])} samples: shorter than one fbank frame "
+                             f"({minimum} samples)")
+
+    def _forward_by_length(self, wav: torch.Tensor, offsets: np.ndarray, lengths: np.ndarray,
+                           pooled: Optional[list]) -> torch.Tensor:
+        """fallback of `forward_ragged`: one `forward_strided` launch sequence per distinct length, the utterances
+        of that length gathered contiguously, their weights already at pool resolution (identity index)"""
+        dev = self.pack.device
+        out = torch.empty((lengths.size, self.embed_dim), dtype=torch.float32, device=dev)
+        for n in np.unique(lengths):
+            n = int(n)
+            sel = np.flatnonzero(lengths == n)
+            buf = torch.cat([wav[int(offsets[i]):int(offsets[i]) + n] for i in sel])
+            m = None
+            if pooled is not None:
+                tp = self.num_pool_frames(n)
+                m = torch.stack([torch.ones(tp, device=dev) if pooled[i] is None else pooled[i] for i in sel])[:, None]
+            emb = self.forward_strided(buf, n, sel.size, n, m)
+            out[torch.from_numpy(sel).to(dev)] = emb[:, 0]
+        return out
+
+
+def length_buckets(sorted_lengths: Sequence[int], ratio: float = EmbeddingEngine.RAGGED_RATIO) -> list:
+    """[(begin, end)) ranges of ascending lengths in which the longest is at most `ratio` x the shortest"""
+    L = np.asarray(sorted_lengths)
+    buckets, b0 = [], 0
+    while b0 < L.size:
+        b1 = int(np.searchsorted(L, ratio * L[b0], side="right"))
+        b1 = max(b1, b0 + 1)
+        buckets.append((b0, b1))
+        b0 = b1
+    return buckets
 
 
 class XVectorEngine(EmbeddingEngine):
@@ -141,8 +266,23 @@ class XVectorEngine(EmbeddingEngine):
         self._ws = None
         self._idx_cache = {}
 
+    READS_PAST_END_AS_ZERO = False    # pa_row_stats normalises over the samples present only
+
     def num_pool_frames(self, num_samples: int) -> int:
         return ffi.load().pa_xvec_num_frames(self.pack.struct, num_samples)
+
+    def _ragged_supported(self) -> bool:
+        return False        # InstanceNorm layers are per utterance: one launch sequence per length
+
+    @property
+    def embed_dim(self) -> int:
+        return self.pack.struct.dimension
+
+    def _check_lengths(self, lengths: np.ndarray, minimum: int = 400):
+        short = [i for i, n in enumerate(lengths) if self.num_pool_frames(int(n)) < 1]
+        if short:
+            raise ValueError(f"utterance {short[0]} has {int(lengths[short[0]])} samples: too short for SincNet + "
+                             "the TDNN stack")
 
     @ffi.on_device(lambda self, *a, **k: self.pack.device)
     def forward_strided(self, wav: torch.Tensor, chunk_stride: int, num_chunks: int, num_samples: int,

@@ -169,6 +169,14 @@ _OPTIONAL: list[tuple] = [
     ("pa_emb_workspace_bytes", [C.POINTER(EmbWeights), C.c_int, C.c_int, C.c_int], C.c_size_t),
     ("pa_emb_forward", [C.POINTER(EmbWeights), c_fp, C.c_int64, C.c_int64, C.c_int, C.c_int, c_fp,
                         C.c_int, C.c_int, c_fp, c_fp, c_fp, C.c_size_t, c_fp], C.c_int),
+    ("pa_emb_ragged_workspace_bytes", [C.POINTER(EmbWeights), C.c_int, C.c_int], C.c_size_t),
+    ("pa_emb_forward_ragged", [C.POINTER(EmbWeights), c_fp, C.c_int64, c_fp, c_fp, C.c_int, C.c_int, c_fp, c_fp,
+                               c_fp, C.c_size_t, c_fp], C.c_int),
+    ("pa_fbank_ragged", [c_fp, C.c_long, c_fp, c_fp, C.c_int, C.c_int, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, C.c_int,
+                         c_fp, c_fp], C.c_int),
+    ("pa_zero_tail_cols", [c_fp, C.c_int, C.c_int, C.c_int, C.c_int, c_fp, C.c_int, c_fp], C.c_int),
+    ("pa_stats_pool_ragged", [c_fp, C.c_int, C.c_int, C.c_int, C.c_int, c_fp, C.c_int, c_fp, C.c_int, c_fp, c_fp],
+     C.c_int),
     ("pa_emb_calibrate_workspace_bytes", [C.POINTER(EmbWeights), C.c_int, C.c_int], C.c_size_t),
     ("pa_emb_calibrate_winograd", [C.POINTER(EmbWeights), c_fp, C.c_int64, C.c_int64, C.c_int, C.c_int, c_fp, c_fp,
                                    c_fp, C.c_size_t, c_fp], C.c_int),

@@ -89,6 +89,13 @@ class Inference(BaseInference):
         if chunks.dim() != 3 or chunks.shape[1] != 1:
             raise ValueError("`chunks` must be a (batch_size, 1, num_samples) tensor (mono models)")
         batch, _, num_samples = chunks.shape
+        if self.model.specifications.resolution == Resolution.CHUNK:
+            # one vector per chunk (embedding models): no conversion (core/inference.py:182-215)
+            try:
+                return self.model(chunks.to(self.model.device, torch.float32)).cpu().numpy()
+            except (MemoryError, torch.OutOfMemoryError):
+                raise MemoryError(f"batch_size ({self.batch_size: d}) is probably too large. "
+                                  f"Try with a smaller value until memory error disappears.") from None
         flat = chunks.to(self.model.device, torch.float32).contiguous().view(-1)
         convert = bool(self.model.specifications.powerset) and not self.skip_conversion
         logp, ml = self._forward(flat, num_samples, batch, num_samples, want_logp=not convert,
@@ -119,9 +126,8 @@ class Inference(BaseInference):
         """waveform: (1, num_samples), host or device.  `chunk_range` restricts processing to chunks
         [begin, end) (multi-GPU sharding); geometry is always that of the whole file."""
         specifications = self.model.specifications
-        if specifications.resolution != Resolution.FRAME:
-            raise NotImplementedError("the accelerated sliding window covers frame-level segmentation "
-                                      "models (powerset, as on the 3.1 hot path, or multi-label)")
+        if specifications.resolution == Resolution.CHUNK:
+            return self._slide_chunks(waveform, sample_rate, hook)
         window_size: int = self.model.audio.get_num_samples(self.duration)
         step_size: int = round(self.step * sample_rate)
         _, num_samples = waveform.shape
@@ -162,6 +168,43 @@ class Inference(BaseInference):
         if has_last_chunk:
             aggregated.data = aggregated.crop(Segment(0.0, num_samples / sample_rate), mode="loose")
         return aggregated
+
+    def _slide_chunks(self, waveform: torch.Tensor, sample_rate: int, hook: Optional[Callable]
+                      ) -> SlidingWindowFeature:
+        """chunk-level models (embeddings): one vector per chunk, no aggregation (core/inference.py:248-254,
+        :328-345).  All chunks go through the engine at once; `hook` is called as the reference's batch loop
+        calls it (:288-320)."""
+        window_size: int = self.model.audio.get_num_samples(self.duration)
+        step_size: int = round(self.step * sample_rate)
+        _, num_samples = waveform.shape
+        num_chunks, has_last_chunk = self.num_chunks(num_samples, window_size, step_size)
+        total = num_chunks + has_last_chunk
+        engine = self.model.engine
+        wav = waveform.to(self.model.device, torch.float32).contiguous().view(-1)
+        if hook is not None:
+            hook(completed=0, total=total)
+        parts = []
+        # the orphan last chunk is zero-padded (:266-273): front ends that read past the end as zeros take it
+        # in the same pass, the others get an explicitly padded copy
+        together = num_chunks + has_last_chunk if engine.READS_PAST_END_AS_ZERO else num_chunks
+        try:
+            if together:
+                parts.append(engine.forward_strided(wav, step_size, together, window_size)[:, 0])
+            if has_last_chunk and not engine.READS_PAST_END_AS_ZERO:
+                last = torch.zeros(window_size, dtype=torch.float32, device=wav.device)
+                tail = wav[num_chunks * step_size:]
+                last[:tail.numel()] = tail
+                parts.append(engine.forward_strided(last, window_size, 1, window_size)[:, 0])
+        except (MemoryError, torch.OutOfMemoryError):
+            raise MemoryError(f"batch_size ({self.batch_size: d}) is probably too large. "
+                              f"Try with a smaller value until memory error disappears.") from None
+        outputs = torch.cat(parts).cpu().numpy()
+        if hook is not None:
+            for c in range(0, num_chunks, self.batch_size):
+                hook(completed=c + self.batch_size, total=total)
+            if has_last_chunk:
+                hook(completed=total, total=total)
+        return SlidingWindowFeature(outputs, SlidingWindow(start=0.0, duration=self.duration, step=self.step))
 
     @staticmethod
     def num_chunks(num_samples: int, window_size: int, step_size: int) -> Tuple[int, bool]:

@@ -73,6 +73,9 @@ def get_class_by_name(class_name: str, default_module_name: Optional[str] = None
     if class_name.startswith("pyannote.audio.pipelines") and tokens[-1] == "SpeakerDiarization":
         from .speaker_diarization import SpeakerDiarization
         return SpeakerDiarization
+    if class_name.startswith("pyannote.audio.pipelines") and tokens[-1] == "SpeakerEmbedding":
+        from .speaker_verification import SpeakerEmbedding
+        return SpeakerEmbedding
     if class_name.startswith("pyannote.audio.pipelines") and tokens[-1] == "VoiceActivityDetection":
         from .voice_activity_detection import VoiceActivityDetection
         return VoiceActivityDetection

@@ -9,14 +9,15 @@ pass per chunk instead of one per (chunk, speaker))."""
 from __future__ import annotations
 
 from pathlib import Path
-from typing import Callable, Mapping, Optional, Union
+from typing import Callable, Iterable, Iterator, List, Mapping, Optional, Tuple, Union
 
 import numpy as np
 import torch
 
 from . import ffi
+from .audio import Audio, AudioFile
 from .model import Model
-from .pipeline import BaseInference
+from .pipeline import BaseInference, Pipeline
 
 PipelineModel = Union[Model, str, Mapping]
 
@@ -106,3 +107,71 @@ def PretrainedSpeakerEmbedding(embedding: PipelineModel, device: Optional[torch.
         raise NotImplementedError(f"{embedding}: SpeechBrain/NeMo embedding back-ends are out of scope")
     return PyannoteAudioPretrainedSpeakerEmbedding(embedding, device=device, token=token,
                                                    cache_dir=cache_dir)
+
+
+def vad_weights(scores: np.ndarray) -> np.ndarray:
+    """aggregated voice-activity scores (frames, 1) -> pooling weights (frames,): NaN -> 0, cubed (:848-852)"""
+    weights = np.array(scores, dtype=np.float32, copy=True)
+    weights[np.isnan(weights)] = 0.0
+    return (weights ** 3)[:, 0]
+
+
+class SpeakerEmbedding(Pipeline):
+    """One embedding per file, which is assumed to hold one speaker (pipelines/speaker_verification.py:781-856).
+
+    `SpeakerEmbedding(embedding, segmentation=None)`: with a segmentation model the statistics pooling is weighted by
+    the cubed voice-activity scores of the file (max over speakers of the aggregated scores).  `apply(file)` -> (1, D);
+    `apply_batch(files)` -> one (1, D) per file, in order, with all files of different lengths batched together
+    (`EmbeddingEngine.forward_ragged`)."""
+
+    def __init__(self, embedding: PipelineModel = None, segmentation: Optional[PipelineModel] = None, token=None,
+                 cache_dir=None):
+        super().__init__()
+        if embedding is None:
+            raise ValueError("`embedding` must be a local checkpoint (or a Model instance): Hugging Face "
+                             "defaults cannot be downloaded in this build.")
+        from .inference import Inference
+        from .voice_activity_detection import any_speaker
+        self.embedding = embedding
+        self.segmentation = segmentation
+        self.embedding_model_: Model = get_model(embedding, token=token, cache_dir=cache_dir)
+        if segmentation is not None:
+            segmentation_model = get_model(segmentation, token=token, cache_dir=cache_dir)
+            self._segmentation = Inference(segmentation_model, pre_aggregation_hook=any_speaker)
+
+    def _audio(self) -> Audio:
+        return Audio(self.embedding_model_.audio.sample_rate, mono="downmix")
+
+    def _weights(self, file: AudioFile) -> Optional[torch.Tensor]:
+        if self.segmentation is None:
+            return None
+        return torch.from_numpy(vad_weights(self._segmentation(file).data))
+
+    def apply(self, file: AudioFile) -> np.ndarray:
+        device = self.embedding_model_.device
+        waveform = self._audio()(file)[0][None].to(device)
+        weights = self._weights(file)
+        if weights is not None:
+            weights = weights[None].to(device)
+        return self.embedding_model_(waveform, weights=weights).cpu().numpy()
+
+    def apply_batch(self, files: Iterable[AudioFile]) -> List[np.ndarray]:
+        files = [Audio.validate_file(f) for f in files]
+        if not files:
+            return []
+        device = self.embedding_model_.device
+        audio = self._audio()
+        waves = [audio(f)[0].reshape(-1) for f in files]
+        lengths = [w.numel() for w in waves]
+        offsets = np.concatenate([[0], np.cumsum(lengths)[:-1]]).astype(np.int64)
+        wav = torch.cat(waves).to(device, torch.float32)
+        masks = None
+        if self.segmentation is not None:
+            masks = [self._weights(f) for f in files]
+        emb = self.embedding_model_.engine.forward_ragged(wav, offsets, lengths, masks).cpu().numpy()
+        return [emb[i:i + 1] for i in range(len(files))]
+
+    def _apply_batch(self, files: list, **kwargs) -> Iterator[Tuple[AudioFile, np.ndarray]]:
+        for f, embedding in zip(files, self.apply_batch(files, **kwargs)):
+            yield f, embedding
+
