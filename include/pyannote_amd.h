@@ -390,6 +390,52 @@ int pa_xvec_forward(const pa_xvec_weights* w, const float* wav, int64_t wav_len,
                     int num_chunks, int num_samples, const float* masks, int num_masks, int mask_frames,
                     const int32_t* nearest_idx, float* emb, void* workspace, size_t workspace_bytes,
                     void* stream);
+/* ------------------------------------------------------------------------------------------
+ * XVectorMFCC embedding model: replaces XVectorMFCC.forward (models/embedding/xvector.py:185-202) =
+ * torchaudio MFCC -> the same TDNN stack, pooling and Linear as XVectorSincNet.  The front end (csrc/mfcc.hip)
+ * is built for n_fft = win_length = 400, reflect padding, power 2, not normalized; the filter bank, window and DCT
+ * matrix are data (the checkpoint's torchaudio buffers).
+ * ---------------------------------------------------------------------------------------- */
+typedef struct pa_xvec_mfcc_weights {
+  int32_t n_fft;                       /* 400 */
+  int32_t hop_length;                  /* 1 .. 400 */
+  int32_t center;                      /* 1: frames reflect-padded by n_fft / 2 on each side of the chunk */
+  int32_t log_mels;                    /* 1: log(mel + 1e-6); 0: dB, clamped at the chunk's max - 80 dB */
+  int32_t n_mels;                      /* <= 256 */
+  int32_t n_mfcc;                      /* <= 64 */
+  int32_t dimension;                   /* embedding size */
+  int32_t tdnn_channels[PA_XVEC_TDNN]; /* as pa_xvec_weights */
+  int32_t tdnn_kernel[PA_XVEC_TDNN];
+  int32_t tdnn_dilation[PA_XVEC_TDNN];
+  const float* window;                 /* [400] */
+  const float* fft_tw;                 /* complex [200] exp(-2 pi i m / 200), then [201] exp(-2 pi i k / 400) */
+  const float* mel_w;                  /* [n_mels][201] = torchaudio's fb transposed */
+  const int32_t* mel_lo;               /* [n_mels] first / last non-zero bin of each filter (lo > hi: none) */
+  const int32_t* mel_hi;
+  const float* dct;                    /* [n_mels][64] torchaudio's dct_mat, zero past n_mfcc */
+  const float* tdnn_w[PA_XVEC_TDNN];   /* as pa_xvec_weights (cin_pad = 64 for layer 0) */
+  const float* tdnn_b[PA_XVEC_TDNN];
+  const float* bn_scale;
+  const float* bn_shift;
+  const float* emb_w;
+  const float* emb_b;
+} pa_xvec_mfcc_weights;
+
+/* frames left after the MFCC front end and the TDNN stack (XVectorMFCC.num_frames, xvector.py:96-126; 0 = too short,
+ * which includes a centred chunk of at most n_fft / 2 samples: torch's reflect padding refuses it) */
+int pa_xvec_mfcc_num_frames(const pa_xvec_mfcc_weights* w, int num_samples);
+size_t pa_xvec_mfcc_workspace_bytes(const pa_xvec_mfcc_weights* w, int num_chunks, int num_samples, int num_masks);
+/* the contract of pa_xvec_forward; samples past wav_len read as zero */
+int pa_xvec_mfcc_forward(const pa_xvec_mfcc_weights* w, const float* wav, int64_t wav_len, int64_t chunk_stride,
+                         int num_chunks, int num_samples, const float* masks, int num_masks, int mask_frames,
+                         const int32_t* nearest_idx, float* emb, void* workspace, size_t workspace_bytes,
+                         void* stream);
+/* the MFCC front end alone: out (num_chunks, frames, n_mfcc) = torchaudio's MFCC of each chunk, transposed;
+ * workspace: pa_xvec_mfcc_workspace_bytes(w, num_chunks, num_samples, 1) bytes suffice */
+int pa_mfcc_features(const pa_xvec_mfcc_weights* w, const float* wav, int64_t wav_len, int64_t chunk_stride,
+                     int num_chunks, int num_samples, float* out, void* workspace, size_t workspace_bytes,
+                     void* stream);
+
 /* StatsPool over the rows of a (tile, t, b16)-ordered activation matrix (models/blocks/pooling.py:64-130) */
 int pa_stats_pool_rows(const float* feat, int B, int T0, int Tp, int C, int ld, const float* masks, int S,
                        int Fm, const int* nearest_idx, float* stats, int ld_stats,

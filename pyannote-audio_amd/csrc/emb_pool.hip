@@ -174,6 +174,79 @@ __global__ __launch_bounds__(256) void k_stats_pool_rows(const float* __restrict
     }
 }
 
+// k_stats_pool_rows for more than POOLR_MAXT frames (XVectorMFCC: 787 pool frames per 10 s chunk at hop 200): the
+// same arithmetic in the same order, the S x Tp weights in dynamic LDS
+__global__ __launch_bounds__(256) void k_stats_pool_rows_long(const float* __restrict__ feat, int T0, int Tp, int Cc,
+                                                              int ld, const float* __restrict__ masks, int S, int Fm,
+                                                              const int* __restrict__ idx, float* __restrict__ stats,
+                                                              int ld_stats, const float* __restrict__ aff_scale,
+                                                              const float* __restrict__ aff_shift) {
+  extern __shared__ float wl[];   // [S][Tp]
+  __shared__ float v1s[POOL_MAXS], dens[POOL_MAXS];
+  const int b = blockIdx.y;
+  const int c = blockIdx.x * 256 + threadIdx.x;
+  for (int i = threadIdx.x; i < S * Tp; i += 256) {
+    const int s = i / Tp, t = i % Tp;
+    wl[i] = masks != nullptr ? masks[((long)b * S + s) * Fm + idx[t]] : 1.f;
+  }
+  __syncthreads();
+  if (threadIdx.x < S) {
+    const int s = threadIdx.x;
+    float a = 0.f, q = 0.f;
+    for (int t = 0; t < Tp; ++t) {
+      a += wl[s * Tp + t];
+      q += wl[s * Tp + t] * wl[s * Tp + t];
+    }
+    if (masks != nullptr) {
+      const float v1 = a + 1e-8f;
+      v1s[s] = v1;
+      dens[s] = v1 - q / v1 + 1e-8f;
+    } else {
+      v1s[s] = (float)Tp;
+      dens[s] = (float)(Tp - 1);
+    }
+  }
+  __syncthreads();
+  for (int i = 2 * Cc + threadIdx.x + blockIdx.x * 256; i < ld_stats; i += 256 * gridDim.x)
+    for (int s = 0; s < S; ++s) stats[((long)b * S + s) * ld_stats + i] = 0.f;
+  if (c >= Cc) return;
+  const float* x = feat + (((long)(b >> 4) * T0) * 16 + (b & 15)) * ld + c;
+  const long ts = 16L * ld;
+  const float sc = aff_scale != nullptr ? aff_scale[c] : 1.f, sh = aff_shift != nullptr ? aff_shift[c] : 0.f;
+  float m[POOL_MAXS];
+#pragma unroll
+  for (int s = 0; s < POOL_MAXS; ++s) m[s] = 0.f;
+  for (int t = 0; t < Tp; ++t) {
+    const float xv = fmaf(x[t * ts], sc, sh);
+#pragma unroll
+    for (int s = 0; s < POOL_MAXS; ++s)
+      if (s < S) m[s] = fmaf(xv, wl[s * Tp + t], m[s]);
+  }
+#pragma unroll
+  for (int s = 0; s < POOL_MAXS; ++s)
+    if (s < S) m[s] /= v1s[s];
+  float v[POOL_MAXS];
+#pragma unroll
+  for (int s = 0; s < POOL_MAXS; ++s) v[s] = 0.f;
+  for (int t = 0; t < Tp; ++t) {
+    const float xv = fmaf(x[t * ts], sc, sh);
+#pragma unroll
+    for (int s = 0; s < POOL_MAXS; ++s)
+      if (s < S) {
+        const float d = xv - m[s];
+        v[s] = fmaf(d * d, wl[s * Tp + t], v[s]);
+      }
+  }
+#pragma unroll
+  for (int s = 0; s < POOL_MAXS; ++s)
+    if (s < S) {
+      float* o = stats + ((long)b * S + s) * ld_stats;
+      o[c] = m[s];
+      o[Cc + c] = sqrtf(v[s] / dens[s]);
+    }
+}
+constexpr int POOLR_LONG_LDS = 144 * 1024;   // bytes of weights k_stats_pool_rows_long holds
+
 // calibration of the Winograd paths (pa_emb_calibrate_winograd): out[0] = max(out[0], max |ref|),
 // out[1] = max(out[1], max |got - ref|) over n floats.  Non-negative floats order like their bit patterns, so the
 // cross-workgroup maximum is an integer atomicMax; NaN in `got` counts as +inf.
@@ -213,6 +286,36 @@ int pa_stats_pool_rows(const float* feat, int B, int T0, int Tp, int C, int ld, 
   PA_CHECK_LAUNCH("pa_stats_pool_rows");
   return 0;
 }
+
+}  // extern "C"
+
+// pa_stats_pool_rows for any number of frames (the x-vector tail, csrc/xvec_forward.cpp): up to POOLR_MAXT frames the
+// same launch as pa_stats_pool_rows, beyond that k_stats_pool_rows_long
+PA_INTERNAL int pa_stats_pool_rows_any(const float* feat, int B, int T0, int Tp, int C, int ld, const float* masks,
+                                       int S, int Fm, const int* nearest_idx, float* stats, int ld_stats,
+                                       const float* aff_scale, const float* aff_shift, void* stream) {
+  if (Tp <= pa::POOLR_MAXT)
+    return pa_stats_pool_rows(feat, B, T0, Tp, C, ld, masks, S, Fm, nearest_idx, stats, ld_stats, aff_scale,
+                              aff_shift, stream);
+  if (B <= 0) return 0;
+  const size_t lds = sizeof(float) * (size_t)S * Tp;
+  PA_REQUIRE(S >= 1 && S <= pa::POOL_MAXS && lds <= (size_t)pa::POOLR_LONG_LDS && ld_stats >= 2 * C,
+             "pa_stats_pool_rows: S <= %d, S x T' <= %d and ld_stats >= 2 C required (got %d, %d)", pa::POOL_MAXS,
+             pa::POOLR_LONG_LDS / 4, S, Tp);
+  static bool attr_set = false;
+  if (!attr_set) {
+    (void)hipFuncSetAttribute((const void*)pa::k_stats_pool_rows_long, hipFuncAttributeMaxDynamicSharedMemorySize,
+                              pa::POOLR_LONG_LDS);
+    attr_set = true;
+  }
+  pa::ProfScope prof("k_stats_pool_rows_long", stream, 6.0 * B * S * C * Tp, 4.0 * B * C * Tp + 8.0 * B * S * C);
+  hipLaunchKernelGGL(pa::k_stats_pool_rows_long, dim3(pa::cdiv(C, 256), B), dim3(256), lds, (hipStream_t)stream,
+                     feat, T0, Tp, C, ld, masks, S, Fm, nearest_idx, stats, ld_stats, aff_scale, aff_shift);
+  PA_CHECK_LAUNCH("pa_stats_pool_rows_long");
+  return 0;
+}
+
+extern "C" {
 
 int pa_stats_pool(const float* feat, int B, int Fh, int Tp, int C, const float* masks, int S, int Fm,
                   const int* nearest_idx, float* stats, void* stream) {

@@ -10,7 +10,7 @@ import torch
 import torch.nn.functional as F
 
 from . import ffi
-from .weights import EmbeddingPack, XVectorPack
+from .weights import EmbeddingPack, XVectorMFCCPack, XVectorPack
 
 
 class EmbeddingEngine:
@@ -267,9 +267,11 @@ class XVectorEngine(EmbeddingEngine):
         self._idx_cache = {}
 
     READS_PAST_END_AS_ZERO = False    # pa_row_stats normalises over the samples present only
+    #: prefix of the C entry points (_num_frames, _workspace_bytes, _forward) and the front end's name in messages
+    _ABI, _FRONT = "pa_xvec", "SincNet"
 
     def num_pool_frames(self, num_samples: int) -> int:
-        return ffi.load().pa_xvec_num_frames(self.pack.struct, num_samples)
+        return getattr(ffi.load(), self._ABI + "_num_frames")(self.pack.struct, num_samples)
 
     def _ragged_supported(self) -> bool:
         return False        # InstanceNorm layers are per utterance: one launch sequence per length
@@ -281,7 +283,7 @@ class XVectorEngine(EmbeddingEngine):
     def _check_lengths(self, lengths: np.ndarray, minimum: int = 400):
         short = [i for i, n in enumerate(lengths) if self.num_pool_frames(int(n)) < 1]
         if short:
-            raise ValueError(f"utterance {short[0]} has {int(lengths[short[0]])} samples: too short for SincNet + "
+            raise ValueError(f"utterance {short[0]} has {int(lengths[short[0]])} samples: too short for {self._FRONT} + "
                              "the TDNN stack")
 
     @ffi.on_device(lambda self, *a, **k: self.pack.device)
@@ -292,7 +294,7 @@ class XVectorEngine(EmbeddingEngine):
         dev = self.pack.device
         Tp = self.num_pool_frames(num_samples)
         if Tp < 1:
-            raise ValueError(f"chunks of {num_samples} samples are too short for SincNet + the TDNN stack")
+            raise ValueError(f"chunks of {num_samples} samples are too short for {self._FRONT} + the TDNN stack")
         S = 1 if masks is None else masks.shape[1]
         Fm = 0 if masks is None else masks.shape[2]
         idx = self.nearest_index(Fm, Tp) if masks is not None else None
@@ -302,13 +304,46 @@ class XVectorEngine(EmbeddingEngine):
         c0 = 0
         while c0 < num_chunks:
             nb = min(self.max_chunks, num_chunks - c0)
-            ws = self._workspace(lib.pa_xvec_workspace_bytes(w, nb, num_samples, S))
+            ws = self._workspace(getattr(lib, self._ABI + "_workspace_bytes")(w, nb, num_samples, S))
             sub = wav[c0 * chunk_stride:]
-            rc = lib.pa_xvec_forward(
+            rc = getattr(lib, self._ABI + "_forward")(
                 w, ffi.c_fp(sub.data_ptr()), sub.numel(), chunk_stride, nb, num_samples,
                 ffi.ptr(masks[c0:c0 + nb]) if masks is not None else None, S, Fm,
                 ffi.ptr(idx) if idx is not None else None, ffi.ptr(emb[c0:c0 + nb]),
                 ffi.ptr(ws), ws.numel(), ffi.stream())
-            ffi.check(rc, "pa_xvec_forward")
+            ffi.check(rc, self._ABI + "_forward")
             c0 += nb
         return emb
+
+
+class XVectorMFCCEngine(XVectorEngine):
+    """XVectorMFCC (models/embedding/xvector.py:42-202) over `pa_xvec_mfcc_forward`: torchaudio MFCC (csrc/mfcc.hip)
+    -> the TDNN stack, pooling and Linear of XVectorEngine.  The MFCC of a chunk depends on that chunk alone (its own
+    reflect padding, its own top_db maximum), so ragged batches fall back to one launch sequence per length."""
+
+    _ABI, _FRONT = "pa_xvec_mfcc", "the MFCC front end"
+    READS_PAST_END_AS_ZERO = True     # k_mfcc_mel reads samples past the waveform as zeros before reflecting
+
+    def __init__(self, pack: XVectorMFCCPack, max_chunks: Optional[int] = None):
+        super().__init__(pack, max_chunks)
+
+    def _ragged_supported(self) -> bool:
+        return False
+
+    @ffi.on_device(lambda self, *a, **k: self.pack.device)
+    def features(self, wav: torch.Tensor, chunk_stride: int, num_chunks: int, num_samples: int) -> torch.Tensor:
+        """the MFCC front end alone: (num_chunks, frames, n_mfcc), torchaudio's MFCC of each chunk transposed"""
+        lib = ffi.load()
+        w = self.pack.struct
+        if num_chunks <= 0:
+            return torch.empty((0, 0, w.n_mfcc), dtype=torch.float32, device=self.pack.device)
+        if (w.center and num_samples <= w.n_fft // 2) or (not w.center and num_samples < w.n_fft):
+            raise ValueError(f"chunks of {num_samples} samples leave no MFCC frame")
+        T = 1 + num_samples // w.hop_length if w.center else 1 + (num_samples - w.n_fft) // w.hop_length
+        out = torch.empty((num_chunks, T, w.n_mfcc), dtype=torch.float32, device=self.pack.device)
+        nbytes = 4 * (num_chunks * T * w.n_mels + num_chunks + 128)     # the mel energies + the chunk maxima, aligned
+        ws = self._workspace(nbytes)
+        rc = lib.pa_mfcc_features(w, ffi.c_fp(wav.data_ptr()), wav.numel(), chunk_stride, num_chunks, num_samples,
+                                  ffi.ptr(out), ffi.ptr(ws), ws.numel(), ffi.stream())
+        ffi.check(rc, "pa_mfcc_features")
+        return out

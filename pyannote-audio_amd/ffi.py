@@ -103,6 +103,19 @@ class XvecWeights(C.Structure):
     ]
 
 
+class XvecMfccWeights(C.Structure):
+    """pa_xvec_mfcc_weights (include/pyannote_amd.h)"""
+    _fields_ = [
+        ("n_fft", C.c_int32), ("hop_length", C.c_int32), ("center", C.c_int32), ("log_mels", C.c_int32),
+        ("n_mels", C.c_int32), ("n_mfcc", C.c_int32), ("dimension", C.c_int32),
+        ("tdnn_channels", C.c_int32 * PA_XVEC_TDNN), ("tdnn_kernel", C.c_int32 * PA_XVEC_TDNN),
+        ("tdnn_dilation", C.c_int32 * PA_XVEC_TDNN),
+        ("window", c_fp), ("fft_tw", c_fp), ("mel_w", c_fp), ("mel_lo", c_fp), ("mel_hi", c_fp), ("dct", c_fp),
+        ("tdnn_w", c_fp * PA_XVEC_TDNN), ("tdnn_b", c_fp * PA_XVEC_TDNN),
+        ("bn_scale", c_fp), ("bn_shift", c_fp), ("emb_w", c_fp), ("emb_b", c_fp),
+    ]
+
+
 class LibraryNotBuilt(RuntimeError):
     pass
 
@@ -235,6 +248,12 @@ _OPTIONAL: list[tuple] = [
     ("pa_xvec_workspace_bytes", [C.POINTER(XvecWeights), C.c_int, C.c_int, C.c_int], C.c_size_t),
     ("pa_xvec_forward", [C.POINTER(XvecWeights), c_fp, C.c_int64, C.c_int64, C.c_int, C.c_int, c_fp,
                          C.c_int, C.c_int, c_fp, c_fp, c_fp, C.c_size_t, c_fp], C.c_int),
+    ("pa_xvec_mfcc_num_frames", [C.POINTER(XvecMfccWeights), C.c_int], C.c_int),
+    ("pa_xvec_mfcc_workspace_bytes", [C.POINTER(XvecMfccWeights), C.c_int, C.c_int, C.c_int], C.c_size_t),
+    ("pa_xvec_mfcc_forward", [C.POINTER(XvecMfccWeights), c_fp, C.c_int64, C.c_int64, C.c_int, C.c_int, c_fp,
+                              C.c_int, C.c_int, c_fp, c_fp, c_fp, C.c_size_t, c_fp], C.c_int),
+    ("pa_mfcc_features", [C.POINTER(XvecMfccWeights), c_fp, C.c_int64, C.c_int64, C.c_int, C.c_int, c_fp, c_fp,
+                          C.c_size_t, c_fp], C.c_int),
 ]
 
 

@@ -310,7 +310,8 @@ class Model:
         arch = ckpt["pyannote.audio"]["architecture"]["class"]
         klass = {"PyanNet": PyanNet, "SSeRiouSS": SSeRiouSS, "WeSpeakerResNet34": WeSpeakerResNet34,
                  "WeSpeakerResNet152": WeSpeakerResNet152, "WeSpeakerResNet221": WeSpeakerResNet221,
-                 "WeSpeakerResNet293": WeSpeakerResNet293, "XVectorSincNet": XVectorSincNet}.get(arch)
+                 "WeSpeakerResNet293": WeSpeakerResNet293, "XVectorSincNet": XVectorSincNet,
+                 "XVectorMFCC": XVectorMFCC}.get(arch)
         # a user's own class (the reference imports `architecture.module` and takes `architecture.class` from it,
         # core/model.py:609-613): its counterpart registered with `register_architecture`
         module = ckpt["pyannote.audio"]["architecture"].get("module", "")
@@ -318,7 +319,7 @@ class Model:
         if klass is None:
             raise NotImplementedError(
                 f"architecture {arch!r} is outside the accelerated hot path (PyanNet, SSeRiouSS, "
-                "WeSpeakerResNet34/152/221/293, XVectorSincNet)")
+                "WeSpeakerResNet34/152/221/293, XVectorSincNet, XVectorMFCC)")
         return klass(ckpt["state_dict"], dict(ckpt.get("hyper_parameters", {})),
                      ckpt["pyannote.audio"]["specifications"])
 
@@ -581,6 +582,47 @@ class XVectorSincNet(Model):
         from .embedding import XVectorEngine
         from .weights import XVectorPack
         return XVectorEngine(XVectorPack(self._state_dict, dict(self.hparams), device))
+
+    def __call__(self, waveforms: torch.Tensor, weights: Optional[torch.Tensor] = None) -> torch.Tensor:
+        return self.engine.forward(waveforms, weights)
+
+    forward = __call__
+
+
+class XVectorMFCC(Model):
+    """models/embedding/xvector.py:42-202 over the HIP x-vector engine with the MFCC front end (csrc/mfcc.hip).  The
+    `mfcc` hyper-parameters (torchaudio.transforms.MFCC's arguments and its `melkwargs`) are validated at load time
+    (`weights.mfcc_config`): what the front end is not built for is refused with NotImplementedError."""
+
+    ARCHITECTURE = ("pyannote.audio.models.embedding.xvector", "XVectorMFCC")
+    _TDNN = XVectorSincNet._TDNN
+
+    def __init__(self, state_dict: dict, hparams: dict, specifications: Specifications):
+        super().__init__(state_dict, hparams, specifications)
+        from .weights import mfcc_config
+        self.mfcc = mfcc_config(dict(self.hparams))
+
+    @property
+    def dimension(self) -> int:
+        return int(self._state_dict["embedding.weight"].shape[0])
+
+    def num_frames(self, num_samples: int) -> int:
+        c = self.mfcc
+        n = 1 + num_samples // c["hop_length"] if c["center"] else 1 + (num_samples - c["n_fft"]) // c["hop_length"]
+        return multi_conv_num_frames(n, *self._TDNN)
+
+    def receptive_field_size(self, num_frames: int = 1) -> int:
+        size = multi_conv_receptive_field_size(num_frames, *self._TDNN)
+        return self.mfcc["n_fft"] + (size - 1) * self.mfcc["hop_length"]
+
+    def receptive_field_center(self, frame: int = 0) -> int:
+        c = multi_conv_receptive_field_center(frame, *self._TDNN) * self.mfcc["hop_length"]
+        return c if self.mfcc["center"] else c + self.mfcc["n_fft"] // 2
+
+    def _build_engine(self, device):
+        from .embedding import XVectorMFCCEngine
+        from .weights import XVectorMFCCPack
+        return XVectorMFCCEngine(XVectorMFCCPack(self._state_dict, dict(self.hparams), device))
 
     def __call__(self, waveforms: torch.Tensor, weights: Optional[torch.Tensor] = None) -> torch.Tensor:
         return self.engine.forward(waveforms, weights)

@@ -417,16 +417,59 @@ class SSeRiouSSPack:
         return C.c_void_p(d.data_ptr())
 
 
+#: kernel size and dilation of the five TDNN layers of both x-vector models (xvector.py:64-66, 227-231)
+XVECTOR_KERNEL, XVECTOR_DILATION = (5, 3, 3, 1, 1), (1, 2, 3, 1, 1)
+
+
+def pack_tdnn_tail(sd: dict, w, up, keep: list) -> dict:
+    """tdnns.* / embedding.* of an x-vector state dict (xvector.py:62-89, 226-252) -> the TDNN, last-BatchNorm and
+    embedding fields that pa_xvec_weights and pa_xvec_mfcc_weights share.  Every BatchNorm follows a LeakyReLU, so it
+    cannot be folded backwards; being an affine map it is folded FORWARD, in float64, into the next convolution
+    (W_j diag(s), b + sum_j W_j t); the last one is handed to the pooling kernel, which applies it on load (it cannot
+    move past the pooling: an all-zero mask pools to mean = std = 0, not to the BatchNorm's shift).  Layer 0 is padded
+    to 64 input channels.  Returns the device tensors the tests read: folded_tdnn [(taps (k, cout, cin_pad), bias)],
+    last_batchnorm (scale, shift), embedding (weight (dimension, ld), bias)."""
+    folded_tdnn: list = []
+    scale = shift = None                       # affine map of the previous BatchNorm (float64)
+    for l in range(ffi.PA_XVEC_TDNN):
+        cw = sd[f"tdnns.{3 * l}.weight"].double()          # (cout, cin, k)
+        cb = sd[f"tdnns.{3 * l}.bias"].double()
+        cout, cin, k = cw.shape
+        if k != XVECTOR_KERNEL[l] or cout % 4 or (l == 0 and cin > 64):
+            raise NotImplementedError(f"unexpected TDNN layer {l}: {tuple(cw.shape)}")
+        if scale is not None:
+            cb = cb + torch.einsum("oik,i->o", cw, shift)
+            cw = cw * scale.view(1, -1, 1)
+        cin_pad = 64 if l == 0 else cin
+        taps = torch.zeros(k, cout, cin_pad, dtype=torch.float64)
+        taps[:, :, :cin] = cw.permute(2, 0, 1)
+        w.tdnn_w[l] = up(taps.float()).value
+        w.tdnn_b[l] = up(cb.float()).value
+        folded_tdnn.append((keep[-2], keep[-1]))
+        w.tdnn_channels[l], w.tdnn_kernel[l], w.tdnn_dilation[l] = cout, k, XVECTOR_DILATION[l]
+        bn = f"tdnns.{3 * l + 2}"
+        scale = sd[bn + ".weight"].double() / torch.sqrt(sd[bn + ".running_var"].double() + 1e-5)
+        shift = sd[bn + ".bias"].double() - sd[bn + ".running_mean"].double() * scale
+    ew, eb = sd["embedding.weight"].double(), sd["embedding.bias"].double()
+    C_ = int(w.tdnn_channels[ffi.PA_XVEC_TDNN - 1])
+    assert ew.shape[1] == 2 * C_
+    ld = (2 * C_ + 31) // 32 * 32
+    packed = torch.zeros(ew.shape[0], ld, dtype=torch.float64)
+    packed[:, :2 * C_] = ew
+    w.bn_scale, w.bn_shift = up(scale.float()), up(shift.float())
+    last_batchnorm = (keep[-2], keep[-1])
+    w.emb_w, w.emb_b = up(packed.float()), up(eb.float())
+    w.dimension = int(ew.shape[0])
+    return {"folded_tdnn": folded_tdnn, "last_batchnorm": last_batchnorm, "embedding": (keep[-2], keep[-1])}
+
+
 class XVectorPack:
     """Device-resident, kernel-ready XVectorSincNet weights + the `pa_xvec_weights` struct
     (models/embedding/xvector.py:205-252).  State-dict layout: sincnet.*, tdnns.{3l}.{weight,bias} (Conv1d),
-    tdnns.{3l+2}.{weight,bias,running_mean,running_var} (BatchNorm1d, eval), embedding.{weight,bias}.
-    Every BatchNorm follows a LeakyReLU, so it cannot be folded backwards; being an affine map it is folded
-    FORWARD, in float64, into the next convolution (W_j diag(s), b + sum_j W_j t); the last one is handed to
-    the pooling kernel, which applies it on load (it cannot move past the pooling: an all-zero mask pools
-    to mean = std = 0, not to the BatchNorm's shift)."""
+    tdnns.{3l+2}.{weight,bias,running_mean,running_var} (BatchNorm1d, eval), embedding.{weight,bias}; the TDNN
+    layers, BatchNorms and Linear are packed by `pack_tdnn_tail`."""
 
-    KERNEL, DILATION = (5, 3, 3, 1, 1), (1, 2, 3, 1, 1)
+    KERNEL, DILATION = XVECTOR_KERNEL, XVECTOR_DILATION
 
     def __init__(self, state_dict: dict, hparams: dict, device: torch.device):
         sd = {k: v.detach().float().cpu() for k, v in state_dict.items() if v.dtype.is_floating_point}
@@ -436,38 +479,231 @@ class XVectorPack:
         self._keep: list[torch.Tensor] = []
         w = ffi.XvecWeights()
         self.sinc_taps = pack_sincnet(sd, w, self._up)
-        self.folded_tdnn: list = []                # [(taps (k, cout, cin_pad), bias (cout))] kept for tests
-        scale = shift = None                       # affine map of the previous BatchNorm (float64)
-        for l in range(ffi.PA_XVEC_TDNN):
-            cw = sd[f"tdnns.{3 * l}.weight"].double()          # (cout, cin, k)
-            cb = sd[f"tdnns.{3 * l}.bias"].double()
-            cout, cin, k = cw.shape
-            if k != self.KERNEL[l] or cout % 4:
-                raise NotImplementedError(f"unexpected TDNN layer {l}: {tuple(cw.shape)}")
-            if scale is not None:
-                cb = cb + torch.einsum("oik,i->o", cw, shift)
-                cw = cw * scale.view(1, -1, 1)
-            cin_pad = 64 if l == 0 else cin
-            taps = torch.zeros(k, cout, cin_pad, dtype=torch.float64)
-            taps[:, :, :cin] = cw.permute(2, 0, 1)
-            w.tdnn_w[l] = self._up(taps.float()).value
-            w.tdnn_b[l] = self._up(cb.float()).value
-            self.folded_tdnn.append((self._keep[-2], self._keep[-1]))
-            w.tdnn_channels[l], w.tdnn_kernel[l], w.tdnn_dilation[l] = cout, k, self.DILATION[l]
-            bn = f"tdnns.{3 * l + 2}"
-            scale = sd[bn + ".weight"].double() / torch.sqrt(sd[bn + ".running_var"].double() + 1e-5)
-            shift = sd[bn + ".bias"].double() - sd[bn + ".running_mean"].double() * scale
-        ew, eb = sd["embedding.weight"].double(), sd["embedding.bias"].double()
-        C_ = int(w.tdnn_channels[ffi.PA_XVEC_TDNN - 1])
-        assert ew.shape[1] == 2 * C_
-        ld = (2 * C_ + 31) // 32 * 32
-        packed = torch.zeros(ew.shape[0], ld, dtype=torch.float64)
-        packed[:, :2 * C_] = ew
-        w.bn_scale, w.bn_shift = self._up(scale.float()), self._up(shift.float())
-        self.last_batchnorm = (self._keep[-2], self._keep[-1])
-        w.emb_w, w.emb_b = self._up(packed.float()), self._up(eb.float())
-        self.embedding = (self._keep[-2], self._keep[-1])
-        w.dimension = int(ew.shape[0])
+        tail = pack_tdnn_tail(sd, w, self._up, self._keep)
+        self.folded_tdnn = tail["folded_tdnn"]      # [(taps (k, cout, cin_pad), bias (cout))] kept for tests
+        self.last_batchnorm = tail["last_batchnorm"]
+        self.embedding = tail["embedding"]
+        self.struct = w
+
+    def _up(self, t: torch.Tensor):
+        d = t.contiguous().to(self.device)
+        self._keep.append(d)
+        return C.c_void_p(d.data_ptr())
+
+
+# ---------------------------------------------------------------------------------------------
+# XVectorMFCC (models/embedding/xvector.py:42-202): torchaudio.transforms.MFCC hyper-parameters and buffers
+# ---------------------------------------------------------------------------------------------
+#: XVectorMFCC.MFCC_DEFAULTS (xvector.py:43)
+MFCC_DEFAULTS = {"n_mfcc": 40, "dct_type": 2, "norm": "ortho", "log_mels": False}
+#: torchaudio.transforms.MelSpectrogram's keyword arguments and their defaults (what `melkwargs` may hold)
+MELSPEC_DEFAULTS = {"n_fft": 400, "win_length": None, "hop_length": None, "f_min": 0.0, "f_max": None, "pad": 0,
+                    "n_mels": 128, "window_fn": None, "power": 2.0, "normalized": False, "wkwargs": None,
+                    "center": True, "pad_mode": "reflect", "onesided": None, "norm": None, "mel_scale": "htk"}
+MFCC_MAX_MELS, MFCC_MAX_COEFFS = 256, 64
+
+
+def _is_int(x) -> bool:
+    return isinstance(x, int) and not isinstance(x, bool)
+
+
+def _is_num(x) -> bool:
+    return isinstance(x, (int, float)) and not isinstance(x, bool)
+
+
+def mfcc_config(hparams: dict) -> dict:
+    """hparams of an XVectorMFCC checkpoint -> the resolved MFCC configuration (n_fft, hop_length, center, log_mels,
+    n_mels, n_mfcc, dct_norm, f_min, f_max, mel_norm, mel_scale, sample_rate), validated on the host.  The HIP front
+    end (csrc/mfcc.hip) is built for n_fft = win_length = 400, reflect padding, power 2, no normalisation, at most
+    256 mel bands and 64 coefficients, DCT-II; whatever else a checkpoint says is refused with NotImplementedError
+    naming the key and its value.  Values that only shape the filter bank (n_mels, f_min, f_max, mel_scale, mel norm)
+    are taken as they come."""
+    sample_rate = hparams.get("sample_rate", 16000)
+    mfcc = dict(MFCC_DEFAULTS, **(hparams.get("mfcc") or {}))
+
+    def refuse(key, value, why):
+        raise NotImplementedError(f"XVectorMFCC: mfcc hyper-parameter {key} = {value!r}: {why}; refusing to load a "
+                                  "checkpoint whose features would silently differ")
+
+    for key, value in mfcc.items():
+        if key not in ("n_mfcc", "dct_type", "norm", "log_mels", "sample_rate", "melkwargs"):
+            refuse(key, value, "not an argument of torchaudio.transforms.MFCC")
+    sample_rate = mfcc.get("sample_rate", sample_rate)
+    if not _is_num(sample_rate) or sample_rate <= 0:
+        refuse("sample_rate", sample_rate, "a positive number is required")
+    mel = dict(MELSPEC_DEFAULTS)
+    melkwargs = mfcc.get("melkwargs") or {}
+    if not isinstance(melkwargs, dict):
+        refuse("melkwargs", melkwargs, "a dict of MelSpectrogram arguments is required")
+    for key, value in melkwargs.items():
+        if key not in MELSPEC_DEFAULTS:
+            refuse(f"melkwargs.{key}", value, "not an argument MFCC passes on to MelSpectrogram")
+        mel[key] = value
+    n_fft = mel["n_fft"]
+    if not _is_int(n_fft) or n_fft != 400:
+        refuse("melkwargs.n_fft", n_fft, "the HIP front end is built for n_fft = 400")
+    if mel["win_length"] is not None and (not _is_int(mel["win_length"]) or mel["win_length"] != n_fft):
+        refuse("melkwargs.win_length", mel["win_length"], "win_length must equal n_fft (400)")
+    hop = mel["hop_length"] if mel["hop_length"] is not None else n_fft // 2
+    if not _is_int(hop) or not 1 <= hop <= n_fft:
+        refuse("melkwargs.hop_length", mel["hop_length"], "1 <= hop_length <= 400 is built")
+    if not isinstance(mel["center"], bool):
+        refuse("melkwargs.center", mel["center"], "True or False")
+    if mel["pad_mode"] != "reflect":
+        refuse("melkwargs.pad_mode", mel["pad_mode"], "only reflect padding is built")
+    if not _is_int(mel["pad"]) or mel["pad"] != 0:
+        refuse("melkwargs.pad", mel["pad"], "only pad = 0 is built")
+    if not _is_num(mel["power"]) or float(mel["power"]) != 2.0:
+        refuse("melkwargs.power", mel["power"], "only the power spectrum (power = 2.0) is built")
+    if mel["normalized"] is not False:
+        refuse("melkwargs.normalized", mel["normalized"], "only normalized = False is built")
+    if mel["onesided"] not in (None, True):
+        refuse("melkwargs.onesided", mel["onesided"], "only the one-sided spectrum is built")
+    if mel["window_fn"] not in (None, torch.hann_window):
+        refuse("melkwargs.window_fn", mel["window_fn"], "only torch.hann_window is built")
+    if mel["wkwargs"] is not None:
+        refuse("melkwargs.wkwargs", mel["wkwargs"], "window arguments are not built")
+    n_mels = mel["n_mels"]
+    if not _is_int(n_mels) or not 1 <= n_mels <= MFCC_MAX_MELS:
+        refuse("melkwargs.n_mels", n_mels, f"1 <= n_mels <= {MFCC_MAX_MELS} is built")
+    if not _is_num(mel["f_min"]) or (mel["f_max"] is not None and not _is_num(mel["f_max"])):
+        refuse("melkwargs.f_min/f_max", (mel["f_min"], mel["f_max"]), "numbers (f_max may be None) are required")
+    if mel["mel_scale"] not in ("htk", "slaney"):
+        refuse("melkwargs.mel_scale", mel["mel_scale"], "htk or slaney")
+    if mel["norm"] not in (None, "slaney"):
+        refuse("melkwargs.norm", mel["norm"], "None or slaney")
+    n_mfcc = mfcc["n_mfcc"]
+    if not _is_int(n_mfcc) or not 1 <= n_mfcc <= min(MFCC_MAX_COEFFS, n_mels):
+        refuse("n_mfcc", n_mfcc, f"1 <= n_mfcc <= min({MFCC_MAX_COEFFS}, n_mels) is built")
+    if not _is_int(mfcc["dct_type"]) or mfcc["dct_type"] != 2:
+        refuse("dct_type", mfcc["dct_type"], "only DCT-II is built")
+    if mfcc["norm"] not in ("ortho", None):
+        refuse("norm", mfcc["norm"], "ortho or None")
+    if not isinstance(mfcc["log_mels"], bool):
+        refuse("log_mels", mfcc["log_mels"], "True or False")
+    return {"sample_rate": sample_rate, "n_fft": n_fft, "hop_length": hop, "center": mel["center"],
+            "log_mels": mfcc["log_mels"], "n_mels": n_mels, "n_mfcc": n_mfcc, "dct_norm": mfcc["norm"],
+            "f_min": float(mel["f_min"]), "f_max": mel["f_max"], "mel_norm": mel["norm"],
+            "mel_scale": mel["mel_scale"]}
+
+
+def _hz_to_mel(freq: float, mel_scale: str) -> float:
+    if mel_scale == "htk":
+        return 2595.0 * math.log10(1.0 + freq / 700.0)
+    f_sp, min_log_hz = 200.0 / 3, 1000.0
+    min_log_mel, logstep = min_log_hz / f_sp, math.log(6.4) / 27.0
+    mels = freq / f_sp
+    return min_log_mel + math.log(freq / min_log_hz) / logstep if freq >= min_log_hz else mels
+
+
+def _mel_to_hz(mels: torch.Tensor, mel_scale: str) -> torch.Tensor:
+    if mel_scale == "htk":
+        return 700.0 * (10.0 ** (mels / 2595.0) - 1.0)
+    f_sp, min_log_hz = 200.0 / 3, 1000.0
+    min_log_mel, logstep = min_log_hz / f_sp, math.log(6.4) / 27.0
+    freqs = f_sp * mels
+    log_t = mels >= min_log_mel
+    freqs[log_t] = min_log_hz * torch.exp(logstep * (mels[log_t] - min_log_mel))
+    return freqs
+
+
+def melscale_fbanks(n_freqs: int, f_min: float, f_max: float, n_mels: int, sample_rate, norm=None,
+                    mel_scale: str = "htk") -> torch.Tensor:
+    """torchaudio.functional.melscale_fbanks, float32 as torchaudio builds it: (n_freqs, n_mels) triangles between
+    mel-spaced points (the buffer `mfcc.MelSpectrogram.mel_scale.fb` of a checkpoint that lacks it)"""
+    all_freqs = torch.linspace(0, sample_rate // 2, n_freqs)
+    m_pts = torch.linspace(_hz_to_mel(f_min, mel_scale), _hz_to_mel(f_max, mel_scale), n_mels + 2)
+    f_pts = _mel_to_hz(m_pts, mel_scale)
+    f_diff = f_pts[1:] - f_pts[:-1]
+    slopes = f_pts.unsqueeze(0) - all_freqs.unsqueeze(1)
+    down = (-1.0 * slopes[:, :-2]) / f_diff[:-1]
+    up = slopes[:, 2:] / f_diff[1:]
+    fb = torch.max(torch.zeros(1), torch.min(down, up))
+    if norm == "slaney":
+        fb *= (2.0 / (f_pts[2:n_mels + 2] - f_pts[:n_mels])).unsqueeze(0)
+    return fb
+
+
+def create_dct(n_mfcc: int, n_mels: int, norm) -> torch.Tensor:
+    """torchaudio.functional.create_dct (DCT-II), float32: (n_mels, n_mfcc) (the buffer `mfcc.dct_mat`)"""
+    n = torch.arange(float(n_mels))
+    k = torch.arange(float(n_mfcc)).unsqueeze(1)
+    dct = torch.cos(math.pi / float(n_mels) * (n + 0.5) * k)
+    if norm is None:
+        dct *= 2.0
+    else:
+        dct[0] *= 1.0 / math.sqrt(2.0)
+        dct *= math.sqrt(2.0 / float(n_mels))
+    return dct.t()
+
+
+def mfcc_buffers(sd: dict, cfg: dict) -> tuple:
+    """(window (400), fb (201, n_mels), dct_mat (n_mels, n_mfcc)) of an XVectorMFCC state dict: the checkpoint's
+    torchaudio buffers where present, else the closed forms torchaudio builds them from"""
+    pre = "mfcc.MelSpectrogram."
+    window = sd.get(pre + "spectrogram.window")
+    if window is None:
+        window = torch.hann_window(cfg["n_fft"])
+    fb = sd.get(pre + "mel_scale.fb")
+    if fb is None:
+        f_max = cfg["f_max"] if cfg["f_max"] is not None else float(cfg["sample_rate"] // 2)
+        fb = melscale_fbanks(cfg["n_fft"] // 2 + 1, cfg["f_min"], f_max, cfg["n_mels"], cfg["sample_rate"],
+                             cfg["mel_norm"], cfg["mel_scale"])
+    dct = sd.get("mfcc.dct_mat")
+    if dct is None:
+        dct = create_dct(cfg["n_mfcc"], cfg["n_mels"], cfg["dct_norm"])
+    shapes = {"window": (tuple(window.shape), (cfg["n_fft"],)),
+              "fb": (tuple(fb.shape), (cfg["n_fft"] // 2 + 1, cfg["n_mels"])),
+              "dct_mat": (tuple(dct.shape), (cfg["n_mels"], cfg["n_mfcc"]))}
+    for name, (got, want) in shapes.items():
+        if got != want:
+            raise ValueError(f"XVectorMFCC: buffer {name} has shape {got}, the hyper-parameters say {want}")
+    return window.float(), fb.float(), dct.float()
+
+
+def fft_twiddles() -> torch.Tensor:
+    """exp(-2 pi i m / 200), m < 200, then exp(-2 pi i k / 400), k <= 200, as (re, im) float32 pairs (the 200-point
+    complex FFT and the real unpack of csrc/mfcc.hip), rounded once from float64"""
+    a = torch.cat([torch.arange(200, dtype=torch.float64) / 200, torch.arange(201, dtype=torch.float64) / 400])
+    return torch.stack([torch.cos(2 * math.pi * a), -torch.sin(2 * math.pi * a)], dim=1).float()
+
+
+class XVectorMFCCPack:
+    """Device-resident, kernel-ready XVectorMFCC weights + the `pa_xvec_mfcc_weights` struct
+    (models/embedding/xvector.py:42-89): the MFCC front end's buffers as kernel tables, then the TDNN stack,
+    BatchNorms and Linear exactly as XVectorPack packs them (`pack_tdnn_tail`)."""
+
+    def __init__(self, state_dict: dict, hparams: dict, device: torch.device):
+        cfg = mfcc_config(hparams)
+        sd = {k: v.detach().float().cpu() for k, v in state_dict.items() if v.dtype.is_floating_point}
+        self.device = device
+        self.cfg = cfg
+        self._keep: list[torch.Tensor] = []
+        up = self._up
+        w = ffi.XvecMfccWeights()
+        w.n_fft, w.hop_length, w.center = cfg["n_fft"], cfg["hop_length"], int(cfg["center"])
+        w.log_mels, w.n_mels, w.n_mfcc = int(cfg["log_mels"]), cfg["n_mels"], cfg["n_mfcc"]
+        window, fb, dct = mfcc_buffers(sd, cfg)
+        nz = fb != 0                                                  # (201, n_mels)
+        any_ = nz.any(dim=0)
+        idx = torch.arange(fb.shape[0]).unsqueeze(1).expand_as(fb)
+        lo = torch.where(nz, idx, fb.shape[0]).min(dim=0).values
+        hi = torch.where(nz, idx, -1).max(dim=0).values
+        lo = torch.where(any_, lo, torch.zeros_like(lo))               # all-zero filter: lo = 0 > hi = -1
+        w.window = up(window)
+        w.fft_tw = up(fft_twiddles())
+        w.mel_w = up(fb.t())
+        w.mel_lo, w.mel_hi = up(lo.to(torch.int32)), up(hi.to(torch.int32))
+        dct_pad = torch.zeros(cfg["n_mels"], MFCC_MAX_COEFFS)
+        dct_pad[:, :cfg["n_mfcc"]] = dct
+        w.dct = up(dct_pad)
+        if sd["tdnns.0.weight"].shape[1] != cfg["n_mfcc"]:
+            raise ValueError(f"XVectorMFCC: tdnns.0 takes {sd['tdnns.0.weight'].shape[1]} channels, "
+                             f"n_mfcc = {cfg['n_mfcc']}")
+        tail = pack_tdnn_tail(sd, w, up, self._keep)
+        self.folded_tdnn = tail["folded_tdnn"]
+        self.last_batchnorm = tail["last_batchnorm"]
+        self.embedding = tail["embedding"]
         self.struct = w
 
     def _up(self, t: torch.Tensor):
