@@ -44,9 +44,14 @@ __global__ __launch_bounds__(256) void k_stats_pool(const float* __restrict__ fe
   __syncthreads();
   if (c >= Cc) return;
   const float* x = feat + (((long)b * Fh + f) * Tp) * Cc + c;
-  float m[POOL_MAXS];
+  // The weighted sum is compensated (Kahan; the product enters through one fma, so its rounding is carried too): a
+  // plain float32 sum of T' terms is off by ~sqrt(T') ulps of |x| sum(w), which a channel whose offset is 1e5 times its
+  // spread turns into a mean that is off by a tenth of the spread -- and the square of that ends up in the variance
+  // (tests/test_pooling_family_gpu.py::test_stats_pool_constant_offset).  A single weighted frame still gives mean = x
+  // and std = 0 exactly.
+  float m[POOL_MAXS], mc[POOL_MAXS];
 #pragma unroll
-  for (int s = 0; s < POOL_MAXS; ++s) m[s] = 0.f;
+  for (int s = 0; s < POOL_MAXS; ++s) m[s] = mc[s] = 0.f;
   // (loads in batches of POOL_LD: one load + a full wait per trip otherwise -- the same operations in the same order)
   for (int t0 = 0; t0 < Tp; t0 += POOL_LD) {
     float xb[POOL_LD];
@@ -57,7 +62,12 @@ __global__ __launch_bounds__(256) void k_stats_pool(const float* __restrict__ fe
       if (t0 + u < Tp) {
 #pragma unroll
         for (int s = 0; s < POOL_MAXS; ++s)
-          if (s < S) m[s] = fmaf(xb[u], ws[s][t0 + u], m[s]);
+          if (s < S) {
+            const float y = fmaf(xb[u], ws[s][t0 + u], -mc[s]);
+            const float t = m[s] + y;
+            mc[s] = (t - m[s]) - y;
+            m[s] = t;
+          }
       }
     }
   }

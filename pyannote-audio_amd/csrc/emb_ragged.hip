@@ -49,7 +49,7 @@ __global__ __launch_bounds__(256) void k_stats_pool_ragged(const float* __restri
   if (Tv > W) Tv = W;
   const float* x = feat + (((long)b * Fh + f) * W) * C + (c < C ? c : 0);
   const float* mrow = masks != nullptr ? masks + (long)b * ld_masks : nullptr;
-  float a = 0.f, q = 0.f, m = 0.f, v = 0.f;
+  float a = 0.f, q = 0.f, m = 0.f, mc = 0.f, v = 0.f;   // mc: Kahan compensation of m, as in k_stats_pool
   // pass 0: weighted sum (+ the weight sums, in column order as k_stats_pool adds them); pass 1: weighted squares
   for (int pass = 0; pass < 2; ++pass) {
     for (int t0 = 0; t0 < Tv; t0 += PR_TILE) {
@@ -71,7 +71,10 @@ __global__ __launch_bounds__(256) void k_stats_pool_ragged(const float* __restri
           for (int u = 0; u < PR_LD; ++u)
             if (u0 + u < n) {
               if (pass == 0) {
-                m = fmaf(xb[u], ws[u0 + u], m);
+                const float y = fmaf(xb[u], ws[u0 + u], -mc);
+                const float t = m + y;
+                mc = (t - m) - y;
+                m = t;
               } else {
                 const float d = xb[u] - m;
                 v = fmaf(d * d, ws[u0 + u], v);

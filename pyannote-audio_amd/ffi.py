@@ -197,6 +197,8 @@ _OPTIONAL: list[tuple] = [
     ("pa_absmax_diff", [c_fp, c_fp, C.c_long, c_fp, c_fp], C.c_int),
     ("pa_gemm_tn_s2", [c_fp, C.c_int, C.c_int, C.c_int, C.c_int, c_fp, C.c_int, c_fp, c_fp, C.c_long, C.c_int,
                        c_fp], C.c_int),
+    ("pa_gemm_tn_batched", [c_fp, C.c_int, C.c_long, C.c_long, c_fp, C.c_int, C.c_long, C.c_long, c_fp, c_fp, C.c_long,
+                            C.c_long, C.c_long, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_fp], C.c_int),
     ("pa_fbank", [c_fp, C.c_long, C.c_long, C.c_int, C.c_int, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp,
                   C.c_int, c_fp, C.c_int, c_fp], C.c_int),
     ("pa_fbank_center_span", [c_fp, C.c_int, C.c_int, C.c_int, C.c_int, c_fp, c_fp], C.c_int),
