@@ -527,6 +527,27 @@ int pa_aggregate(const float* scores, int C, int F, int K, const int32_t* start_
                  const double* window, const double* warm, float epsilon, float missing, int skip_average,
                  float* out, void* stream);
 
+/* Hysteresis thresholding of an aggregated score array into per-class region lists, replaces `Binarize.__call__`
+ * (utils/signal.py:254-318) applied to every class, `Annotation.support(collar)` and the min_duration_on deletion:
+ * scores (T,K) fp32 row-major on the device (as pa_aggregate leaves it), K <= 16.  onset / offset (K) fp32 and
+ * min_duration_on / min_duration_off (K) fp64 are HOST arrays.  State rule per class: inactive -> active iff
+ * score > onset, active -> inactive iff score < offset (fp32 comparisons, NaN changes nothing); state of frame 0 =
+ * score > onset.  A region runs from the middle of the frame that switched on to the middle of the frame that
+ * switched off (or of the last frame); middle of frame i = 0.5 * (s + (s + duration)), s = start + i * step, fp64,
+ * bit-identical to the host.  Regions not longer than 1e-6 do not exist; with min_duration_off > 0 neighbours whose gap
+ * is shorter are merged, then with min_duration_on > 0 shorter regions are removed.
+ * Outputs (device): counts (K) int32; regions (K, capacity, 2) fp64 start / end in time order, class k's at
+ * regions + k * capacity * 2; tracks (K, capacity) int32, optional (NULL): index of every region among the class's
+ * regions after merging and before removal when min_duration_off > 0, else 0 (its track name in the reference).
+ * `capacity` bounds a class's regions BEFORE merging (at most T / 2): if a class needs more, nothing is written past
+ * capacity, the call returns 3 and pa_last_error says which class.  T < 2 gives zero regions.  The call waits for the
+ * stream (it reads the counts back to check the capacity). */
+size_t pa_binarize_regions_workspace_bytes(int T, int K, int capacity);
+int pa_binarize_regions(const float* scores, int T, int K, const float* onset, const float* offset,
+                        const double* min_duration_on, const double* min_duration_off, double start,
+                        double duration, double step, int capacity, int32_t* counts, double* regions,
+                        int32_t* tracks, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- audio front door (core/io.py:223-265) ---- */
 
 /* Polyphase windowed-sinc resampling, replaces torchaudio.functional.resample in

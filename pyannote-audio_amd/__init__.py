@@ -17,4 +17,5 @@ from .plda import PLDA  # noqa: E402,F401
 from .speaker_verification import PretrainedSpeakerEmbedding, SpeakerEmbedding  # noqa: E402,F401
 from .speaker_diarization import SpeakerDiarization, DiarizeOutput  # noqa: E402,F401
 from .voice_activity_detection import VoiceActivityDetection  # noqa: E402,F401
+from .multilabel import MultiLabelSegmentation  # noqa: E402,F401
 from .hook import ArtifactHook, Hooks, ProgressHook, TimingHook  # noqa: E402,F401

@@ -376,6 +376,18 @@ if not HAVE_PYANNOTE_CORE:
                 out[s, t] = mapping.get(l, l)
             return out
 
+        def update(self, annotation: "Annotation", copy: bool = False) -> "Annotation":
+            """add every (segment, track, label) of `annotation`; an existing (segment, track) is overwritten
+            (pyannote.core Annotation.update)."""
+            result = self
+            if copy:
+                result = Annotation(uri=self.uri, modality=self.modality)
+                for s, t, l in self.itertracks(yield_label=True):
+                    result[s, t] = l
+            for s, t, l in annotation.itertracks(yield_label=True):
+                result[s, t] = l
+            return result
+
         def support(self, collar: float = 0.0):
             """merge same-label segments closer than `collar` (Annotation.support)."""
             gen = string_generator()

@@ -231,6 +231,9 @@ _OPTIONAL: list[tuple] = [
     ("pa_cluster_max", [c_fp, C.c_int, C.c_int, C.c_int, c_fp, C.c_int, c_fp, c_fp], C.c_int),
     ("pa_aggregate", [c_fp, C.c_int, C.c_int, C.c_int, c_fp, C.c_int, c_fp, c_fp, C.c_float, C.c_float, C.c_int,
                       c_fp, c_fp], C.c_int),
+    ("pa_binarize_regions_workspace_bytes", [C.c_int, C.c_int, C.c_int], C.c_size_t),
+    ("pa_binarize_regions", [c_fp, C.c_int, C.c_int, c_fp, c_fp, c_fp, c_fp, C.c_double, C.c_double, C.c_double,
+                             C.c_int, c_fp, c_fp, c_fp, c_fp, C.c_size_t, c_fp], C.c_int),
     ("pa_resample_poly", [c_fp, C.c_long, c_fp, C.c_int, C.c_int, C.c_int, C.c_int, c_fp, C.c_long, c_fp],
      C.c_int),
     ("pa_plda_transform", [c_fp, C.c_int, C.c_int, C.c_int, C.c_int, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp],

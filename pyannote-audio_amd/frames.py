@@ -7,7 +7,7 @@ warm_up=(0, 0), hard {0,1} scores).  Results are bit-identical to the reference'
 (small-integer sums; see the kernel file).  There is no host implementation behind these calls."""
 from __future__ import annotations
 
-from typing import Tuple
+from typing import Optional, Tuple
 
 import numpy as np
 import torch
@@ -73,11 +73,11 @@ def speaker_count(seg: torch.Tensor, chunks: SlidingWindow, frames: SlidingWindo
     return SlidingWindowFeature(count.cpu().numpy().reshape(T, 1), out_frames)
 
 
-def aggregate(scores, chunks: SlidingWindow, frames: SlidingWindow, device: torch.device,
-              warm_up: Tuple[float, float] = (0.0, 0.0), epsilon: float = 1e-12, hamming: bool = False,
-              missing: float = np.nan, skip_average: bool = False) -> SlidingWindowFeature:
-    """`Inference.aggregate` (core/inference.py:498-620) on the GPU: scores (C, F, K) host array or device
-    tensor -> SlidingWindowFeature (T, K) float32, bit-identical to the reference's chunk loop."""
+def aggregate_device(scores, chunks: SlidingWindow, frames: SlidingWindow, device: torch.device,
+                     warm_up: Tuple[float, float] = (0.0, 0.0), epsilon: float = 1e-12, hamming: bool = False,
+                     missing: float = np.nan, skip_average: bool = False) -> Tuple[torch.Tensor, SlidingWindow]:
+    """`aggregate` whose result stays where the kernel wrote it: (T, K) float32 device tensor and its frame grid.
+    Same kernel, same arguments, so bit-identical to `aggregate` (which is this plus one copy)."""
     x = torch.as_tensor(scores).to(device=device, dtype=torch.float32).contiguous()
     C, F, K = x.shape
     starts, T, out_frames = frame_geometry(chunks, frames, C)
@@ -95,7 +95,59 @@ def aggregate(scores, chunks: SlidingWindow, frames: SlidingWindow, device: torc
         ffi.check(ffi.load().pa_aggregate(ffi.ptr(x), C, F, K, ffi.ptr(st), T, ffi.ptr(w), ffi.ptr(wu), float(epsilon),
                                           float(missing), int(skip_average), ffi.ptr(out), ffi.stream()),
                   "pa_aggregate")
+    return out, out_frames
+
+
+def aggregate(scores, chunks: SlidingWindow, frames: SlidingWindow, device: torch.device,
+              warm_up: Tuple[float, float] = (0.0, 0.0), epsilon: float = 1e-12, hamming: bool = False,
+              missing: float = np.nan, skip_average: bool = False) -> SlidingWindowFeature:
+    """`Inference.aggregate` (core/inference.py:498-620) on the GPU: scores (C, F, K) host array or device
+    tensor -> SlidingWindowFeature (T, K) float32, bit-identical to the reference's chunk loop."""
+    out, out_frames = aggregate_device(scores, chunks, frames, device, warm_up=warm_up, epsilon=epsilon,
+                                       hamming=hamming, missing=missing, skip_average=skip_average)
     return SlidingWindowFeature(out.cpu().numpy(), out_frames)
+
+
+@ffi.on_device(lambda scores, *a, **k: scores.device)
+def binarize_regions(scores: torch.Tensor, frames: SlidingWindow, onset, offset, min_duration_on=0.0,
+                     min_duration_off=0.0, capacity: Optional[int] = None, return_tracks: bool = False):
+    """`Binarize` (utils/signal.py:207-318, no padding) of every column of an aggregated (T, K) float32 device
+    tensor at once (`pa_binarize_regions`): per-class thresholds and minimum durations (scalars are shared) ->
+    list of K float64 arrays (n_k, 2) of region start / end times in time order, bit-identical to the host's
+    frame middles.  With `return_tracks`, also K int arrays: the position of every region in the reference's
+    track-name sequence.  Only the region lists cross to the host.  `capacity` (regions per class before
+    merging) defaults to the most a class can have, T // 2."""
+    if scores.dim() != 2 or scores.dtype != torch.float32:
+        raise ValueError("binarize_regions expects a (frames, classes) float32 tensor")
+    x = scores.contiguous()
+    T, K = x.shape
+    dev = x.device
+
+    def per_class(v, dtype):
+        return np.ascontiguousarray(np.broadcast_to(np.asarray(v, dtype=dtype), (K,)))
+
+    on, off = per_class(onset, np.float32), per_class(offset, np.float32)
+    d_on, d_off = per_class(min_duration_on, np.float64), per_class(min_duration_off, np.float64)
+    cap = T // 2 if capacity is None else int(capacity)
+    lib = ffi.load()
+    counts = torch.empty(K, dtype=torch.int32, device=dev)
+    regions = torch.empty((K, cap, 2), dtype=torch.float64, device=dev)
+    tracks = torch.empty((K, cap), dtype=torch.int32, device=dev)
+    nbytes = int(lib.pa_binarize_regions_workspace_bytes(T, K, cap))
+    workspace = torch.empty(max(nbytes, 8), dtype=torch.uint8, device=dev)
+    ffi.check(lib.pa_binarize_regions(
+        ffi.ptr(x), T, K, on.ctypes.data, off.ctypes.data, d_on.ctypes.data, d_off.ctypes.data,
+        float(frames.start), float(frames.duration), float(frames.step), cap, ffi.ptr(counts), ffi.ptr(regions),
+        ffi.ptr(tracks), ffi.ptr(workspace), nbytes, ffi.stream()), "pa_binarize_regions")
+    n = counts.cpu().numpy()
+    # one packed copy of the filled prefixes: rows of class k first, then k + 1, ...
+    packed = torch.cat([regions[k, :n[k]] for k in range(K)]).cpu().numpy()
+    bounds = np.concatenate([[0], np.cumsum(n)])
+    out = [packed[bounds[k]:bounds[k + 1]] for k in range(K)]
+    if not return_tracks:
+        return out
+    packed_tracks = torch.cat([tracks[k, :n[k]] for k in range(K)]).cpu().numpy()
+    return out, [packed_tracks[bounds[k]:bounds[k + 1]] for k in range(K)]
 
 
 @ffi.on_device(lambda scores, *a, **k: scores.device)

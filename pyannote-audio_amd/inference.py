@@ -169,6 +169,41 @@ class Inference(BaseInference):
             aggregated.data = aggregated.crop(Segment(0.0, num_samples / sample_rate), mode="loose")
         return aggregated
 
+    def slide_device(self, waveform: torch.Tensor, sample_rate: int, hook: Optional[Callable] = None
+                     ) -> Tuple[torch.Tensor, SlidingWindow]:
+        """`slide` of a frame-level model whose aggregate never leaves the device: -> (frames, classes) float32
+        device tensor and its frame grid.  Same kernels and arguments as `slide`, so the values are bit-identical
+        to `slide(...).data`; the padding of the last chunk is cut off as a frame count (the rows `crop(...,
+        mode="loose")` keeps are a prefix).  For callers that go on working on the device
+        (MultiLabelSegmentation); nothing is copied to the host."""
+        specifications = self.model.specifications
+        if specifications.resolution == Resolution.CHUNK or specifications.powerset or self.skip_aggregation \
+                or self.pre_aggregation_hook is not None or specifications.permutation_invariant:
+            raise ValueError("slide_device aggregates the scores of a frame-level multi-label model on the device: "
+                             "no powerset conversion, no pre-aggregation hook, no skipped aggregation")
+        window_size: int = self.model.audio.get_num_samples(self.duration)
+        step_size: int = round(self.step * sample_rate)
+        _, num_samples = waveform.shape
+        num_chunks, has_last_chunk = self.num_chunks(num_samples, window_size, step_size)
+        total = num_chunks + has_last_chunk
+        wav = waveform.to(self.model.device, torch.float32).contiguous().view(-1)
+        if hook is not None:
+            hook(completed=0, total=total)
+        scores, _ = self._forward(wav, step_size, total, window_size, want_logp=True, want_multilabel=False)
+        self.last_device_output = scores
+        self.last_host_output = None
+        self.last_enqueued = time.perf_counter()
+        if hook is not None:
+            hook(completed=total, total=total)
+        from . import frames as frame_ops
+        aggregated, frames = frame_ops.aggregate_device(
+            scores, SlidingWindow(start=0.0, duration=self.duration, step=self.step), self.model.receptive_field,
+            self.model.device, warm_up=self.warm_up, hamming=True, missing=0.0)
+        if has_last_chunk:
+            (first, stop), = frames.crop(Segment(0.0, num_samples / sample_rate), mode="loose", return_ranges=True)
+            aggregated = aggregated[max(first, 0):min(stop, aggregated.shape[0])]
+        return aggregated, frames
+
     def _slide_chunks(self, waveform: torch.Tensor, sample_rate: int, hook: Optional[Callable]
                       ) -> SlidingWindowFeature:
         """chunk-level models (embeddings): one vector per chunk, no aggregation (core/inference.py:248-254,
