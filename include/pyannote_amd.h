@@ -106,6 +106,17 @@ int pa_sinc_fir_span(const float* wav, long wav_len, long span, const float* fil
 int pa_sinc_fix_pool(const float* S, long Pc, int positions_per_chunk_step, int B, int P, const float* mean,
                      const float* rstd, float gamma, float beta, const float* filt_packed, float* tap_sums,
                      float* out, void* stream);
+/* The same with the span re-centred, what pa_seg_forward runs: a DC offset that is large against the level of the
+ * recording cancels in the fix-up above (the error grows like sqrt(1 + (mean / std)^2)).  mean / rstd: the chunk
+ * statistics on the device, chunk 0 first (pa_sinc_fir_span_centred reads chunk 0's only).  m0 = mean[0] if
+ * |mean[0]| rstd[0] > 0.5, else 0 (then S and the fix-up are those of the functions above, bit for bit) is taken off
+ * the samples on load, and a chunk with |mean[b] - m0| rstd[b] > 0.5 is computed from wav (wav_len, N as in
+ * pa_sinc_fir_pool, stride 10) by the per-chunk kernel instead of being fixed up. */
+int pa_sinc_fir_span_centred(const float* wav, long wav_len, long span, const float* mean0, const float* rstd0,
+                             const float* filt_packed, float* S, void* stream);
+int pa_sinc_fix_pool_centred(const float* S, long Pc, int positions_per_chunk_step, int B, int P, const float* wav,
+                             long wav_len, int N, const float* mean, const float* rstd, float gamma, float beta,
+                             const float* filt_packed, float* tap_sums, float* out, void* stream);
 int pa_conv5_pool(const float* xin, int B, int cin, int Lin, const float* in_mean,
                   const float* in_rstd, const float* gam, const float* bet, const float* w_packed,
                   const float* bias64, float* out, void* stream);

@@ -25,7 +25,8 @@ struct SegPlan {
 };
 
 // see seg_frontend.hip (k_sinc_fix_pool).  Measured on MI355X (round 4, one audio-hour = 3 591 chunks): k_sinc_fir_pool
-// 21.2 ms -> k_sinc_fir_span 2.6 ms + k_sinc_fix_pool 3.2 ms, pipeline step 914.9 -> 903.7 ms; parity test
+// 21.2 ms -> k_sinc_fir_span 2.6 ms + k_sinc_fix_pool 3.2 ms, pipeline step 914.9 -> 903.7 ms; parity tests
+// tests/test_seg_frontend_gpu.py::test_shared_sinc_pair* (float64, DC offsets included) and
 // tests/test_seg_gpu.py::test_shared_sinc_layer_matches_the_per_chunk_layer.
 inline bool shared_sinc_wanted(const pa_seg_weights* w, int B, int N, int64_t chunk_stride) {
   const char* e = getenv("PA_SEG_SHARED_SINC");
@@ -152,10 +153,12 @@ int pa_seg_forward(const pa_seg_weights* w, const float* wav, int64_t wav_len, i
   // SincNet (models/blocks/sincnet.py:163-184)
   RUN(pa_row_stats(wav, chunk_stride, wav_len, B, p.N, 1e-5f, ws + p.wav_mean, ws + p.wav_rstd, stream));
   if (p.span_pos > 0) {
-    RUN(pa_sinc_fir_span(wav, wav_len, p.span, w->sinc_filt, ws + p.span_s, stream));
-    RUN(pa_sinc_fix_pool(ws + p.span_s, p.span_pos, (int)(chunk_stride / 10), B, p.P1, ws + p.wav_mean,
-                         ws + p.wav_rstd, w->wav_gamma, w->wav_beta, w->sinc_filt, ws + p.tap_sums, ws + p.s1,
-                         stream));
+    // (chunk 0's statistics decide the constant the span is re-centred by: no further pass over the audio)
+    RUN(pa_sinc_fir_span_centred(wav, wav_len, p.span, ws + p.wav_mean, ws + p.wav_rstd, w->sinc_filt, ws + p.span_s,
+                                 stream));
+    RUN(pa_sinc_fix_pool_centred(ws + p.span_s, p.span_pos, (int)(chunk_stride / 10), B, p.P1, wav, wav_len, p.N,
+                                 ws + p.wav_mean, ws + p.wav_rstd, w->wav_gamma, w->wav_beta, w->sinc_filt,
+                                 ws + p.tap_sums, ws + p.s1, stream));
   } else {
     RUN(pa_sinc_fir_pool(wav, wav_len, chunk_stride, B, p.N, w->sinc_stride, ws + p.wav_mean,
                          ws + p.wav_rstd, w->wav_gamma, w->wav_beta, w->sinc_filt, ws + p.s1, stream));

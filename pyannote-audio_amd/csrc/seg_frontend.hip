@@ -62,17 +62,32 @@ constexpr int SINC_PT = 128;                       // pooled outputs per workgro
 constexpr int SINC_XS = 30 * SINC_PT + 256;        // staged samples (>= 30*PT + 242)
 constexpr int SINC_OS = SINC_PT + 4;               // out-tile row stride in LDS
 constexpr int SINC_T = 640;                        // threads
+// the shared layer keeps a chunk while |mean_b - m0| <= SINC_DEMOTE standard deviations of that chunk (DESIGN.md,
+// "What the shared sinc layer's error depends on"): its rounding error grows like sqrt(1 + (that distance)^2)
+constexpr float SINC_DEMOTE = 0.5f;
 
 // RAW = true (the sinc layer ONCE for a whole span of overlapping chunks, see k_sinc_fix_pool): no normalisation on
 // load, no magnitude, no pooling -- MFMA row i is convolution position i, `P` counts convolution positions and `out`
 // is (80, P) raw filter outputs of the span [wav, wav + N).
 // STR: the SincNet stride (models/blocks/sincnet.py:58-69 accepts any; the released checkpoints use 10).  The staged
 // sample window of a workgroup is 3 STR SINC_PT + 256 floats (30 KB at STR = 20).
+//
+// centred (the shared layer, see k_sinc_fix_pool): mean / rstd of chunk 0 decide the constant m0 that is taken off
+// the raw samples (sinc_centre).  RAW: it is subtracted while staging (zero padding behind wav_len included:
+// S = sinc(x - m0) of the zero-extended span).  !RAW: the launch serves only the chunks the shared layer hands back
+// (sinc_demoted); the workgroups of every other chunk leave at once.
+__device__ __forceinline__ float sinc_centre(float mean0, float rstd0) {
+  return fabsf(mean0) * rstd0 > SINC_DEMOTE ? mean0 : 0.f;
+}
+__device__ __forceinline__ bool sinc_demoted(float mu, float rstd, float m0) {
+  return fabsf(mu - m0) * rstd > SINC_DEMOTE;
+}
+
 template <bool RAW, int STR = 10>
 __global__ __launch_bounds__(SINC_T) void k_sinc_fir_pool(
     const float* __restrict__ wav, long wav_len, long chunk_stride, int N, int stride, int P,
     const float* __restrict__ mean, const float* __restrict__ rstd, float gamma, float beta,
-    const float* __restrict__ filt, float* __restrict__ out) {
+    const float* __restrict__ filt, float* __restrict__ out, int centred) {
   constexpr int XS_MAX = 3 * STR * SINC_PT + 256;   // (= SINC_XS at STR = 10)
   extern __shared__ __attribute__((aligned(16))) float smem[];
   float* xs = smem;                // [XS_MAX]
@@ -86,7 +101,8 @@ __global__ __launch_bounds__(SINC_T) void k_sinc_fir_pool(
 
   // stage normalised samples [PS*p0, PS*p0 + nstage)
   const long cbase = (long)b * chunk_stride;
-  const float mu = RAW ? 0.f : mean[b], rs = RAW ? 1.f : rstd[b] * gamma;
+  if (!RAW && centred && !sinc_demoted(mean[b], rstd[b], sinc_centre(mean[0], rstd[0]))) return;   // (uniform)
+  const float mu = RAW ? (centred ? sinc_centre(mean[0], rstd[0]) : 0.f) : mean[b], rs = RAW ? 1.f : rstd[b] * gamma;
   if (RAW) beta = 0.f;
   // (all loads of a thread are issued before the first use: as a plain loop the compiler waits for every load
   //  in turn)
@@ -147,6 +163,16 @@ __global__ __launch_bounds__(SINC_T) void k_sinc_fir_pool(
 // 10 convolution positions and the waveform InstanceNorm is affine, so with S = sinc(raw span), S1[f] = sum of
 // the taps of filter f and g = rstd * gamma:
 //     sinc((x - mu) g + beta)[f][q] = g (S[f][c Q + q] - mu S1[f]) + beta S1[f]
+// In float32 the subtraction cancels when mu S1 dominates S, i.e. when the offset of the recording is large against
+// its level (a quiet recording with a DC offset of 0.1 leaves the contract by a factor of 2 to 13).  So the span is
+// filtered with ONE constant m0 taken off on load:
+//     S = sinc(raw - m0),    sinc((x - mu) g + beta) = g (S - (mu - m0) S1) + beta S1
+// and what cancels now is the distance of a chunk's mean from m0, not the offset.  m0 is chunk 0's mean (which
+// pa_row_stats has just written) when that mean is further than SINC_DEMOTE of chunk 0's standard deviations from
+// zero, and zero otherwise (sinc_centre): a recording without an offset worth the name keeps the arithmetic of the
+// raw span, bit for bit.  A chunk whose mean is further than SINC_DEMOTE of its own standard deviations from m0 (a
+// span whose offset steps) is not fixed up at all: the per-chunk kernel computes it from the waveform in the same
+// call (sinc_demoted: one device-side rule for both).  centred == 0: the formula on the raw span for every chunk.
 // k_sinc_tapsum: S1 from the packed B-operand image.  k_sinc_fix_pool: the fix-up + |.| + maxpool3 of chunk b,
 // (B, 80, P) out, as k_sinc_fir_pool<false> writes it.  grid = (ceil(P / 256), B), block = 256; a thread walks
 // the 80 filters of its pooled position (reads 12 contiguous bytes per filter, coalesced across the wave).
@@ -163,10 +189,13 @@ __global__ __launch_bounds__(128) void k_sinc_tapsum(const float* __restrict__ f
 __global__ __launch_bounds__(256) void k_sinc_fix_pool(const float* __restrict__ S, long Pc, int Q, int P,
                                                         const float* __restrict__ mean,
                                                         const float* __restrict__ rstd, float gamma, float beta,
-                                                        const float* __restrict__ S1, float* __restrict__ out) {
+                                                        const float* __restrict__ S1, float* __restrict__ out,
+                                                        int centred) {
   const int b = blockIdx.y, p = blockIdx.x * 256 + threadIdx.x;
   if (p >= P) return;
-  const float mu = mean[b], g = rstd[b] * gamma;
+  const float m0 = centred ? sinc_centre(mean[0], rstd[0]) : 0.f;
+  if (centred && sinc_demoted(mean[b], rstd[b], m0)) return;
+  const float mu = mean[b] - m0, g = rstd[b] * gamma;
   const float* src = S + (long)b * Q + 3 * p;
   float* dst = out + (long)b * 80 * P + p;
 #pragma unroll 8
@@ -336,7 +365,7 @@ int pa_sinc_fir_pool(const float* wav, long wav_len, long chunk_stride, int B, i
                               (int)lds);                                                                           \
     hipLaunchKernelGGL((pa::k_sinc_fir_pool<false, S>), dim3(pa::cdiv(P, pa::SINC_PT), B), dim3(pa::SINC_T), lds,  \
                        (hipStream_t)stream, wav, wav_len, chunk_stride, N, stride, P, mean, rstd, gamma, beta,      \
-                       filt_packed, out);                                                                          \
+                       filt_packed, out, 0);                                                                       \
   } while (0)
   // the strides that are built (the kernel's staging window and MFMA row pitch are compile-time)
   switch (stride) {
@@ -356,10 +385,11 @@ int pa_sinc_fir_pool(const float* wav, long wav_len, long chunk_stride, int B, i
   return 0;
 }
 
-// EXPERIMENTAL (see k_sinc_fix_pool).  S: (80, Pc) raw sinc outputs of the span wav[0, span) (zeros past wav_len),
-// Pc = (span - 251) / 10 + 1.
-int pa_sinc_fir_span(const float* wav, long wav_len, long span, const float* filt_packed, float* S,
-                     void* stream) {
+// EXPERIMENTAL (see k_sinc_fix_pool).  S: (80, Pc) sinc outputs of the span wav[0, span) - m0 (zeros past wav_len
+// before the subtraction), Pc = (span - 251) / 10 + 1.  mean0 / rstd0: the statistics of chunk 0 on the device, which
+// decide m0 (sinc_centre); null: m0 = 0, the raw span.
+static int sinc_fir_span(const float* wav, long wav_len, long span, const float* mean0, const float* rstd0,
+                         const float* filt_packed, float* S, void* stream) {
   if (span < 251) return 0;
   PA_REQUIRE(span <= 0x7fffffffL, "pa_sinc_fir_span: span of %ld samples is too long", span);
   const int Pc = (int)((span - 251) / 10 + 1);
@@ -368,12 +398,23 @@ int pa_sinc_fir_span(const float* wav, long wav_len, long span, const float* fil
                             (int)lds);
   pa::ProfScope prof("k_sinc_fir_span", stream, 2.0 * 80 * 251 * (double)Pc, 4.0 * span + 4.0 * 80 * Pc);
   hipLaunchKernelGGL(pa::k_sinc_fir_pool<true>, dim3(pa::cdiv(Pc, pa::SINC_PT), 1), dim3(pa::SINC_T), lds,
-                     (hipStream_t)stream, wav, wav_len, 0L, (int)span, 10, Pc, (const float*)nullptr,
-                     (const float*)nullptr, 1.f, 0.f, filt_packed, S);
+                     (hipStream_t)stream, wav, wav_len, 0L, (int)span, 10, Pc, mean0, rstd0, 1.f, 0.f, filt_packed, S,
+                     mean0 != nullptr ? 1 : 0);
   PA_CHECK_LAUNCH("pa_sinc_fir_span");
   return 0;
 }
 
+int pa_sinc_fir_span(const float* wav, long wav_len, long span, const float* filt_packed, float* S, void* stream) {
+  return sinc_fir_span(wav, wav_len, span, nullptr, nullptr, filt_packed, S, stream);
+}
+
+int pa_sinc_fir_span_centred(const float* wav, long wav_len, long span, const float* mean0, const float* rstd0,
+                             const float* filt_packed, float* S, void* stream) {
+  PA_REQUIRE(mean0 != nullptr && rstd0 != nullptr, "pa_sinc_fir_span_centred: the statistics of chunk 0 are missing");
+  return sinc_fir_span(wav, wav_len, span, mean0, rstd0, filt_packed, S, stream);
+}
+
+// the formula on the raw span for every chunk (S of pa_sinc_fir_span)
 int pa_sinc_fix_pool(const float* S, long Pc, int positions_per_chunk_step, int B, int P, const float* mean,
                      const float* rstd, float gamma, float beta, const float* filt_packed, float* tap_sums,
                      float* out, void* stream) {
@@ -381,8 +422,33 @@ int pa_sinc_fix_pool(const float* S, long Pc, int positions_per_chunk_step, int 
   pa::ProfScope prof("k_sinc_fix_pool", stream, 8.0 * B * 80 * 3.0 * P, 4.0 * B * 80 * 4.0 * P);
   hipLaunchKernelGGL(pa::k_sinc_tapsum, dim3(1), dim3(128), 0, (hipStream_t)stream, filt_packed, tap_sums);
   hipLaunchKernelGGL(pa::k_sinc_fix_pool, dim3(pa::cdiv(P, 256), B), dim3(256), 0, (hipStream_t)stream, S, Pc,
-                     positions_per_chunk_step, P, mean, rstd, gamma, beta, (const float*)tap_sums, out);
+                     positions_per_chunk_step, P, mean, rstd, gamma, beta, (const float*)tap_sums, out, 0);
   PA_CHECK_LAUNCH("pa_sinc_fix_pool");
+  return 0;
+}
+
+// S of pa_sinc_fir_span_centred with the same mean / rstd (chunk 0 first).  wav, wav_len, N: what pa_sinc_fir_pool
+// takes (chunk b starts 10 positions_per_chunk_step samples after chunk b - 1), for the chunks that are too far from
+// m0 to be fixed up.
+int pa_sinc_fix_pool_centred(const float* S, long Pc, int positions_per_chunk_step, int B, int P, const float* wav,
+                             long wav_len, int N, const float* mean, const float* rstd, float gamma, float beta,
+                             const float* filt_packed, float* tap_sums, float* out, void* stream) {
+  if (B <= 0 || P <= 0) return 0;
+  PA_REQUIRE(N >= 251 && P == ((N - 251) / 10 + 1) / 3, "pa_sinc_fix_pool_centred: %d pooled positions of %d samples",
+             P, N);
+  pa::ProfScope prof("k_sinc_fix_pool", stream, 8.0 * B * 80 * 3.0 * P, 4.0 * B * 80 * 4.0 * P);
+  hipLaunchKernelGGL(pa::k_sinc_tapsum, dim3(1), dim3(128), 0, (hipStream_t)stream, filt_packed, tap_sums);
+  hipLaunchKernelGGL(pa::k_sinc_fix_pool, dim3(pa::cdiv(P, 256), B), dim3(256), 0, (hipStream_t)stream, S, Pc,
+                     positions_per_chunk_step, P, mean, rstd, gamma, beta, (const float*)tap_sums, out, 1);
+  {
+    const size_t lds = (pa::SINC_XS + 80 * pa::SINC_OS) * sizeof(float);
+    (void)hipFuncSetAttribute((const void*)pa::k_sinc_fir_pool<false, 10>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                              (int)lds);
+    hipLaunchKernelGGL((pa::k_sinc_fir_pool<false, 10>), dim3(pa::cdiv(P, pa::SINC_PT), B), dim3(pa::SINC_T), lds,
+                       (hipStream_t)stream, wav, wav_len, 10L * positions_per_chunk_step, N, 10, P, mean, rstd, gamma,
+                       beta, filt_packed, out, 1);
+  }
+  PA_CHECK_LAUNCH("pa_sinc_fix_pool_centred");
   return 0;
 }
 

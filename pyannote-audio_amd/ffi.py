@@ -155,6 +155,9 @@ def load():
     lib.pa_sinc_fir_span.argtypes = [c_fp, C.c_long, C.c_long, c_fp, c_fp, c_fp]
     lib.pa_sinc_fix_pool.argtypes = [c_fp, C.c_long, C.c_int, C.c_int, C.c_int, c_fp, c_fp, C.c_float, C.c_float,
                                      c_fp, c_fp, c_fp, c_fp]
+    lib.pa_sinc_fir_span_centred.argtypes = [c_fp, C.c_long, C.c_long, c_fp, c_fp, c_fp, c_fp, c_fp]
+    lib.pa_sinc_fix_pool_centred.argtypes = [c_fp, C.c_long, C.c_int, C.c_int, C.c_int, c_fp, C.c_long, C.c_int, c_fp,
+                                             c_fp, C.c_float, C.c_float, c_fp, c_fp, c_fp, c_fp]
     lib.pa_conv5_pool.argtypes = [c_fp, C.c_int, C.c_int, C.c_int, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp,
                                   c_fp, c_fp]
     lib.pa_norm_transpose.argtypes = [c_fp, C.c_int, C.c_int, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp]

@@ -8,7 +8,8 @@ The rules every one of them follows:
   * the kernel is then held to the contract, or to twice the distance of float32 torch from the truth where that is
     larger (a different summation order of the same float32 arithmetic);
   * every output lives inside a NaN-filled buffer: one guard block in front, one behind, and NaN in every gap that a
-    leading dimension larger than the row leaves.  Guards and gaps are NaN afterwards, nothing written is."""
+    leading dimension larger than the row leaves.  Guards and gaps are NaN afterwards, nothing written is;
+  * where a kernel ends in a max (NaN would be swallowed), its inputs live between blocks of +-1e30 (GuardedInput)."""
 import ctypes as C
 import os
 
@@ -66,6 +67,27 @@ class Guarded:
     def untouched(self) -> bool:
         torch.cuda.synchronize()
         return bool(self._untouched(self.buf.cpu()).all())
+
+
+class GuardedInput:
+    """A kernel INPUT between two blocks of large finite values of alternating sign (+-1e30).  NaN would not do here:
+    the front-end kernels end in fmaxf, and fmaxf(NaN, x) is x, so NaN around an input hides an over-read instead of
+    showing it; 1e30 of either sign survives |.|, max and a leaky ReLU of either branch.  `behind`: elements of poison
+    behind the data (at least one guard block; more where a kernel is told of samples that lie behind the end of the
+    buffer and must take them as zeros -- the poison stays inside the allocation)."""
+    POISON = 1e30
+
+    def __init__(self, data, device, behind: int = GUARD):
+        data = data.reshape(-1).float()
+        self.n, behind = data.numel(), max(int(behind), GUARD)
+        host = torch.full((GUARD + self.n + behind,), self.POISON)
+        host[1::2] = -self.POISON
+        host[GUARD:GUARD + self.n] = data
+        self.buf = host.to(device)
+
+    @property
+    def ptr(self):
+        return C.c_void_p(self.buf.data_ptr() + GUARD * self.buf.element_size())
 
 
 def assert_parity(name, got, truth64, ref32, limit=1.0):

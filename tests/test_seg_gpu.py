@@ -57,8 +57,8 @@ def test_frontend_stages(seg, gpu_device):
     st = ffi.stream()
     mean = torch.empty(B, device=dev); rstd = torch.empty(B, device=dev)
     ffi.check(lib.pa_row_stats(ffi.ptr(xd), N, xd.numel(), B, N, 1e-5, ffi.ptr(mean), ffi.ptr(rstd), st))
-    report("wav_mean", mean, x.mean(-1).view(-1))
-    report("wav_rstd", rstd, 1.0 / torch.sqrt(x.var(-1, unbiased=False) + 1e-5).view(-1))
+    assert north_star_ratio("wav_mean", mean, x.double().mean(-1).view(-1)) <= 1.0
+    assert north_star_ratio("wav_rstd", rstd, 1.0 / torch.sqrt(x.double().var(-1, unbiased=False) + 1e-5).view(-1)) <= 1.0
     P1 = p1.shape[-1]
     s1 = torch.zeros(B, 80, P1, device=dev)
     ffi.check(lib.pa_sinc_fir_pool(ffi.ptr(xd), xd.numel(), N, B, N, 10, ffi.ptr(mean), ffi.ptr(rstd),
@@ -222,6 +222,38 @@ def test_shared_sinc_layer_matches_the_per_chunk_layer(seg, gpu_device):
     top2 = outs["0"][0].topk(2, dim=-1).values
     decided = (top2[..., 0] - top2[..., 1]) > 1e-4
     same = (outs["1"][1] == outs["0"][1]).all(dim=-1)
+    assert bool((same | ~decided).all())
+
+
+def test_quiet_recording_with_a_dc_offset(seg, gpu_device):
+    """A DC offset of 0.1 under noise of std 0.01 (7 chunks of 160 000, step 16 000): the shared sinc layer's fix-up
+    g (S - mu S1) + beta S1 cancels against the offset unless the span is re-centred by chunk 0's mean
+    (csrc/seg_frontend.hip, k_sinc_fix_pool, pa_sinc_*_centred; tests/test_seg_frontend_gpu.py holds the layer itself
+    to float64).  Here the whole forward against the oracle, with the shared layer (default) and without, and the two
+    against each other."""
+    model, pack, eng = seg
+    N, STEP, B = 160000, 16000, 7
+    g = torch.Generator().manual_seed(31)
+    x = (0.1 + 0.01 * torch.randn((B - 1) * STEP + N, generator=g)).float()
+    chunks = torch.stack([x[c * STEP: c * STEP + N] for c in range(B)]).unsqueeze(1)
+    with torch.inference_mode():
+        ref = model(chunks)
+    xd = x.to(gpu_device)
+    outs = {}
+    for flag in (None, "0"):
+        if flag is not None:
+            os.environ["PA_SEG_SHARED_SINC"] = flag
+        try:
+            logp, ml = eng.forward_strided(xd, STEP, B, N)
+            outs[flag] = (logp.cpu(), ml.cpu())
+        finally:
+            os.environ.pop("PA_SEG_SHARED_SINC", None)
+    assert north_star_ratio("dc_offset_logp_shared_sinc", outs[None][0], ref) <= 1.0
+    assert north_star_ratio("dc_offset_logp_per_chunk_sinc", outs["0"][0], ref) <= 1.0
+    assert north_star_ratio("dc_offset_logp_shared_vs_per_chunk", outs[None][0], outs["0"][0]) <= 1.0
+    top2 = outs["0"][0].topk(2, dim=-1).values
+    decided = (top2[..., 0] - top2[..., 1]) > 1e-4
+    same = (outs[None][1] == outs["0"][1]).all(dim=-1)
     assert bool((same | ~decided).all())
 
 
