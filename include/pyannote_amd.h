@@ -581,6 +581,35 @@ int pa_vbx_iteration(const double* fea, const double* Phi, int n, int s, int d, 
                      int first, double* gamma, double* elbo_out, void* workspace, size_t workspace_bytes,
                      void* stream);
 
+/* ---- frame-level diarization error rates (utils/metric.py:41-93,
+ *      torchmetrics/functional/audio/diarization_error_rate.py:33-162) ---- */
+
+/* File mode: ref (T, Sr) and hyp (T, Sh) uint8 (non-zero = on), row-major, 1 <= Sr, Sh <= 32, T < 2^31;
+ * keep (T) uint8 optional (NULL): frames with 0 are ignored.  One pass, exact integer sums.
+ * out, int64, Sr*Sh + Sr + Sh + 4 values, overwritten:
+ *   cooc (Sr, Sh)   frames in which reference speaker i and hypothesis speaker j are both on
+ *   ref_frames (Sr), hyp_frames (Sh)
+ *   total = sum Nr, false_alarm = sum max(0, Nh - Nr), missed = sum max(0, Nr - Nh), both = sum min(Nr, Nh)
+ * (Nr / Nh = speakers on in a frame).  Under a one-to-one speaker mapping pi, correct = sum_i cooc[i][pi(i)] and
+ * confusion = both - correct; the reference's mapping maximises `correct` (csrc/metrics.hip). */
+int pa_der_counts(const uint8_t* ref, const uint8_t* hyp, const uint8_t* keep, long T, int Sr, int Sh,
+                  int64_t* out, void* stream);
+
+/* Chunk mode: preds (B, S, F) fp32 scores, target (B, S, F) 0/1 as uint8 or (target_is_f32) fp32, thresholds (Q)
+ * fp32, 1 <= Q <= 64, 1 <= S <= 32.  perm (B, S) int32: score row perm[b][i] plays target speaker i (outside
+ * 0..S-1: nobody does); NULL with S <= 4: the kernel takes the permutation with the smallest summed squared
+ * error (fp64), the first in lexicographic order among equals.  Hypothesis at threshold q = score > thresholds[q]
+ * (fp32 comparison).  counts (B, Q, 3) int32 = false alarm, missed detection, confusion; total (B) int32 = target
+ * speech frames.  Nothing of size F * Q is allocated or written. */
+int pa_der_chunks(const float* preds, const void* target, int target_is_f32, int B, int S, int F,
+                  const float* thresholds, int Q, const int32_t* perm, int32_t* counts, int32_t* total,
+                  void* stream);
+/* bytes of the per-chunk tables (`counts` and `total` above) that a caller who only wants the batch sums
+ * allocates as scratch: 4 B (3 Q + 1), whatever F is */
+size_t pa_der_chunks_workspace_bytes(int B, int Q);
+/* out (3 Q + 1) int64, overwritten: sums over the B chunks of counts (Q, 3), then of total */
+int pa_der_chunks_sum(const int32_t* counts, const int32_t* total, int B, int Q, int64_t* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -262,6 +262,11 @@ _OPTIONAL: list[tuple] = [
                               C.c_int, C.c_int, c_fp, c_fp, c_fp, C.c_size_t, c_fp], C.c_int),
     ("pa_mfcc_features", [C.POINTER(XvecMfccWeights), c_fp, C.c_int64, C.c_int64, C.c_int, C.c_int, c_fp, c_fp,
                           C.c_size_t, c_fp], C.c_int),
+    ("pa_der_counts", [c_fp, c_fp, c_fp, C.c_long, C.c_int, C.c_int, c_fp, c_fp], C.c_int),
+    ("pa_der_chunks", [c_fp, c_fp, C.c_int, C.c_int, C.c_int, C.c_int, c_fp, C.c_int, c_fp, c_fp, c_fp, c_fp],
+     C.c_int),
+    ("pa_der_chunks_workspace_bytes", [C.c_int, C.c_int], C.c_size_t),
+    ("pa_der_chunks_sum", [c_fp, c_fp, C.c_int, C.c_int, c_fp, c_fp], C.c_int),
 ]
 
 
