@@ -355,6 +355,45 @@ size_t pa_sser_workspace_bytes(const pa_sser_weights* w, int num_chunks, int num
 int pa_sser_forward(const pa_sser_weights* w, const float* wav, int64_t wav_len, int64_t chunk_stride,
                     int num_chunks, int num_samples, const float* rel_bias, float* logp, uint8_t* multilabel,
                     void* workspace, size_t workspace_bytes, void* stream);
+/* building blocks of pa_sser_forward (exported for unit parity tests): the encoder kernels that are not GEMMs.
+ * Layout: channels-last rows; row (b, t) of a stage is row b * P + t of its buffer, P >= T the per-chunk row pitch.
+ * Rows T .. P - 1 of a chunk are padding: never read as data (pa_w2v_conv0 writes zeros there, the others leave them
+ * alone).  Every function checks its arguments before it computes with them and returns 3, having launched nothing,
+ * when one is refused; B <= 0, rows <= 0 and n <= 0 are an empty success (0).
+ *
+ * pa_w2v_conv0: out[b * P + t][c] = bias[c] + sum_j w[c * K0 + j] * chunk_b[t * S0 + j] for t < T, 0 for T <= t < P;
+ *   chunk_b = wav[b * chunk_stride, + N), zeros from wav_len on; w: [C][K0]; bias: [C] or NULL; 1 <= K0, S0 <= 16;
+ *   P >= T >= 1, C >= 1, chunk_stride >= 0.  The caller passes T = (N - K0) / S0 + 1. */
+int pa_w2v_conv0(const float* wav, long wav_len, long chunk_stride, int B, int N, int T, int P, int C, int K0, int S0,
+                 const float* w, const float* bias, float* out, void* stream);
+/* GroupNorm(num_groups = C) + GELU (exact erf) in place: per (chunk, channel) mean and biased variance over the T valid
+ * rows of x [B * P][C], eps 1e-5; gamma, beta: [C]; mean_scratch, rstd_scratch: [B][C] floats, left holding the
+ * statistics.  P >= T >= 1, C >= 1. */
+int pa_w2v_group_norm_gelu(float* x, int B, int T, int P, int C, const float* gamma, const float* beta,
+                           float* mean_scratch, float* rstd_scratch, void* stream);
+/* LayerNorm over the C channels of each of `rows` contiguous rows [rows][C] (eps 1e-5, biased variance), then GELU if
+ * gelu != 0; out may be in.  1 <= C <= 1024. */
+int pa_w2v_layernorm(const float* in, float* out, long rows, int C, const float* gamma, const float* beta, int gelu,
+                     void* stream);
+/* convolutional positional embedding: out = x + gelu(grouped conv1d(x, padding KW / 2) + bias) on the frames 0 .. T - 1
+ * of each chunk (the last frame of an even kernel is dropped), zero padding outside [0, T) of the chunk.  x, out:
+ * [B * P][D], distinct buffers; w3: [g][j][ci][co] (groups, taps, input channel, output channel of the group; co
+ * fastest) = torch's weight (D, D / groups, KW) as weight.reshape(groups, CG, CG, KW).permute(0, 3, 2, 1); bias: [D].
+ * groups >= 1, KW >= 1, D % groups == 0, P >= T >= 1, (16 + KW - 1) * D / groups floats within 64 KiB of LDS. */
+int pa_w2v_posconv(const float* x, int B, int T, int P, int D, int groups, int KW, const float* w3, const float* bias,
+                   float* out, void* stream);
+/* attention soft-max in place: S [B][H][T][Tp] (row pitch Tp >= T) <- softmax_k(S * scale + gate[b][h][t] * bias[h][t][k])
+ * over k < T; columns T .. Tp - 1 are set to 0.  bias: [H][T][T] or NULL (no gate; xin, gate_* are then unused).
+ * gate (WavLM): q = xin[b * P + t][h * hd, + hd), hd = D / H; u = gate_w q + gate_b (gate_w [8][hd], gate_b [8]);
+ * gate = ga * (gb * gate_const[h] - 1) + 2 with ga = sigmoid(u0 + .. + u3), gb = sigmoid(u4 + .. + u7).
+ * Tp >= T >= 1, H >= 1, D % H == 0, hd <= 128; with a bias xin, gate_w, gate_b, gate_const non-NULL and P >= T. */
+int pa_w2v_softmax(float* S, int B, int H, int T, int Tp, float scale, const float* bias, const float* xin, int P, int D,
+                   const float* gate_w, const float* gate_b, const float* gate_const, void* stream);
+/* acc[i] = (first ? 0 : acc[i]) + w * x[i], i < n (one fma); n % 4 == 0, both 16-byte aligned */
+int pa_w2v_axpy(float* acc, const float* x, float w, long n, int first, void* stream);
+/* rows [b * P + t][D] -> LSTM input rows out[((b >> 4) * T + t) * 16 + (b & 15)][D]; the chunks B .. 16 * ceil(B / 16) - 1
+ * are zero.  P >= T >= 1, D >= 1. */
+int pa_w2v_to_tiles(const float* x, int B, int T, int P, int D, float* out, void* stream);
 /* outer x inner independent TN GEMMs in one launch (operand z = (zo, zi) starts zo * s?o + zi * s?i floats
  * after its base pointer); act 0 or 3 (GELU) */
 int pa_gemm_tn_batched(const float* A, int lda, long sAo, long sAi, const float* W, int ldw, long sWo, long sWi,

@@ -244,10 +244,14 @@ __global__ __launch_bounds__(256) void k_w2v_to_tiles(const float* __restrict__ 
 
 extern "C" {
 
-PA_INTERNAL int pa_w2v_conv0(const float* wav, long wav_len, long chunk_stride, int B, int N, int T, int P, int C, int K0,
-                 int S0, const float* w, const float* bias, float* out, void* stream) {
+// Every launcher validates its arguments before any arithmetic on them and launches nothing when it refuses (return 3);
+// B <= 0, rows <= 0 and n <= 0 are the empty success.
+int pa_w2v_conv0(const float* wav, long wav_len, long chunk_stride, int B, int N, int T, int P, int C, int K0, int S0,
+                 const float* w, const float* bias, float* out, void* stream) {
   if (B <= 0) return 0;
   PA_REQUIRE(K0 >= 1 && K0 <= 16 && S0 >= 1 && S0 <= 16, "pa_w2v_conv0: kernel and stride <= 16 required");
+  PA_REQUIRE(T >= 1 && P >= T && C >= 1, "pa_w2v_conv0: P >= T >= 1 and C >= 1 required (got T %d, P %d, C %d)", T, P, C);
+  PA_REQUIRE(chunk_stride >= 0, "pa_w2v_conv0: chunk_stride >= 0 required (got %ld)", chunk_stride);
   pa::ProfScope prof("k_w2v_conv0", stream, 2.0 * B * T * C * K0, 4.0 * B * (N + (double)P * C));
   hipLaunchKernelGGL(pa::k_w2v_conv0, dim3(pa::cdiv(P, 32), B), dim3(256), 0, (hipStream_t)stream, wav, wav_len,
                      chunk_stride, N, T, P, C, K0, S0, w, bias, out);
@@ -255,9 +259,11 @@ PA_INTERNAL int pa_w2v_conv0(const float* wav, long wav_len, long chunk_stride, 
   return 0;
 }
 
-PA_INTERNAL int pa_w2v_group_norm_gelu(float* x, int B, int T, int P, int C, const float* gamma, const float* beta,
+int pa_w2v_group_norm_gelu(float* x, int B, int T, int P, int C, const float* gamma, const float* beta,
                            float* mean_scratch, float* rstd_scratch, void* stream) {
   if (B <= 0) return 0;
+  PA_REQUIRE(T >= 1 && P >= T && C >= 1, "pa_w2v_group_norm_gelu: P >= T >= 1 and C >= 1 required (got T %d, P %d, C %d)",
+             T, P, C);
   pa::ProfScope prof("k_w2v_group_norm", stream, 8.0 * B * T * C, 16.0 * B * T * C);
   hipLaunchKernelGGL(pa::k_w2v_colstats, dim3(pa::cdiv(C, 64), B), dim3(256), 0, (hipStream_t)stream, x, T, P, C,
                      1e-5f, mean_scratch, rstd_scratch);
@@ -267,10 +273,10 @@ PA_INTERNAL int pa_w2v_group_norm_gelu(float* x, int B, int T, int P, int C, con
   return 0;
 }
 
-PA_INTERNAL int pa_w2v_layernorm(const float* in, float* out, long rows, int C, const float* gamma, const float* beta,
-                     int gelu, void* stream) {
+int pa_w2v_layernorm(const float* in, float* out, long rows, int C, const float* gamma, const float* beta, int gelu,
+                     void* stream) {
   if (rows <= 0) return 0;
-  PA_REQUIRE(C >= 1 && C <= 1024, "pa_w2v_layernorm: C <= 1024 required (got %d)", C);
+  PA_REQUIRE(C >= 1 && C <= 1024, "pa_w2v_layernorm: 1 <= C <= 1024 required (got %d)", C);
   pa::ProfScope prof("k_w2v_layernorm", stream, 8.0 * rows * C, 8.0 * rows * C);
   if (gelu)
     hipLaunchKernelGGL(pa::k_w2v_layernorm<true>, dim3(pa::cdiv(rows, 4)), dim3(256), 0, (hipStream_t)stream, in,
@@ -282,12 +288,17 @@ PA_INTERNAL int pa_w2v_layernorm(const float* in, float* out, long rows, int C, 
   return 0;
 }
 
-PA_INTERNAL int pa_w2v_posconv(const float* x, int B, int T, int P, int D, int groups, int KW, const float* w3,
-                   const float* bias, float* out, void* stream) {
+int pa_w2v_posconv(const float* x, int B, int T, int P, int D, int groups, int KW, const float* w3, const float* bias,
+                   float* out, void* stream) {
   if (B <= 0) return 0;
+  PA_REQUIRE(groups >= 1 && KW >= 1 && D >= 1, "pa_w2v_posconv: groups, kernel and D >= 1 required (got %d, %d, %d)",
+             groups, KW, D);
+  PA_REQUIRE(D % groups == 0, "pa_w2v_posconv: D %% groups == 0 required (got D %d, groups %d)", D, groups);
+  PA_REQUIRE(T >= 1 && P >= T, "pa_w2v_posconv: P >= T >= 1 required (got T %d, P %d)", T, P);
   const int CG = D / groups;
-  const size_t lds = (size_t)(16 + KW - 1) * CG * sizeof(float);
-  PA_REQUIRE(D % groups == 0 && lds <= 64 * 1024, "pa_w2v_posconv: (16 + kernel - 1) * D / groups floats of LDS");
+  const size_t lds = ((size_t)16 + KW - 1) * CG * sizeof(float);
+  PA_REQUIRE(lds <= 64 * 1024, "pa_w2v_posconv: (16 + kernel - 1) * D / groups floats of LDS exceed 64 KiB (%zu bytes)",
+             lds);
   pa::ProfScope prof("k_w2v_posconv", stream, 2.0 * B * T * D * CG * KW, 8.0 * B * T * D);
   hipLaunchKernelGGL(pa::k_w2v_posconv, dim3(pa::cdiv(T, 16), groups, B), dim3(256), lds, (hipStream_t)stream, x, T,
                      P, D, CG, KW, KW / 2, w3, bias, out);
@@ -295,10 +306,16 @@ PA_INTERNAL int pa_w2v_posconv(const float* x, int B, int T, int P, int D, int g
   return 0;
 }
 
-PA_INTERNAL int pa_w2v_softmax(float* S, int B, int H, int T, int Tp, float scale, const float* bias, const float* xin, int P,
-                   int D, const float* gate_w, const float* gate_b, const float* gate_const, void* stream) {
+int pa_w2v_softmax(float* S, int B, int H, int T, int Tp, float scale, const float* bias, const float* xin, int P, int D,
+                   const float* gate_w, const float* gate_b, const float* gate_const, void* stream) {
   if (B <= 0) return 0;
-  PA_REQUIRE(D % H == 0 && D / H <= 128, "pa_w2v_softmax: head dimension <= 128 required");
+  PA_REQUIRE(T >= 1 && Tp >= T, "pa_w2v_softmax: Tp >= T >= 1 required (got T %d, Tp %d)", T, Tp);
+  PA_REQUIRE(H >= 1 && D >= 1, "pa_w2v_softmax: H >= 1 and D >= 1 required (got H %d, D %d)", H, D);
+  PA_REQUIRE(D % H == 0 && D / H <= 128, "pa_w2v_softmax: D %% H == 0 and a head dimension <= 128 required (got D %d, H %d)",
+             D, H);
+  PA_REQUIRE(bias == nullptr ||
+                 (xin != nullptr && gate_w != nullptr && gate_b != nullptr && gate_const != nullptr && P >= T),
+             "pa_w2v_softmax: a position bias needs xin (P >= T), gate_w, gate_b and gate_const");
   const long rows = (long)B * H * T;
   pa::ProfScope prof("k_w2v_softmax", stream, 6.0 * rows * T, 8.0 * rows * T);
   hipLaunchKernelGGL(pa::k_w2v_softmax, dim3(pa::cdiv(rows, 4)), dim3(256), 0, (hipStream_t)stream, S, B, H, T, Tp,
@@ -307,7 +324,7 @@ PA_INTERNAL int pa_w2v_softmax(float* S, int B, int H, int T, int Tp, float scal
   return 0;
 }
 
-PA_INTERNAL int pa_w2v_axpy(float* acc, const float* x, float w, long n, int first, void* stream) {
+int pa_w2v_axpy(float* acc, const float* x, float w, long n, int first, void* stream) {
   if (n <= 0) return 0;
   PA_REQUIRE(n % 4 == 0, "pa_w2v_axpy: n %% 4 == 0 required");
   pa::ProfScope prof("k_w2v_axpy", stream, 2.0 * n, 12.0 * n);
@@ -317,8 +334,9 @@ PA_INTERNAL int pa_w2v_axpy(float* acc, const float* x, float w, long n, int fir
   return 0;
 }
 
-PA_INTERNAL int pa_w2v_to_tiles(const float* x, int B, int T, int P, int D, float* out, void* stream) {
+int pa_w2v_to_tiles(const float* x, int B, int T, int P, int D, float* out, void* stream) {
   if (B <= 0) return 0;
+  PA_REQUIRE(T >= 1 && P >= T && D >= 1, "pa_w2v_to_tiles: P >= T >= 1 and D >= 1 required (got T %d, P %d, D %d)", T, P, D);
   const int ntiles = (B + 15) / 16;
   pa::ProfScope prof("k_w2v_to_tiles", stream, 0.0, 8.0 * B * T * D);
   hipLaunchKernelGGL(pa::k_w2v_to_tiles, dim3(T, ntiles * 16), dim3(256), 0, (hipStream_t)stream, x, B, T, P, D, out);

@@ -252,6 +252,15 @@ _OPTIONAL: list[tuple] = [
     ("pa_sser_workspace_bytes", [C.POINTER(SserWeights), C.c_int, C.c_int], C.c_size_t),
     ("pa_sser_forward", [C.POINTER(SserWeights), c_fp, C.c_int64, C.c_int64, C.c_int, C.c_int, c_fp, c_fp, c_fp,
                          c_fp, C.c_size_t, c_fp], C.c_int),
+    ("pa_w2v_conv0", [c_fp, C.c_long, C.c_long, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_fp,
+                      c_fp, c_fp, c_fp], C.c_int),
+    ("pa_w2v_group_norm_gelu", [c_fp, C.c_int, C.c_int, C.c_int, C.c_int, c_fp, c_fp, c_fp, c_fp, c_fp], C.c_int),
+    ("pa_w2v_layernorm", [c_fp, c_fp, C.c_long, C.c_int, c_fp, c_fp, C.c_int, c_fp], C.c_int),
+    ("pa_w2v_posconv", [c_fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_fp, c_fp, c_fp, c_fp], C.c_int),
+    ("pa_w2v_softmax", [c_fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, c_fp, c_fp, C.c_int, C.c_int, c_fp, c_fp,
+                        c_fp, c_fp], C.c_int),
+    ("pa_w2v_axpy", [c_fp, c_fp, C.c_float, C.c_long, C.c_int, c_fp], C.c_int),
+    ("pa_w2v_to_tiles", [c_fp, C.c_int, C.c_int, C.c_int, C.c_int, c_fp, c_fp], C.c_int),
     ("pa_xvec_num_frames", [C.POINTER(XvecWeights), C.c_int], C.c_int),
     ("pa_xvec_workspace_bytes", [C.POINTER(XvecWeights), C.c_int, C.c_int, C.c_int], C.c_size_t),
     ("pa_xvec_forward", [C.POINTER(XvecWeights), c_fp, C.c_int64, C.c_int64, C.c_int, C.c_int, c_fp,

@@ -78,6 +78,25 @@ def test_wav2vec2_dict_config(gpu_device, layer):
     assert north_star_ratio(f"sseriouss_tiny_layer{layer}", got, ref) <= 1.0
 
 
+def test_wav2vec2_dict_config_group_norm_post_ln(gpu_device):
+    """the branches of pa_sser_forward that otherwise run with the 95 M parameter WavLM base only, at the size of
+    TINY_WAV2VEC2: group_norm feature extractor without convolution biases, post-LN encoder (the encoder-level LayerNorm
+    in front of the layers), an ODD positional kernel (5: no frame is dropped), 96 wide with 3 heads; 1 s chunks"""
+    from oracle import seeded_sseriouss
+    from oracle.models import TINY_WAV2VEC2
+    cfg = dict(TINY_WAV2VEC2, extractor_mode="group_norm", extractor_conv_bias=False, encoder_layer_norm_first=False,
+               encoder_pos_conv_kernel=5, encoder_embed_dim=96, encoder_num_heads=3)
+    model = seeded_sseriouss(wav2vec=dict(cfg), num_layers=2)
+    eng = _engine(model, {"wav2vec": dict(cfg), "wav2vec_layer": -1, "lstm": {"num_layers": 2}}, gpu_device)
+    g = torch.Generator().manual_seed(6)
+    wav = (0.1 * torch.randn(19, 1, 16000, generator=g)).clamp(-1, 1)       # 19 chunks: two 16-chunk LSTM tiles
+    with torch.inference_mode():
+        ref = model(wav)
+    got = eng.forward(wav.to(gpu_device))
+    assert got.shape == ref.shape == (19, eng.frames_of(16000), 7)
+    assert north_star_ratio("sseriouss_tiny_group_norm_post_ln", got, ref) <= 1.0
+
+
 def test_sseriouss_model_and_inference(gpu_device, tmp_path):
     """the product `SSeRiouSS` model class from a reference-format checkpoint, and `Inference` sliding over a
     file with it (10 s / 1 s chunks, 499 frames of 20 ms per chunk) vs the oracle's slide."""
