@@ -162,12 +162,14 @@ def test_linkage_centroid_bit_exact_vs_scipy(gpu_device, n, d, dup, seed):
     assert len(bad) == 0, f"first differing merge {bad[0]}: {got[bad[0]]} vs {want[bad[0]]}"
 
 
-@pytest.mark.parametrize("n,workgroups", [(12300, None), (3000, 4), (12300, 1)])
+@pytest.mark.parametrize("n,workgroups", [(12300, None), (3000, 4), (12300, 1), (13100, 2)])
 def test_linkage_multi_workgroup_vs_scipy(gpu_device, n, workgroups, monkeypatch):
-    """the heap kernels of csrc/linkage.hip on data WITH exact ties (duplicated rows: the heap-free merge gives up at
+    """the heap kernel of csrc/linkage.hip on data WITH exact ties (duplicated rows: the heap-free merge gives up at
     its first pop and the gated heap kernel recomputes the dendrogram): the default at N = 12 300 (one workgroup,
-    heap in global memory), a forced 4-workgroup run (k_linkage_centroid_mw, opt-in through PA_LINKAGE_WGS) on a
-    small problem, a forced single workgroup -- bit-identical to SciPy."""
+    heap in global memory), a forced 4-workgroup run (the multi-workgroup form, opt-in through PA_LINKAGE_WGS) on a
+    small problem, a forced single workgroup, and two workgroups at N = 13 100 (the first round size whose
+    12 (N - 1) heap bytes exceed the LDS budget: multi-workgroup form with the heap in global memory) --
+    bit-identical to SciPy."""
     from scipy.cluster.hierarchy import linkage
     from scipy.spatial.distance import pdist
     from pyannote_audio_amd import distance
@@ -184,6 +186,58 @@ def test_linkage_multi_workgroup_vs_scipy(gpu_device, n, workgroups, monkeypatch
     assert len(bad) == 0, f"first differing merge {bad[0]}: {got[bad[0]]} vs {want[bad[0]]}"
     st = distance.last_linkage_stats
     assert st[8] == 1 and st[7] == n, "expected: heap-free merge gave up on a tie, heap kernel ran"
+
+
+@pytest.mark.parametrize("n", [2, 3, 65])
+def test_linkage_multi_workgroup_small_sizes(gpu_device, n, monkeypatch):
+    """the multi-workgroup form of the heap kernel (3 workgroups) at sizes where a workgroup's slice of the z pass is
+    empty or shorter than a wave.  Every row appears three times, so from N = 3 on the two smallest lower bounds tie
+    at the first pop (both 0) and the heap-free merge hands over; N = 2 is below its smallest size."""
+    from scipy.cluster.hierarchy import linkage
+    from scipy.spatial.distance import pdist
+    from pyannote_audio_amd import distance
+    monkeypatch.setenv("PA_LINKAGE_WGS", "3")
+    rng = np.random.default_rng(n)
+    X = rng.standard_normal(((n + 2) // 3, 32)).astype(np.float32)
+    X /= np.linalg.norm(X, axis=1, keepdims=True)
+    X = X[np.arange(n) // 3]
+    want = linkage(pdist(X), method="centroid")
+    got = distance.linkage_centroid(X, gpu_device)
+    bad = np.nonzero((got != want).any(axis=1))[0]
+    assert len(bad) == 0, f"first differing merge {bad[0]}: {got[bad[0]]} vs {want[bad[0]]}"
+    st = distance.last_linkage_stats
+    assert st[7] == n, "expected: the heap kernel ran"
+    if n >= 3:
+        assert st[8] == 1, "expected: heap-free merge gave up on a tie"
+
+
+@pytest.mark.parametrize("workgroups", [None, 3])
+def test_linkage_heap_pending_overflow(gpu_device, workgroups, monkeypatch):
+    """the heap kernel (heap-free merge switched off) when one merge lowers more lower bounds than its pending list
+    holds (LK_PEND = 256): 600 random unit vectors plus the pair +u/2, -u/2 in the last two rows.  That pair is the
+    closest (distance 1.0 against 1.035 for the runner-up) and its centroid, the origin, is nearer to every other
+    row than that row's neighbour was, so the first merge refreshes all 600 rows at once and the replay reads the
+    candidate bitmap instead of the list -- in the single- and in the multi-workgroup form, bit-identical to SciPy
+    (whose dendrogram has no tied heights here)."""
+    from scipy.cluster.hierarchy import linkage
+    from scipy.spatial.distance import pdist
+    from pyannote_audio_amd import distance
+    monkeypatch.setenv("PA_LINKAGE_FAST", "0")
+    if workgroups is not None:
+        monkeypatch.setenv("PA_LINKAGE_WGS", str(workgroups))
+    rng = np.random.default_rng(11)
+    X = rng.standard_normal((600, 256))
+    X /= np.linalg.norm(X, axis=1, keepdims=True)
+    u = rng.standard_normal(256)
+    u /= np.linalg.norm(u)
+    X = np.concatenate([X, [0.5 * u], [-0.5 * u]]).astype(np.float32)
+    want = linkage(pdist(X), method="centroid")
+    got = distance.linkage_centroid(X, gpu_device)
+    bad = np.nonzero((got != want).any(axis=1))[0]
+    assert len(bad) == 0, f"first differing merge {bad[0]}: {got[bad[0]]} vs {want[bad[0]]}"
+    st = distance.last_linkage_stats
+    assert st[2] >= 1, "expected: a refresh overflowed the pending list"
+    assert st[7] == 602 and st[12] == 0, "expected: the heap kernel ran, the heap-free merge was off"
 
 
 @pytest.mark.parametrize("n,d,wgs", [(3, 8, None), (700, 16, None), (4000, 64, None), (7176, 256, None),
