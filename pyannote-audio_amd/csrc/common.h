@@ -19,6 +19,15 @@ typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 // launchers shared between translation units of the library that are NOT part of the C ABI (include/pyannote_amd.h
 // declares every exported symbol; tests/test_capi.py checks both directions)
 #define PA_INTERNAL __attribute__((visibility("hidden")))
+// csrc/mfcc.hip, csrc/emb_pool.hip -> csrc/xvec_forward.cpp
+PA_INTERNAL int pa_mfcc_frontend(const float* wav, long wav_len, long chunk_stride, int B, int N, int T, int hop,
+                                 int center, int log_mels, const float* window, const float* fft_tw,
+                                 const float* mel_w, const int* mel_lo, const int* mel_hi, int nmel,
+                                 const float* dct, int n_mfcc, float* mel_buf, unsigned int* chunk_max, float* out,
+                                 int rows, void* stream);
+PA_INTERNAL int pa_stats_pool_rows_any(const float* feat, int B, int T0, int Tp, int C, int ld, const float* masks,
+                                       int S, int Fm, const int* nearest_idx, float* stats, int ld_stats,
+                                       const float* aff_scale, const float* aff_shift, void* stream);
 
 namespace pa {
 

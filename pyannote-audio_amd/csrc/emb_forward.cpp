@@ -1,14 +1,6 @@
 // pa_emb_forward: fbank -> ResNet34 -> weighted stats pooling -> Linear, sequenced on one stream.
 // Replaces WeSpeakerResNet34.forward (wespeaker/__init__.py:324-343, resnet.py:399-430).
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-#include <stdlib.h>
-
-#include "../../include/pyannote_amd.h"
-
-namespace pa {
-void set_error(const char* fmt, ...);
-}
+#include "forward_common.h"
 
 namespace {
 
@@ -18,7 +10,6 @@ struct EmbPlan {
   size_t fbank, act[4], stats, total, act_elems;
   size_t t2_off, gather_off;  // Bottleneck: sub-regions of act[3] (t1 at 0)
 };
-inline size_t align64(size_t n) { return (n + 63) & ~(size_t)63; }
 
 // Winograd F(4x4,3x3) (pa_conv3x3_wino4: units of 4 x 64 output pixels) or F(2x2,3x3) (pa_conv3x3_wino: 8 x 32,
 // 4 x 64 or 2 x 128 per workgroup) for an H x W map, both weight images being available.  Per USEFUL pixel F(4x4) is
@@ -43,14 +34,6 @@ inline bool prefer_wino4(int H, int W, int cin) {
   return p4 * 100 <= p2 * gain;
 }
 
-// OFF by default: measured neutral on MI355X (profiles/r5_row_split_ab.txt: per audio-hour k_conv3x3_wino4 417.0 ->
-// 395.7 ms, k_conv3x3_wino 161.5 -> 184.1 ms; step 793.8 / 802.2 vs 795.7 / 794.8 ms) -- the 2 x 128 tiles of the
-// F(2x2) kernel run the two-row strips at 2.25 ms per launch, exactly what the F(4x4) kernel saves.
-inline bool split_rows_wanted() {   // PA_EMB_SPLIT_ROWS=1 switches it on
-  static const bool on = getenv("PA_EMB_SPLIT_ROWS") != nullptr && atoi(getenv("PA_EMB_SPLIT_ROWS")) != 0;
-  return on;
-}
-
 bool make_plan(const pa_emb_weights* w, int B, int N, int S, EmbPlan* p, bool calib = false) {
   if (N < 400) return false;
   p->B = B;
@@ -65,19 +48,14 @@ bool make_plan(const pa_emb_weights* w, int B, int N, int S, EmbPlan* p, bool ca
     p->Hs[l + 1] = (p->Hs[l] - 1) / s + 1;
     p->Ws[l + 1] = (p->Ws[l] - 1) / s + 1;
   }
-  size_t o = 0;
-  auto take = [&](size_t n) {
-    size_t r = o;
-    o += align64(n);
-    return r;
-  };
-  p->fbank = take((size_t)B * p->T * p->F);
+  pa::Bump ws;
+  p->fbank = ws.take((size_t)B * p->T * p->F);
   // largest activation: the output of layer 1 (Hs[0] x Ws[0] pixels, planes[0] x expansion channels)
   const int ex = w->bottleneck ? 4 : 1;
   p->act_elems = (size_t)B * p->Hs[0] * p->Ws[0] * w->planes[0] * ex;
   // BasicBlock: 3 ping-pong buffers; Bottleneck: block input / output / shortcut at 4 x planes channels
   // (3 buffers) + the two planes-wide intermediates and the stride-2 gather (a 4th buffer, split in 3)
-  for (int i = 0; i < 3; ++i) p->act[i] = take(p->act_elems);
+  for (int i = 0; i < 3; ++i) p->act[i] = ws.take(p->act_elems);
   p->t2_off = p->gather_off = 0;
   if (w->bottleneck) {
     // sub-regions sized from the real block dimensions (odd maps: Ho = ceil(H / 2), so Ho * Wo > H * W / 4)
@@ -92,15 +70,15 @@ bool make_plan(const pa_emb_weights* w, int B, int N, int S, EmbPlan* p, bool ca
       if (l > 0) g = g > out_px * cin ? g : out_px * cin;
       cin = 4 * (int)planes;
     }
-    p->t2_off = align64(t1);
-    p->gather_off = p->t2_off + align64(t2);
-    p->act[3] = take(p->gather_off + align64(g));
+    p->t2_off = pa::Bump::align(t1);
+    p->gather_off = p->t2_off + pa::Bump::align(t2);
+    p->act[3] = ws.take(p->gather_off + pa::Bump::align(g));
   } else if (calib) {
-    p->act[3] = take(p->act_elems);   // where the Winograd result of a convolution waits for its comparison
+    p->act[3] = ws.take(p->act_elems);   // where the Winograd result of a convolution waits for its comparison
   }
   const int L = w->num_layers;
-  p->stats = take((size_t)B * p->S * 2 * w->planes[L - 1] * ex * p->Hs[L]);
-  p->total = o;
+  p->stats = ws.take((size_t)B * p->S * 2 * w->planes[L - 1] * ex * p->Hs[L]);
+  p->total = ws.o;
   return true;
 }
 
@@ -125,8 +103,6 @@ size_t pa_emb_workspace_bytes(const pa_emb_weights* w, int num_chunks, int num_s
 }
 
 }  // extern "C"
-
-extern "C" int pa_absmax_diff(const float* got, const float* ref, long n, float* out2, void* stream);   // emb_pool.hip
 
 // Ragged batches (pa_emb_forward_ragged: `lengths` != NULL): utterance b has lengths[b] samples at wav[offsets[b]],
 // and the maps are padded to the longest utterance (T = the frames of num_samples).  THE ZERO-PADDING RULE: every
@@ -163,12 +139,6 @@ static int emb_forward_impl(const pa_emb_weights* w, const float* wav, int64_t w
   }
   float* ws = (float*)workspace;
   const int B = p.B;
-  int rc;
-#define RUN(call)           \
-  do {                      \
-    rc = (call);            \
-    if (rc != 0) return rc; \
-  } while (0)
 
   // fbank + centring: the mean over the whole chunk (fused behind the fbank kernel), or -- fbank_centering_span, a
   // checkpoint hyper-parameter -- the running mean of fb_center_kernel frames, out of place into the second
@@ -179,11 +149,11 @@ static int emb_forward_impl(const pa_emb_weights* w, const float* wav, int64_t w
     return 3;
   }
   if (ragged)
-    RUN(pa_fbank_ragged(wav, wav_len, offsets, lengths, B, p.N, w->fb_window, w->fb_tw256, w->fb_tw512, w->fb_mel_w,
-                        w->fb_mel_lo, w->fb_mel_hi, w->num_mel, ws + p.fbank, stream));
+    PA_RUN(pa_fbank_ragged(wav, wav_len, offsets, lengths, B, p.N, w->fb_window, w->fb_tw256, w->fb_tw512, w->fb_mel_w,
+                           w->fb_mel_lo, w->fb_mel_hi, w->num_mel, ws + p.fbank, stream));
   else
-    RUN(pa_fbank(wav, wav_len, chunk_stride, B, p.N, w->fb_window, w->fb_tw256, w->fb_tw512, w->fb_mel_w,
-                 w->fb_mel_lo, w->fb_mel_hi, w->num_mel, ws + p.fbank, span == 0 ? 1 : 0, stream));
+    PA_RUN(pa_fbank(wav, wav_len, chunk_stride, B, p.N, w->fb_window, w->fb_tw256, w->fb_tw512, w->fb_mel_w,
+                    w->fb_mel_lo, w->fb_mel_hi, w->num_mel, ws + p.fbank, span == 0 ? 1 : 0, stream));
   // ragged batches: zero the padded columns of an H x W x C map of layer `l` (l = 0: stem / layer 1 resolution)
   auto zero_tail = [&](float* X, int l, int C) -> int {
     return ragged ? pa_zero_tail_cols(X, B, p.Hs[l], p.Ws[l], C, lengths, l > 0 ? l - 1 : 0, stream) : 0;
@@ -193,11 +163,11 @@ static int emb_forward_impl(const pa_emb_weights* w, const float* wav, int64_t w
   float* f2 = ws + p.act[2];
   const float* feats = ws + p.fbank;
   if (span != 0) {
-    RUN(pa_fbank_center_span(ws + p.fbank, B, p.T, p.F, span, f1, stream));
+    PA_RUN(pa_fbank_center_span(ws + p.fbank, B, p.T, p.F, span, f1, stream));
     feats = f1;
   }
-  RUN(pa_resnet_stem(feats, B, p.T, p.F, w->stem_w, w->stem_shift, cur, stream));
-  if (!w->bottleneck) RUN(zero_tail(cur, 0, w->planes[0]));
+  PA_RUN(pa_resnet_stem(feats, B, p.T, p.F, w->stem_w, w->stem_shift, cur, stream));
+  if (!w->bottleneck) PA_RUN(zero_tail(cur, 0, w->planes[0]));
 
   // a stride-1 3x3 convolution (+ shift, residual R, ReLU) of a BasicBlock: F(4x4) where it pays, else F(2x2), else
   // the direct kernel -- as far as the block carries the images (the numerical guard of EmbeddingPack removes them)
@@ -217,13 +187,6 @@ static int emb_forward_impl(const pa_emb_weights* w, const float* wav, int64_t w
         if (r == 0) r = pa_absmax_diff(scratch, Y, n, rep + 2, stream);
       }
       return r;
-    }
-    if (v != nullptr && u != nullptr && H % 4 == 2 && H > 4 && split_rows_wanted() && prefer_wino4(H - 2, W, ci)) {
-      // a map whose height is 2 (mod 4) -- the 10-row maps of layer 4 on 10 s chunks -- would pad its last tile row
-      // half empty (12 rows of F(4x4) work for 10): F(4x4) on the rows above, the last two through the 2 x 128 tiles
-      // of the F(2x2) kernel (per useful pixel 1.29x the F(4x4) cost at 256 channels: 8 + 2.6 instead of 12)
-      const int r = pa_conv3x3_wino4_rows(X, B, H, W, ci, v, shift, R, Y, co, 1, H - 2, stream);
-      return r != 0 ? r : pa_conv3x3_wino_rows(X, B, H, W, ci, u, shift, R, Y, co, 1, H - 2, stream);
     }
     if (v != nullptr && prefer_wino4(H, W, ci)) return pa_conv3x3_wino4(X, B, H, W, ci, v, shift, R, Y, co, 1, stream);
     if (u != nullptr) return pa_conv3x3_wino(X, B, H, W, ci, u, shift, R, Y, co, 1, stream);
@@ -251,29 +214,29 @@ static int emb_forward_impl(const pa_emb_weights* w, const float* wav, int64_t w
         const int Ho = p.Hs[l + 1], Wo = p.Ws[l + 1];
         float* t1 = tmp;
         float* t2 = tmp + p.t2_off;
-        RUN(pa_gemm_tn_ex(cur, cin, w->blk_w1[blk], cin, w->blk_shift1[blk], nullptr, t1, planes, B * H * W,
-                          planes, cin, 2, 0, stream));
-        RUN(zero_tail(t1, stride == 2 ? l : l + 1, planes));
+        PA_RUN(pa_gemm_tn_ex(cur, cin, w->blk_w1[blk], cin, w->blk_shift1[blk], nullptr, t1, planes, B * H * W,
+                             planes, cin, 2, 0, stream));
+        PA_RUN(zero_tail(t1, stride == 2 ? l : l + 1, planes));
         if (stride == 1 && w->blk_u2[blk] != nullptr)
-          RUN(pa_conv3x3_wino(t1, B, H, W, planes, w->blk_u2[blk], w->blk_shift2[blk], nullptr, t2, planes, 1,
-                              stream));
+          PA_RUN(pa_conv3x3_wino(t1, B, H, W, planes, w->blk_u2[blk], w->blk_shift2[blk], nullptr, t2, planes, 1,
+                                 stream));
         else
-          RUN(pa_conv3x3(t1, B, H, W, planes, w->blk_w2[blk], w->blk_shift2[blk], nullptr, t2, planes, stride,
-                         1, stream));
+          PA_RUN(pa_conv3x3(t1, B, H, W, planes, w->blk_w2[blk], w->blk_shift2[blk], nullptr, t2, planes, stride,
+                            1, stream));
         const float* res = cur;      // identity shortcut
         if (w->blk_wsc[blk] != nullptr) {
           if (stride == 2)
-            RUN(pa_gemm_tn_s2(cur, B, H, W, cin, w->blk_wsc[blk], cin, w->blk_shiftsc[blk], sc, cout, cout, stream));
+            PA_RUN(pa_gemm_tn_s2(cur, B, H, W, cin, w->blk_wsc[blk], cin, w->blk_shiftsc[blk], sc, cout, cout, stream));
           else
-            RUN(pa_gemm_tn_ex(cur, cin, w->blk_wsc[blk], cin, w->blk_shiftsc[blk], nullptr, sc, cout,
-                              B * Ho * Wo, cout, cin, 0, 0, stream));
+            PA_RUN(pa_gemm_tn_ex(cur, cin, w->blk_wsc[blk], cin, w->blk_shiftsc[blk], nullptr, sc, cout,
+                                 B * Ho * Wo, cout, cin, 0, 0, stream));
           res = sc;
         } else if (stride != 1 || cin != cout) {
           pa::set_error("pa_emb_forward: block %d needs a shortcut conv but none was given", blk);
           return 3;
         }
-        RUN(pa_gemm_tn_ex(t2, planes, w->blk_w3[blk], planes, w->blk_shift3[blk], res, nxt, cout, B * Ho * Wo,
-                          cout, planes, 2, 0, stream));
+        PA_RUN(pa_gemm_tn_ex(t2, planes, w->blk_w3[blk], planes, w->blk_shift3[blk], res, nxt, cout, B * Ho * Wo,
+                             cout, planes, 2, 0, stream));
         float* t = cur;
         cur = nxt;
         nxt = t;
@@ -293,31 +256,31 @@ static int emb_forward_impl(const pa_emb_weights* w, const float* wav, int64_t w
       const int Ho = p.Hs[l + 1], Wo = p.Ws[l + 1];
       if (w->blk_wsc[blk] != nullptr) {
         // out = relu(bn2(conv2(relu(bn1(conv1_s(x))))) + bn_sc(conv1x1_s(x)))   (resnet.py:140-145)
-        RUN(pa_conv3x3(cur, B, H, W, cin, w->blk_w1[blk], w->blk_shift1[blk], nullptr, f1, cout, stride,
-                       1, stream));
-        RUN(zero_tail(f1, l + 1, cout));
+        PA_RUN(pa_conv3x3(cur, B, H, W, cin, w->blk_w1[blk], w->blk_shift1[blk], nullptr, f1, cout, stride,
+                          1, stream));
+        PA_RUN(zero_tail(f1, l + 1, cout));
         const size_t q = (size_t)B * Ho * Wo * cin;
-        float* R = f2 + ((q + 63) & ~(size_t)63);
+        float* R = f2 + pa::Bump::align(q);
         // (the 1x1 stride-2 shortcut reads its pixels in place: no gathered copy)
         if (stride == 2)
-          RUN(pa_gemm_tn_s2(cur, B, H, W, cin, w->blk_wsc[blk], cin, w->blk_shiftsc[blk], R, cout, cout, stream));
+          PA_RUN(pa_gemm_tn_s2(cur, B, H, W, cin, w->blk_wsc[blk], cin, w->blk_shiftsc[blk], R, cout, cout, stream));
         else
-          RUN(pa_gemm_tn(cur, cin, w->blk_wsc[blk], cin, w->blk_shiftsc[blk], R, cout, B * Ho * Wo, cout, cin, 0, 0,
-                         stream));
-        RUN(conv_s1(f1, Ho, Wo, cout, w->blk_v2[blk], w->blk_u2[blk], w->blk_w2[blk], w->blk_shift2[blk], R, cur, cout,
-                    2 * blk + 1));
-        RUN(zero_tail(cur, l + 1, cout));
+          PA_RUN(pa_gemm_tn(cur, cin, w->blk_wsc[blk], cin, w->blk_shiftsc[blk], R, cout, B * Ho * Wo, cout, cin, 0, 0,
+                            stream));
+        PA_RUN(conv_s1(f1, Ho, Wo, cout, w->blk_v2[blk], w->blk_u2[blk], w->blk_w2[blk], w->blk_shift2[blk], R, cur,
+                       cout, 2 * blk + 1));
+        PA_RUN(zero_tail(cur, l + 1, cout));
       } else {
         if (stride != 1 || cin != cout) {
           pa::set_error("pa_emb_forward: block %d needs a shortcut conv but none was given", blk);
           return 3;
         }
-        RUN(conv_s1(cur, H, W, cin, w->blk_v1[blk], w->blk_u1[blk], w->blk_w1[blk], w->blk_shift1[blk], nullptr, f1,
-                    cout, 2 * blk));
-        RUN(zero_tail(f1, l + 1, cout));
-        RUN(conv_s1(f1, H, W, cout, w->blk_v2[blk], w->blk_u2[blk], w->blk_w2[blk], w->blk_shift2[blk], cur, f2, cout,
-                    2 * blk + 1));
-        RUN(zero_tail(f2, l + 1, cout));
+        PA_RUN(conv_s1(cur, H, W, cin, w->blk_v1[blk], w->blk_u1[blk], w->blk_w1[blk], w->blk_shift1[blk], nullptr, f1,
+                       cout, 2 * blk));
+        PA_RUN(zero_tail(f1, l + 1, cout));
+        PA_RUN(conv_s1(f1, H, W, cout, w->blk_v2[blk], w->blk_u2[blk], w->blk_w2[blk], w->blk_shift2[blk], cur, f2,
+                       cout, 2 * blk + 1));
+        PA_RUN(zero_tail(f2, l + 1, cout));
         float* t = cur;
         cur = f2;
         f2 = t;
@@ -329,13 +292,12 @@ static int emb_forward_impl(const pa_emb_weights* w, const float* wav, int64_t w
   const int S = p.S;
   const int cfin = w->planes[L - 1] * (w->bottleneck ? 4 : 1);
   if (ragged)
-    RUN(pa_stats_pool_ragged(cur, B, p.Hs[L], p.Ws[L], cfin, lengths, L - 1, masks, p.Ws[L], ws + p.stats, stream));
+    PA_RUN(pa_stats_pool_ragged(cur, B, p.Hs[L], p.Ws[L], cfin, lengths, L - 1, masks, p.Ws[L], ws + p.stats, stream));
   else
-    RUN(pa_stats_pool(cur, B, p.Hs[L], p.Ws[L], cfin, masks, S, mask_frames, nearest_idx, ws + p.stats, stream));
+    PA_RUN(pa_stats_pool(cur, B, p.Hs[L], p.Ws[L], cfin, masks, S, mask_frames, nearest_idx, ws + p.stats, stream));
   const int D2 = 2 * cfin * p.Hs[L];
-  RUN(pa_gemm_tn(ws + p.stats, D2, w->seg1_w, D2, w->seg1_b, emb, w->embed_dim, B * S, w->embed_dim, D2,
-                 0, 0, stream));
-#undef RUN
+  PA_RUN(pa_gemm_tn(ws + p.stats, D2, w->seg1_w, D2, w->seg1_b, emb, w->embed_dim, B * S, w->embed_dim, D2,
+                    0, 0, stream));
   return 0;
 }
 

@@ -1,6 +1,6 @@
 // pa_xvec_forward: XVectorSincNet (models/embedding/xvector.py:205-349) sequenced on one stream:
-//   SincNet front end (the segmentation model's kernels: row stats, sinc FIR + pool, conv5 + pool x2,
-//   last InstanceNorm + leaky_relu written as rows [(tile, t, b16)][64])
+//   SincNet front end (forward_common.h: row stats, sinc FIR + pool, conv5 + pool x2, last InstanceNorm +
+//   leaky_relu written as rows [(tile, t, b16)][64])
 //   -> 5 TDNN layers = Conv1d(k, dilation d) + LeakyReLU + BatchNorm1d (xvector.py:232-247).  In the
 //      (tile, t, b16) row order one time step is 16 rows, so tap j of a dilated convolution is the SAME
 //      activation matrix shifted by 16 j d rows: a layer is k chained GEMMs C += A(shift j) W_j^T on
@@ -12,80 +12,11 @@
 //   -> Linear(3000 -> dimension).
 // pa_xvec_mfcc_forward: XVectorMFCC (xvector.py:42-202), the same layers after the torchaudio MFCC front end of
 // csrc/mfcc.hip, which writes its coefficients straight into the rows [(tile, t, b16)][64] (xvec_tail below).
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-
-#include "../../include/pyannote_amd.h"
-
-#define PA_INTERNAL __attribute__((visibility("hidden")))
-// csrc/mfcc.hip, csrc/emb_pool.hip
-PA_INTERNAL int pa_mfcc_frontend(const float* wav, long wav_len, long chunk_stride, int B, int N, int T, int hop,
-                                 int center, int log_mels, const float* window, const float* fft_tw,
-                                 const float* mel_w, const int* mel_lo, const int* mel_hi, int nmel,
-                                 const float* dct, int n_mfcc, float* mel_buf, unsigned int* chunk_max, float* out,
-                                 int rows, void* stream);
-PA_INTERNAL int pa_stats_pool_rows_any(const float* feat, int B, int T0, int Tp, int C, int ld, const float* masks,
-                                       int S, int Fm, const int* nearest_idx, float* stats, int ld_stats,
-                                       const float* aff_scale, const float* aff_shift, void* stream);
-
-namespace pa {
-void set_error(const char* fmt, ...);
-}
+#include "forward_common.h"
 
 namespace {
 
-struct XvecPlan {
-  int B, N, L1, P1, P2, T, ntiles, Tp, S, ldstats;
-  long M;
-  size_t wav_mean, wav_rstd, s1, st1m, st1r, s2, st2m, st2r, s3, st3m, st3r, x0, a0, a1, stats, total;
-};
-inline size_t align64(size_t n) { return (n + 63) & ~(size_t)63; }
 constexpr int SLACK_ROWS = 128;   // >= 16 * (k - 1) * d of every layer (96)
-
-bool make_plan(const pa_xvec_weights* w, int B, int N, int S, XvecPlan* p) {
-  p->B = B;
-  p->N = N;
-  p->S = S < 1 ? 1 : S;
-  p->L1 = (N - 251) / w->sinc_stride + 1;
-  if (N < 251 || p->L1 < 3) return false;
-  p->P1 = p->L1 / 3;
-  if (p->P1 < 5) return false;
-  p->P2 = (p->P1 - 4) / 3;
-  if (p->P2 < 5) return false;
-  p->T = (p->P2 - 4) / 3;
-  p->Tp = p->T;
-  for (int l = 0; l < PA_XVEC_TDNN; ++l) p->Tp -= (w->tdnn_kernel[l] - 1) * w->tdnn_dilation[l];
-  if (p->Tp < 1) return false;
-  p->ntiles = (B + 15) / 16;
-  p->M = (long)p->ntiles * p->T * 16;
-  int cmax = 64;
-  for (int l = 0; l < PA_XVEC_TDNN; ++l) cmax = w->tdnn_channels[l] > cmax ? w->tdnn_channels[l] : cmax;
-  p->ldstats = (2 * w->tdnn_channels[PA_XVEC_TDNN - 1] + 31) & ~31;
-  size_t o = 0;
-  auto take = [&](size_t n) {
-    size_t r = o;
-    o += align64(n);
-    return r;
-  };
-  p->wav_mean = take(B);
-  p->wav_rstd = take(B);
-  p->s1 = take((size_t)B * 80 * p->P1);
-  p->st1m = take((size_t)B * 80);
-  p->st1r = take((size_t)B * 80);
-  p->s2 = take((size_t)B * 60 * p->P2);
-  p->st2m = take((size_t)B * 60);
-  p->st2r = take((size_t)B * 60);
-  p->s3 = take((size_t)B * 60 * p->T);
-  p->st3m = take((size_t)B * 60);
-  p->st3r = take((size_t)B * 60);
-  p->x0 = take((size_t)(p->M + SLACK_ROWS) * 64);
-  p->a0 = take((size_t)(p->M + SLACK_ROWS) * cmax);
-  p->a1 = take((size_t)(p->M + SLACK_ROWS) * cmax);
-  p->stats = take((size_t)B * p->S * p->ldstats);
-  p->total = o;
-  return true;
-}
-
 
 // the layers after the front end, shared by XVectorSincNet and XVectorMFCC (the fields of pa_xvec_weights and
 // pa_xvec_mfcc_weights that carry the same names)
@@ -104,50 +35,81 @@ TdnnTail tail_of(const W* w) {
           w->bn_scale,  w->bn_shift,      w->emb_w,       w->emb_b};
 }
 
+// T input frames -> Tp valid frames after the stack; the input rows, the two ping-pong activations (each with
+// SLACK_ROWS rows past the last tile) and the pooled statistics of S masks per chunk
+struct TdnnPlan {
+  int T, Tp, S, ldstats;
+  long M;
+  size_t x0, a0, a1, stats;
+};
+void tdnn_plan(const TdnnTail& w, int B, int T, int S, pa::Bump* ws, TdnnPlan* p) {
+  p->T = p->Tp = T;
+  p->S = S < 1 ? 1 : S;
+  for (int l = 0; l < PA_XVEC_TDNN; ++l) p->Tp -= (w.kernel[l] - 1) * w.dilation[l];
+  p->M = pa::tile_rows(B, T);
+  int cmax = 64;
+  for (int l = 0; l < PA_XVEC_TDNN; ++l) cmax = w.channels[l] > cmax ? w.channels[l] : cmax;
+  p->ldstats = (2 * w.channels[PA_XVEC_TDNN - 1] + 31) & ~31;
+  p->x0 = ws->take((size_t)(p->M + SLACK_ROWS) * 64);
+  p->a0 = ws->take((size_t)(p->M + SLACK_ROWS) * cmax);
+  p->a1 = ws->take((size_t)(p->M + SLACK_ROWS) * cmax);
+  p->stats = ws->take((size_t)B * p->S * p->ldstats);
+}
+
 // x0 [(tile, t, b16)][64] (+ SLACK_ROWS zero rows) -> TDNN stack (a0 / a1) -> pooling (stats) -> Linear -> emb
-int xvec_tail(const TdnnTail& w, const float* x0, float* a0, float* a1, float* stats, int B, int T, int Tp, long M,
-              int ldstats, const float* masks, int num_masks, int mask_frames, const int32_t* nearest_idx, float* emb,
-              void* stream) {
+int xvec_tail(const TdnnTail& w, const TdnnPlan& p, float* ws, int B, const float* masks, int num_masks,
+              int mask_frames, const int32_t* nearest_idx, float* emb, void* stream) {
   hipStream_t st = (hipStream_t)stream;
-  int rc;
-#define RUN(call)           \
-  do {                      \
-    rc = (call);            \
-    if (rc != 0) return rc; \
-  } while (0)
   // TDNN stack
-  const float* in = x0;
+  const float* in = ws + p.x0;
   int cin = 64;
-  float* buf[2] = {a0, a1};
+  float* buf[2] = {ws + p.a0, ws + p.a1};
   for (int l = 0; l < PA_XVEC_TDNN; ++l) {
     const int cout = w.channels[l], k = w.kernel[l], d = w.dilation[l];
     float* out = buf[l & 1];
-    if (hipMemsetAsync(out + (size_t)M * cout, 0, sizeof(float) * SLACK_ROWS * cout, st) != hipSuccess) return 1;
+    if (hipMemsetAsync(out + (size_t)p.M * cout, 0, sizeof(float) * SLACK_ROWS * cout, st) != hipSuccess) return 1;
     for (int j = 0; j < k; ++j) {
       // tap j: rows shifted by j * d time steps = 16 j d rows; W_j = tdnn_w[l] + j * cout * cin
-      RUN(pa_gemm_tn_ex(in + (size_t)16 * j * d * cin, cin, w.w[l] + (size_t)j * cout * cin, cin,
-                        j == 0 ? w.b[l] : nullptr, j == 0 ? nullptr : out, out, cout, (int)M, cout, cin,
-                        j == k - 1 ? 1 : 0, 0, stream));
+      PA_RUN(pa_gemm_tn_ex(in + (size_t)16 * j * d * cin, cin, w.w[l] + (size_t)j * cout * cin, cin,
+                           j == 0 ? w.b[l] : nullptr, j == 0 ? nullptr : out, out, cout, (int)p.M, cout, cin,
+                           j == k - 1 ? 1 : 0, 0, stream));
     }
     in = out;
     cin = cout;
   }
   // statistics pooling over the Tp valid frames, for every mask of a chunk at once
   const int S = masks ? num_masks : 1;
-  RUN(pa_stats_pool_rows_any(in, B, T, Tp, cin, cin, masks, S, mask_frames, nearest_idx, stats, ldstats, w.bn_scale,
-                             w.bn_shift, stream));
+  PA_RUN(pa_stats_pool_rows_any(in, B, p.T, p.Tp, cin, cin, masks, S, mask_frames, nearest_idx, ws + p.stats,
+                                p.ldstats, w.bn_scale, w.bn_shift, stream));
   // embedding Linear(2 C -> dimension) (xvector.py:250, 348); K padded to a multiple of 32 with zeros
-  RUN(pa_gemm_tn_ex(stats, ldstats, w.emb_w, ldstats, w.emb_b, nullptr, emb, w.dimension, B * S, w.dimension, ldstats,
-                    0, 0, stream));
-#undef RUN
-  return 0;
+  return pa_gemm_tn_ex(ws + p.stats, p.ldstats, w.emb_w, p.ldstats, w.emb_b, nullptr, emb, w.dimension, B * S,
+                       w.dimension, p.ldstats, 0, 0, stream);
+}
+
+// the zero rows past the last tile of x0 that the taps of the last frames read
+int zero_x0_slack(const TdnnPlan& p, float* ws, void* stream) {
+  return hipMemsetAsync(ws + p.x0 + (size_t)p.M * 64, 0, sizeof(float) * SLACK_ROWS * 64, (hipStream_t)stream) !=
+                 hipSuccess ? 1 : 0;
+}
+
+struct XvecPlan {
+  pa::SincNetPlan sinc;
+  TdnnPlan tdnn;
+  size_t total;
+};
+
+bool make_plan(const pa_xvec_weights* w, int B, int N, int S, XvecPlan* p) {
+  pa::Bump ws;
+  if (!pa::sincnet_plan(w->sinc_stride, B, N, &ws, &p->sinc)) return false;
+  tdnn_plan(tail_of(w), B, p->sinc.T, S, &ws, &p->tdnn);
+  p->total = ws.o;
+  return p->tdnn.Tp >= 1;
 }
 
 // XVectorMFCC: MFCC frames (xvector.py:111-118), then the TDNN stack
 struct MfccPlan {
-  int B, N, T, Tp, ntiles, S, ldstats;
-  long M;
-  size_t mel, cmax, x0, a0, a1, stats, frontend, total;
+  size_t mel, cmax, frontend, total;
+  TdnnPlan tdnn;
 };
 
 int mfcc_frames(const pa_xvec_mfcc_weights* w, int N) {
@@ -156,34 +118,24 @@ int mfcc_frames(const pa_xvec_mfcc_weights* w, int N) {
   return N >= w->n_fft ? 1 + (N - w->n_fft) / w->hop_length : 0;
 }
 
+// true with at least one MFCC frame (pa_mfcc_features); the embedding also needs tdnn.Tp >= 1
 bool make_mfcc_plan(const pa_xvec_mfcc_weights* w, int B, int N, int S, MfccPlan* p) {
-  p->B = B;
-  p->N = N;
-  p->S = S < 1 ? 1 : S;
-  p->T = mfcc_frames(w, N);
-  if (p->T < 1) return false;
-  p->Tp = p->T;
-  for (int l = 0; l < PA_XVEC_TDNN; ++l) p->Tp -= (w->tdnn_kernel[l] - 1) * w->tdnn_dilation[l];
-  p->ntiles = (B + 15) / 16;
-  p->M = (long)p->ntiles * p->T * 16;
-  int cmax = 64;
-  for (int l = 0; l < PA_XVEC_TDNN; ++l) cmax = w->tdnn_channels[l] > cmax ? w->tdnn_channels[l] : cmax;
-  p->ldstats = (2 * w->tdnn_channels[PA_XVEC_TDNN - 1] + 31) & ~31;
-  size_t o = 0;
-  auto take = [&](size_t n) {
-    size_t r = o;
-    o += align64(n);
-    return r;
-  };
-  p->mel = take((size_t)B * p->T * w->n_mels);
-  p->cmax = take((size_t)B);
-  p->frontend = o;
-  p->x0 = take((size_t)(p->M + SLACK_ROWS) * 64);
-  p->a0 = take((size_t)(p->M + SLACK_ROWS) * cmax);
-  p->a1 = take((size_t)(p->M + SLACK_ROWS) * cmax);
-  p->stats = take((size_t)B * p->S * p->ldstats);
-  p->total = o;
+  const int T = mfcc_frames(w, N);
+  if (T < 1) return false;
+  pa::Bump ws;
+  p->mel = ws.take((size_t)B * T * w->n_mels);
+  p->cmax = ws.take((size_t)B);
+  p->frontend = ws.o;
+  tdnn_plan(tail_of(w), B, T, S, &ws, &p->tdnn);
+  p->total = ws.o;
   return true;
+}
+
+int mfcc_frontend(const pa_xvec_mfcc_weights* w, const MfccPlan& p, const float* wav, int64_t wav_len,
+                  int64_t chunk_stride, int B, int N, float* ws, float* out, int rows, void* stream) {
+  return pa_mfcc_frontend(wav, wav_len, chunk_stride, B, N, p.tdnn.T, w->hop_length, w->center, w->log_mels, w->window,
+                          w->fft_tw, w->mel_w, w->mel_lo, w->mel_hi, w->n_mels, w->dct, w->n_mfcc, ws + p.mel,
+                          (unsigned int*)(ws + p.cmax), out, rows, stream);
 }
 
 }  // namespace
@@ -192,7 +144,7 @@ extern "C" {
 
 int pa_xvec_num_frames(const pa_xvec_weights* w, int num_samples) {
   XvecPlan p;
-  return make_plan(w, 1, num_samples, 1, &p) ? p.Tp : 0;
+  return make_plan(w, 1, num_samples, 1, &p) ? p.tdnn.Tp : 0;
 }
 
 size_t pa_xvec_workspace_bytes(const pa_xvec_weights* w, int num_chunks, int num_samples, int num_masks) {
@@ -217,42 +169,21 @@ int pa_xvec_forward(const pa_xvec_weights* w, const float* wav, int64_t wav_len,
     return 3;
   }
   float* ws = (float*)workspace;
-  const int B = p.B;
-  hipStream_t st = (hipStream_t)stream;
-  int rc;
-#define RUN(call)           \
-  do {                      \
-    rc = (call);            \
-    if (rc != 0) return rc; \
-  } while (0)
-
-  // SincNet (models/blocks/sincnet.py:163-184), as in pa_seg_forward
-  RUN(pa_row_stats(wav, chunk_stride, wav_len, B, p.N, 1e-5f, ws + p.wav_mean, ws + p.wav_rstd, stream));
-  RUN(pa_sinc_fir_pool(wav, wav_len, chunk_stride, B, p.N, w->sinc_stride, ws + p.wav_mean, ws + p.wav_rstd,
-                       w->wav_gamma, w->wav_beta, w->sinc_filt, ws + p.s1, stream));
-  RUN(pa_row_stats(ws + p.s1, p.P1, (long)B * 80 * p.P1, B * 80, p.P1, 1e-5f, ws + p.st1m, ws + p.st1r, stream));
-  RUN(pa_conv5_pool(ws + p.s1, B, 80, p.P1, ws + p.st1m, ws + p.st1r, w->norm0, w->norm0 + 80, w->conv1_w,
-                    w->conv1_b, ws + p.s2, stream));
-  RUN(pa_row_stats(ws + p.s2, p.P2, (long)B * 60 * p.P2, B * 60, p.P2, 1e-5f, ws + p.st2m, ws + p.st2r, stream));
-  RUN(pa_conv5_pool(ws + p.s2, B, 60, p.P2, ws + p.st2m, ws + p.st2r, w->norm1, w->norm1 + 60, w->conv2_w,
-                    w->conv2_b, ws + p.s3, stream));
-  RUN(pa_row_stats(ws + p.s3, p.T, (long)B * 60 * p.T, B * 60, p.T, 1e-5f, ws + p.st3m, ws + p.st3r, stream));
-  if (hipMemsetAsync(ws + p.x0 + (size_t)p.M * 64, 0, sizeof(float) * SLACK_ROWS * 64, st) != hipSuccess) return 1;
-  RUN(pa_norm_transpose(ws + p.s3, B, p.T, ws + p.st3m, ws + p.st3r, w->norm2, w->norm2 + 60, ws + p.x0, stream));
-
-  return xvec_tail(tail_of(w), ws + p.x0, ws + p.a0, ws + p.a1, ws + p.stats, B, p.T, p.Tp, p.M, p.ldstats,
-                   masks, num_masks, mask_frames, nearest_idx, emb, stream);
-#undef RUN
+  // the slack rows first: no launch of the front end writes them
+  PA_RUN(zero_x0_slack(p.tdnn, ws, stream));
+  PA_RUN(pa::sincnet_run(pa::sincnet_of(w), p.sinc, wav, wav_len, chunk_stride, num_chunks, num_samples, ws,
+                         ws + p.tdnn.x0, stream));
+  return xvec_tail(tail_of(w), p.tdnn, ws, num_chunks, masks, num_masks, mask_frames, nearest_idx, emb, stream);
 }
 
 int pa_xvec_mfcc_num_frames(const pa_xvec_mfcc_weights* w, int num_samples) {
   MfccPlan p;
-  return make_mfcc_plan(w, 1, num_samples, 1, &p) && p.Tp > 0 ? p.Tp : 0;
+  return make_mfcc_plan(w, 1, num_samples, 1, &p) && p.tdnn.Tp > 0 ? p.tdnn.Tp : 0;
 }
 
 size_t pa_xvec_mfcc_workspace_bytes(const pa_xvec_mfcc_weights* w, int num_chunks, int num_samples, int num_masks) {
   MfccPlan p;
-  if (!make_mfcc_plan(w, num_chunks, num_samples, num_masks, &p) || p.Tp < 1) return 0;
+  if (!make_mfcc_plan(w, num_chunks, num_samples, num_masks, &p) || p.tdnn.Tp < 1) return 0;
   return p.total * sizeof(float);
 }
 
@@ -262,7 +193,7 @@ int pa_xvec_mfcc_forward(const pa_xvec_mfcc_weights* w, const float* wav, int64_
                          void* stream) {
   if (num_chunks <= 0) return 0;
   MfccPlan p;
-  if (!make_mfcc_plan(w, num_chunks, num_samples, masks ? num_masks : 1, &p) || p.Tp < 1) {
+  if (!make_mfcc_plan(w, num_chunks, num_samples, masks ? num_masks : 1, &p) || p.tdnn.Tp < 1) {
     pa::set_error("pa_xvec_mfcc_forward: %d samples leave no frame after the MFCC front end + the TDNN stack",
                   num_samples);
     return 3;
@@ -273,15 +204,9 @@ int pa_xvec_mfcc_forward(const pa_xvec_mfcc_weights* w, const float* wav, int64_
     return 3;
   }
   float* ws = (float*)workspace;
-  int rc = pa_mfcc_frontend(wav, wav_len, chunk_stride, p.B, p.N, p.T, w->hop_length, w->center, w->log_mels,
-                            w->window, w->fft_tw, w->mel_w, w->mel_lo, w->mel_hi, w->n_mels, w->dct, w->n_mfcc,
-                            ws + p.mel, (unsigned int*)(ws + p.cmax), ws + p.x0, 1, stream);
-  if (rc != 0) return rc;
-  if (hipMemsetAsync(ws + p.x0 + (size_t)p.M * 64, 0, sizeof(float) * SLACK_ROWS * 64, (hipStream_t)stream) !=
-      hipSuccess)
-    return 1;
-  return xvec_tail(tail_of(w), ws + p.x0, ws + p.a0, ws + p.a1, ws + p.stats, p.B, p.T, p.Tp, p.M, p.ldstats, masks,
-                   num_masks, mask_frames, nearest_idx, emb, stream);
+  PA_RUN(mfcc_frontend(w, p, wav, wav_len, chunk_stride, num_chunks, num_samples, ws, ws + p.tdnn.x0, 1, stream));
+  PA_RUN(zero_x0_slack(p.tdnn, ws, stream));
+  return xvec_tail(tail_of(w), p.tdnn, ws, num_chunks, masks, num_masks, mask_frames, nearest_idx, emb, stream);
 }
 
 int pa_mfcc_features(const pa_xvec_mfcc_weights* w, const float* wav, int64_t wav_len, int64_t chunk_stride,
@@ -298,10 +223,7 @@ int pa_mfcc_features(const pa_xvec_mfcc_weights* w, const float* wav, int64_t wa
                   p.frontend * sizeof(float));
     return 3;
   }
-  float* ws = (float*)workspace;
-  return pa_mfcc_frontend(wav, wav_len, chunk_stride, p.B, p.N, p.T, w->hop_length, w->center, w->log_mels, w->window,
-                          w->fft_tw, w->mel_w, w->mel_lo, w->mel_hi, w->n_mels, w->dct, w->n_mfcc, ws + p.mel,
-                          (unsigned int*)(ws + p.cmax), out, 0, stream);
+  return mfcc_frontend(w, p, wav, wav_len, chunk_stride, num_chunks, num_samples, (float*)workspace, out, 0, stream);
 }
 
 }  // extern "C"

@@ -334,8 +334,8 @@ def test_conv3x3_winograd_f4_unit_shapes(gpu_device, linear):
 
 
 def test_conv3x3_row_split_between_f4_and_f2(gpu_device):
-    """a map whose height is 2 (mod 4) -- layer 4 on 10 s chunks: 10 x 125 x 256 -- is split by pa_emb_forward: rows
-    0 .. H - 3 through pa_conv3x3_wino4_rows, the last two through pa_conv3x3_wino_rows; together they are the whole
+    """a map whose height is 2 (mod 4) -- layer 4 on 10 s chunks: 10 x 125 x 256 -- can be split between the row-range
+    launchers: rows 0 .. H - 3 through pa_conv3x3_wino4_rows, the last two through pa_conv3x3_wino_rows; together they are the whole
     convolution (every output pixel written exactly once: Y starts as NaN), with and without the residual, for
     heights 10, 6 and 18 and a ragged width."""
     import pyannote_audio_amd.ffi as ffi
@@ -534,3 +534,43 @@ def test_bottleneck_resnet_matches_oracle(gpu_device, num_blocks):
     assert out.shape == ref.shape == (B, 2, 256)
     assert north_star_ratio(f"bottleneck{num_blocks}_emb", out, ref) <= 1.0
     assert north_star_ratio(f"bottleneck{num_blocks}_emb_unweighted", out1, ref1) <= 1.0
+
+
+@pytest.mark.parametrize("case", ["one_sample_short", "workspace_one_byte_short", "num_layers_3",
+                                  "ragged_fbank_span_checkpoint"])
+def test_emb_forward_refusals(emb, gpu_device, case):
+    """what pa_emb_forward / pa_emb_forward_ragged refuse, they refuse with code 3, the same words as ever and no write
+    (tests/refusals.py)"""
+    import pyannote_audio_amd.ffi as ffi
+    from refusals import altered, check_refusal
+    lib = ffi.load()
+    _, pack, _ = emb
+    B, N, S = 2, 16000, 1
+    w, n = pack.struct, N
+    wav = _wave(B, N, seed=6).view(-1).to(gpu_device)
+    need = lib.pa_emb_workspace_bytes(w, B, N, S)
+    ws = torch.empty(need, dtype=torch.uint8, device=gpu_device)
+    outputs = [((B, S, w.embed_dim), torch.float32)]
+    if case == "ragged_fbank_span_checkpoint":
+        w = altered(w, fb_center_kernel=39)
+        offsets = torch.tensor([0, N], dtype=torch.int64, device=gpu_device)
+        lengths = torch.tensor([N, N - 1000], dtype=torch.int32, device=gpu_device)
+        assert lib.pa_emb_ragged_workspace_bytes(w, B, N) <= need
+        check_refusal(lambda out: lib.pa_emb_forward_ragged(w, ffi.ptr(wav), wav.numel(), ffi.ptr(offsets),
+                                                            ffi.ptr(lengths), B, N, None, out, ffi.ptr(ws), need,
+                                                            ffi.stream()),
+                      outputs, "pa_emb_forward_ragged: fbank_centering_span checkpoints run one launch sequence per "
+                      "length", gpu_device)
+        return
+    if case == "one_sample_short":
+        n = 399
+        assert lib.pa_emb_num_pool_frames(w, 400) == 1 and lib.pa_emb_num_pool_frames(w, n) == 0
+        message = f"pa_emb_forward: {n} samples is too short (fbank needs >= 400) or bad layer count"
+    elif case == "workspace_one_byte_short":
+        need -= 1
+        message = f"pa_emb_forward: workspace too small ({need} < {need + 1} bytes)"
+    else:
+        w = altered(w, num_layers=3)
+        message = f"pa_emb_forward: {N} samples is too short (fbank needs >= 400) or bad layer count"
+    check_refusal(lambda out: lib.pa_emb_forward(w, ffi.ptr(wav), wav.numel(), N, B, n, None, S, 0, None, out,
+                                                 ffi.ptr(ws), need, ffi.stream()), outputs, message, gpu_device)

@@ -352,3 +352,36 @@ def test_other_sincnet_strides_match_oracle(gpu_device, stride):
     torch.cuda.synchronize()
     assert logp.shape == ref.shape == (B, model.num_frames(N), 7)
     assert north_star_ratio(f"seg_sinc_stride_{stride}", logp, ref) <= 1.0
+
+
+@pytest.mark.parametrize("case", ["one_sample_short", "workspace_one_byte_short", "lstm_hidden_40",
+                                  "unidirectional_48", "linear_hidden_48"])
+def test_seg_forward_refusals(seg, gpu_device, case):
+    """what pa_seg_forward refuses, it refuses with code 3, the same words as ever and no write (tests/refusals.py)"""
+    import pyannote_audio_amd.ffi as ffi
+    from refusals import altered, check_refusal, smallest_accepted
+    lib = ffi.load()
+    _, pack, eng = seg
+    B, N = 2, 16000
+    w, n = pack.struct, N
+    wav = _wave(B, N, seed=5).view(-1).to(gpu_device)
+    need = lib.pa_seg_workspace_bytes(w, B, N)
+    ws = torch.empty(need, dtype=torch.uint8, device=gpu_device)
+    limits = ("pa_seg_forward: LSTM hidden size must be a multiple of 16 (32 when unidirectional) up to 512, "
+              "Linear widths multiples of 32 (got %d, %d)")
+    if case == "one_sample_short":
+        n = smallest_accepted(lambda n: lib.pa_seg_num_frames(n, 10)) - 1
+        message = f"pa_seg_forward: chunk of {n} samples is too short for SincNet"
+    elif case == "workspace_one_byte_short":
+        need -= 1
+        message = f"pa_seg_forward: workspace too small ({need} < {need + 1} bytes)"
+    elif case == "lstm_hidden_40":
+        w, message = altered(w, lstm_hidden=40), limits % (40, w.linear_hidden)
+    elif case == "unidirectional_48":
+        w, message = altered(w, lstm_hidden=48, lstm_bidir=0), limits % (48, w.linear_hidden)
+    else:
+        w, message = altered(w, linear_hidden=48), limits % (w.lstm_hidden, 48)
+    F = eng.frames_of(N)
+    check_refusal(lambda logp, ml: lib.pa_seg_forward(w, ffi.ptr(wav), wav.numel(), N, B, n, logp, ml, ffi.ptr(ws), need,
+                                                      ffi.stream()),
+                  [((B, F, 7), torch.float32), ((B, F, 3), torch.uint8)], message, gpu_device)

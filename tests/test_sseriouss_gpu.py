@@ -128,3 +128,40 @@ def test_sseriouss_model_and_inference(gpu_device, tmp_path):
     top2 = ref.topk(2, dim=-1).values
     safe = ((top2[..., 0] - top2[..., 1]) > 1e-4).numpy()
     assert np.array_equal(swf.data[safe], want[safe])
+
+
+@pytest.mark.parametrize("case", ["one_sample_short", "workspace_one_byte_short", "lstm_hidden_40",
+                                  "unidirectional_48", "linear_hidden_48"])
+def test_sser_forward_refusals(gpu_device, case):
+    """what pa_sser_forward refuses, it refuses with code 3, the same words as ever and no write (tests/refusals.py)"""
+    import pyannote_audio_amd.ffi as ffi
+    from oracle import seeded_sseriouss
+    from oracle.models import TINY_WAV2VEC2
+    from refusals import altered, check_refusal, smallest_accepted
+    lib = ffi.load()
+    model = seeded_sseriouss(wav2vec=dict(TINY_WAV2VEC2), num_layers=2)
+    eng = _engine(model, {"wav2vec": dict(TINY_WAV2VEC2), "wav2vec_layer": -1, "lstm": {"num_layers": 2}}, gpu_device)
+    B, N = 2, 16000
+    w, n = eng.pack.struct, N
+    g = torch.Generator().manual_seed(8)
+    wav = (0.1 * torch.randn(B * N, generator=g)).clamp(-1, 1).to(gpu_device)
+    need = lib.pa_sser_workspace_bytes(w, B, N)
+    ws = torch.empty(need, dtype=torch.uint8, device=gpu_device)
+    limits = ("pa_sser_forward: LSTM hidden size must be a multiple of 16 (32 when unidirectional) up to 512, "
+              "Linear widths multiples of 32 (got %d, %d)")
+    if case == "one_sample_short":
+        n = smallest_accepted(lambda n: lib.pa_sser_num_frames(w, n)) - 1
+        message = f"pa_sser_forward: bad configuration or a chunk of {n} samples is too short"
+    elif case == "workspace_one_byte_short":
+        need -= 1
+        message = f"pa_sser_forward: workspace too small ({need} < {need + 1} bytes)"
+    elif case == "lstm_hidden_40":
+        w, message = altered(w, lstm_hidden=40), limits % (40, w.linear_hidden)
+    elif case == "unidirectional_48":
+        w, message = altered(w, lstm_hidden=48, lstm_bidir=0), limits % (48, w.linear_hidden)
+    else:
+        w, message = altered(w, linear_hidden=48), limits % (w.lstm_hidden, 48)
+    F = eng.frames_of(N)
+    check_refusal(lambda logp, ml: lib.pa_sser_forward(w, ffi.ptr(wav), wav.numel(), N, B, n, None, logp, ml,
+                                                       ffi.ptr(ws), need, ffi.stream()),
+                  [((B, F, 7), torch.float32), ((B, F, 3), torch.uint8)], message, gpu_device)

@@ -229,3 +229,27 @@ def test_pipeline_with_xvector_mfcc_embeddings(synthetic_models, gpu_device, tmp
     assert north_star_ratio("xvector_mfcc_pipeline_embeddings", seen["embeddings"], want.embeddings) <= 1.0
     got = [(s.start, s.end, l) for s, _, l in out.speaker_diarization.itertracks(yield_label=True)]
     assert got == want.diarization
+
+
+@pytest.mark.parametrize("case", ["one_sample_short", "workspace_one_byte_short"])
+def test_pa_xvec_mfcc_forward_refusals(gpu_device, case):
+    """what pa_xvec_mfcc_forward refuses, it refuses with code 3, the same words as ever and no write (tests/refusals.py)"""
+    import pyannote_audio_amd.ffi as ffi
+    from refusals import check_refusal, smallest_accepted
+    lib = ffi.load()
+    eng = _model(gpu_device)[1].engine
+    B, N, S = 2, 16000, 1
+    w, n = eng.pack.struct, N
+    g = torch.Generator().manual_seed(9)
+    wav = (0.1 * torch.randn(B * N, generator=g)).clamp(-1, 1).to(gpu_device)
+    need = lib.pa_xvec_mfcc_workspace_bytes(w, B, N, S)
+    ws = torch.empty(need, dtype=torch.uint8, device=gpu_device)
+    if case == "one_sample_short":
+        n = smallest_accepted(eng.num_pool_frames) - 1
+        message = f"pa_xvec_mfcc_forward: {n} samples leave no frame after the MFCC front end + the TDNN stack"
+    else:
+        need -= 1
+        message = f"pa_xvec_mfcc_forward: workspace too small ({need} < {need + 1} bytes)"
+    check_refusal(lambda emb: lib.pa_xvec_mfcc_forward(w, ffi.ptr(wav), wav.numel(), N, B, n, None, S, 0, None, emb,
+                                                     ffi.ptr(ws), need, ffi.stream()),
+                  [((B, S, w.dimension), torch.float32)], message, gpu_device)
