@@ -649,6 +649,36 @@ size_t pa_der_chunks_workspace_bytes(int B, int Q);
 /* out (3 Q + 1) int64, overwritten: sums over the B chunks of counts (Q, 3), then of total */
 int pa_der_chunks_sum(const int32_t* counts, const int32_t* total, int B, int Q, int64_t* out, void* stream);
 
+/* ---- speaker-verification trials (pipelines/speaker_verification.py:858-895,
+ *      torchmetrics/classification/equal_error_rate.py) ---- */
+
+/* out[t] = scipy.spatial.distance.cdist(E[idx1[t]:idx1[t]+1], E[idx2[t]:idx2[t]+1], "cosine")[0, 0], bit for bit
+ * (the arithmetic of pa_cdist_cosine_f64).  E: (N, D) float64 rows; idx1, idx2: (T) int32, each in 0..N-1 (the
+ * CALLER checks the range: the kernel does not); T < 2^31; norms_scratch: N doubles. */
+int pa_trial_cosine_f64(const double* E, int N, int D, const int32_t* idx1, const int32_t* idx2, long T,
+                        double* out, double* norms_scratch, void* stream);
+
+/* the sizes at which the curve kernels change path: scores per workgroup, and workgroup sums per chunk of the
+ * two-level scan (a list of more than block * chunk scores fills a second chunk) */
+int pa_det_block_elements(void);
+int pa_det_scan_chunk(void);
+/* bytes of `workspace` below for T scores (0: T outside 1..2^31-1) */
+size_t pa_det_workspace_bytes(long T);
+/* sklearn.metrics.roc_curve(drop_intermediate=True) + det_curve's fnr = 1 - tpr, first crossing and equal error
+ * rate, in exact integers and single float64 divisions (csrc/verification.hip).
+ * sorted_keys (T) float64 ASCENDING from a stable sort, labels (T) uint8 (non-zero = target trial) in the same
+ * order; the curve is walked from the far end.  negate: the keys are negated distances; thresholds are negated back.
+ * fps, tps: (T + 1) int32, required; thresholds, fpr, fnr: (T + 1) float64, all three or all NULL (only the
+ * equal error rate is wanted).  Point 0 is (0, 0) at threshold +inf (-inf when negate).
+ * status, 8 int64, overwritten: [0] non-finite keys, [1] targets P, [2] non-targets N, [3] points written,
+ * [4] k = first point with fpr > fnr (-1: none), [5] the bits of the float64 eer =
+ * 0.25 * (((fpr[k-1] + fpr[k]) + fnr[k-1]) + fnr[k]) (NaN without a crossing), [6] tie groups.
+ * With status[0] != 0 or P == 0 or N == 0 the curve is meaningless and the caller must refuse it.
+ * Several launches on `stream`, none of which waits for another workgroup; results are bit-reproducible. */
+int pa_det_curve_f64(const double* sorted_keys, const uint8_t* labels, long T, int negate, int32_t* fps,
+                     int32_t* tps, double* thresholds, double* fpr, double* fnr, int64_t* status, void* workspace,
+                     size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -20,5 +20,6 @@ from .voice_activity_detection import VoiceActivityDetection  # noqa: E402,F401
 from .multilabel import MultiLabelSegmentation  # noqa: E402,F401
 from .hook import ArtifactHook, Hooks, ProgressHook, TimingHook  # noqa: E402,F401
 from . import metrics  # noqa: E402,F401
+from . import verification  # noqa: E402,F401
 from .metrics import (DiscreteDiarizationErrorRate, diarization_error_rate,  # noqa: E402,F401
                       discrete_diarization_error_rate, optimal_diarization_error_rate)

@@ -276,6 +276,12 @@ _OPTIONAL: list[tuple] = [
      C.c_int),
     ("pa_der_chunks_workspace_bytes", [C.c_int, C.c_int], C.c_size_t),
     ("pa_der_chunks_sum", [c_fp, c_fp, C.c_int, C.c_int, c_fp, c_fp], C.c_int),
+    ("pa_trial_cosine_f64", [c_fp, C.c_int, C.c_int, c_fp, c_fp, C.c_long, c_fp, c_fp, c_fp], C.c_int),
+    ("pa_det_block_elements", [], C.c_int),
+    ("pa_det_scan_chunk", [], C.c_int),
+    ("pa_det_workspace_bytes", [C.c_long], C.c_size_t),
+    ("pa_det_curve_f64", [c_fp, c_fp, C.c_long, C.c_int, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, C.c_size_t,
+                          c_fp], C.c_int),
 ]
 
 

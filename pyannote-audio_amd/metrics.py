@@ -28,6 +28,7 @@ from scipy.optimize import linear_sum_assignment
 from . import ffi
 from .core import HAVE_PYANNOTE_CORE, SEGMENT_PRECISION, Annotation, Segment, SlidingWindowFeature
 from .permutation import permutate
+from .verification import EqualErrorRate  # noqa: F401  (the classification half of the reference's torchmetrics)
 
 MAX_SPEAKERS = 32        # a frame's speakers travel as one 32-bit mask
 MAX_THRESHOLDS = 64      # per launch; longer sweeps are split
