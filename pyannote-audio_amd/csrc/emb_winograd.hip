@@ -31,7 +31,7 @@
 //     accumulator registers, epilogue addresses are incremental, and two independent workgroups per CU
 //     interleave at instruction granularity (a strict two-phase ping-pong of an 8-wave workgroup was
 //     measured 6 % slower: tools/probes/emb_winograd_pingpong.hip.txt).
-//   * where a stage's time goes (s_memtime stamps of an instrumented build, tools/wino_stamps.py, cycles per
+//   * where a stage's time goes (s_memtime stamps of the `stamp` variant, tools/wino_stamps.py, cycles per
 //     wave and stage on the 20 x 250 x 128 layer): barrier 90 | DMA issue 3 100-4 700 | wait 450-600 |
 //     barrier 200-270 | transform 700-1 240 | 128 MFMAs 4 190 | epilogue 1 000 (amortised) = 11 100, against
 //     2 x 4 096 for the two waves of a SIMD.  The DMA phase is long because its 15 instructions only issue in
@@ -39,74 +39,21 @@
 //     instructions); a wave's own DMA spread through its own MFMA run costs 5-25 cycles per instruction
 //     (tools/probes/interleave_probe.py) but needs both LDS images double-buffered = one workgroup per CU.
 //     Raising the wave priority outside the MFMA run (s_setprio) does not change the picture.  That
-//     one-workgroup-per-CU software-pipelined form was built (tools/probes/emb_winograd_sp.hip.txt: next
-//     stage's DMA and the residual loads issued from inside the MFMA run, one barrier per stage, results
-//     identical) and measured 10-17 % SLOWER (6 350 instead of 5 430 cycles per stage and wave on the
-//     128-channel layer): with nothing else on the SIMD its transform, descriptor arithmetic, barrier and
-//     epilogue are all exposed.  Two workgroups per CU stay.
+//     one-workgroup-per-CU software-pipelined form exists as a probe only, not in this file
+//     (tools/probes/emb_winograd_sp.hip.txt: next stage's DMA and the residual loads issued from inside the
+//     MFMA run, one barrier per stage, results identical); it measured 10-17 % SLOWER (6 350 instead of 5 430
+//     cycles per stage and wave on the 128-channel layer): with nothing else on the SIMD its transform,
+//     descriptor arithmetic, barrier and epilogue are all exposed.  Two workgroups per CU stay.
 // Numerics: fp32 throughout; the transforms only add/subtract and the 1/2 factors of G are applied in
 // float64 on the host; error ~3x the direct form's (tests: |err| <= 1e-4 max|ref| per conv, end to end).
 #include <stdlib.h>
 
 #include "common.h"
-#ifndef PA_WINO32_PATCH_FIRST   // k_conv3x3_wino32: the next tile's patch DMA in front of the epilogue (0: behind it, round 3)
-#define PA_WINO32_PATCH_FIRST 1
-#endif
-#ifndef PA_WINO32_WAIT_STORES   // 1: the step barrier of k_conv3x3_wino32 also waits for the epilogue's stores (A/B aid)
-#define PA_WINO32_WAIT_STORES 0
-#endif
-#ifndef PA_WINO_STORE_AUX   // cache-policy bits of the output stores (2 = nt): A/B aid, see profiles/r5_xcd_ranges.txt
-#define PA_WINO_STORE_AUX 0
-#endif
-
-#ifdef PA_WINO_NOSCHED   // development A/B switch (never defined in the product build)
-#define WINO_SCHED_BARRIER()
-#else
-#define WINO_SCHED_BARRIER() __builtin_amdgcn_sched_barrier(0)
-#endif
-
-#ifndef PA_WINO_STAMP
-#define PA_WINO_STAMP 0
-#endif
-// (nt / "streaming" cache-policy bits on the patch DMA, the residual loads or the stores: measured neutral to
-//  10-25 % slower, profiles/r3_wino_cache_policy.txt -- every access keeps the default policy)
-#ifndef PA_WINO_RPIN
-#define PA_WINO_RPIN 1
-#endif
-#ifndef PA_WINO_REFRESH   // 128-channel residual kernel with pinned residual loads (-DPA_WINO_REFRESH=0: A/B)
-#define PA_WINO_REFRESH 1
-#endif
-#ifndef PA_WINO_RTOUCH
-#define PA_WINO_RTOUCH 1
-#endif
-#ifndef PA_WINO_RPRE   // residual prefetch through LDS in front of a tile's last MFMA run (-DPA_WINO_RPRE=0: A/B)
-#define PA_WINO_RPRE 1
-#endif
-namespace pa {
-
-#if PA_WINO_STAMP
-// development instrumentation (never in the product build): s_memtime stamps of the phases of the first
-// 64 stages of the first 16 workgroups, per wave; read back with pa_wino_read_stamps
-constexpr int STAMP_WG = 16, STAMP_IT = 64, STAMP_PH = 8;
-__device__ unsigned long long g_wino_stamps[STAMP_WG * 4 * STAMP_IT * STAMP_PH];
-#define WINO_STAMP(p) st_[p] = __builtin_amdgcn_s_memtime()
-#define WINO_STAMP_FLUSH()                                                                    \
-  do {                                                                                        \
-    if (blockIdx.x < STAMP_WG && st_iter < STAMP_IT && lane == 0) {                            \
-      _Pragma("unroll") for (int p_ = 0; p_ < STAMP_PH; ++p_)                                  \
-          g_wino_stamps[((blockIdx.x * 4 + slw) * STAMP_IT + st_iter) * STAMP_PH + p_] = st_[p_]; \
-    }                                                                                         \
-    ++st_iter;                                                                                \
-  } while (0)
-#else
-#define WINO_STAMP(p)
-#define WINO_STAMP_FLUSH()
-#endif
-
-}  // namespace pa
 #include "emb_winograd_geom.h"
 namespace pa {
 
+// (nt / "streaming" cache-policy bits on the patch DMA, the residual loads or the stores: measured neutral to
+//  10-25 % slower, profiles/r3_wino_cache_policy.txt and r5_xcd_ranges.txt -- every access keeps the default policy)
 typedef __attribute__((address_space(3))) void* lds_ptr_t;
 
 // Workgroup barrier WITHOUT the release/acquire fence of __syncthreads(): the fence drains vmcnt, i.e. it
@@ -190,13 +137,13 @@ __device__ __forceinline__ void wino_transform(const float* patch, const int (&p
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
     if (i + 1 < 4) rd(i + 1, d[(i + 1) & 1]);
-    WINO_SCHED_BARRIER();
+    __builtin_amdgcn_sched_barrier(0);
     const f32x4(&c)[4] = d[i & 1];
     v[i][0] = vsub(c[0], c[2], m1);
     v[i][1] = c[1] + c[2];
     v[i][2] = vsub(c[2], c[1], m1);
     v[i][3] = vsub(c[1], c[3], m1);
-    WINO_SCHED_BARRIER();
+    __builtin_amdgcn_sched_barrier(0);
   }
   } else {
 #pragma unroll
@@ -229,33 +176,32 @@ __device__ __forceinline__ void wino_transform(const float* patch, const int (&p
 struct WinoNoHook {
   __device__ __forceinline__ void operator()(int) const {}
 };
-// `hook(xi)` runs after the MFMAs of point xi: the software-pipelined kernel issues the NEXT stage's DMA
-// pieces (and the residual loads of the epilogue) from there -- a wave's own memory instructions cost it
-// 5-25 cycles each inside its MFMA run (tools/probes/interleave_probe.py).
+// `hook(xi)` runs after the MFMAs of point xi.  No kernel of this file passes one: the software-pipelined probe
+// (tools/probes/emb_winograd_sp.hip.txt) issued the NEXT stage's DMA pieces from there.  The parameter and the second
+// scheduling barrier stay because hipcc allocates the registers of k_conv3x3_wino differently without them
+// (profiles/switch_removal_objects.txt), and these kernels are kept at their measured code.
 template <bool FIRST, typename Hook = WinoNoHook>
 __device__ __forceinline__ void wino_mfma(const float* uslab, const f32x4 (&v)[4][4], f32x4 (&acc)[16][2],
                                           int t, int g, const Hook& hook = Hook()) {
-  constexpr int PF = 1;
-  f32x4 bf[PF + 1][2];
+  f32x4 bf[2][2];
   // row = 32 xi + 16 cg + t: its swizzle bit ((row >> 2) & 1) = (t >> 2) & 1 does not depend on xi / cg,
   // so every read is (lane base) + compile-time offset -> folded into the ds_read immediate
   const float* ub = uslab + t * WCB + 4 * wslot(t, g);
   auto load = [&](int xi) {
 #pragma unroll
     for (int cg = 0; cg < 2; ++cg)
-      bf[xi % (PF + 1)][cg] = *reinterpret_cast<const f32x4*>(ub + (xi * W_BN + 16 * cg) * WCB);
+      bf[xi & 1][cg] = *reinterpret_cast<const f32x4*>(ub + (xi * W_BN + 16 * cg) * WCB);
   };
-#pragma unroll
-  for (int xi = 0; xi < PF; ++xi) load(xi);
+  load(0);
   // sched_barrier(0): nothing moves across.  Without them the scheduler (minimising register pressure)
   // sinks each ds_read pair right in front of its first MFMA and the LDS latency is exposed 16 times per
   // stage (measured: 46 instead of 32 cycles per MFMA).
-  WINO_SCHED_BARRIER();
+  __builtin_amdgcn_sched_barrier(0);
   const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
   for (int xi = 0; xi < 16; ++xi) {
-    if (xi + PF < 16) load(xi + PF);
-    WINO_SCHED_BARRIER();
+    if (xi + 1 < 16) load(xi + 1);
+    __builtin_amdgcn_sched_barrier(0);
     const f32x4 av = v[xi >> 2][xi & 3];
     // alternate the two accumulators: a 16x16x4 MFMA issues every 32 cycles but its result is ready
     // after 40, so back-to-back MFMAs on ONE accumulator would stall 8 cycles each
@@ -263,12 +209,12 @@ __device__ __forceinline__ void wino_mfma(const float* uslab, const f32x4 (&v)[4
     for (int ks = 0; ks < 4; ++ks) {
       // U as the A operand (rows = output channels), V as B (columns = tiles): D[cout 4g + r][tile t],
       // i.e. a lane ends up with FOUR CONSECUTIVE output channels of ONE tile -> 16-byte epilogue accesses
-      acc[xi][0] = MFMA16(bf[xi % (PF + 1)][0][ks], av[ks], (FIRST && ks == 0) ? zero : acc[xi][0]);
-      acc[xi][1] = MFMA16(bf[xi % (PF + 1)][1][ks], av[ks], (FIRST && ks == 0) ? zero : acc[xi][1]);
+      acc[xi][0] = MFMA16(bf[xi & 1][0][ks], av[ks], (FIRST && ks == 0) ? zero : acc[xi][0]);
+      acc[xi][1] = MFMA16(bf[xi & 1][1][ks], av[ks], (FIRST && ks == 0) ? zero : acc[xi][1]);
     }
-    WINO_SCHED_BARRIER();
+    __builtin_amdgcn_sched_barrier(0);
     hook(xi);
-    WINO_SCHED_BARRIER();
+    __builtin_amdgcn_sched_barrier(0);
   }
 }
 
@@ -293,7 +239,6 @@ __device__ __forceinline__ void wino_out_offsets(int (&off)[4], const WinoTile& 
   off[3] = in1 ? obase + srow + spix : OOB;
 }
 
-// PRE: the residual values were loaded by the caller (inside the last MFMA run) into `rv`
 // PRE0: the first channel group's four residual vectors were sent to LDS (`rbuf`, 1 KB per wave and vector, lane l
 // at 16 l) by LDS-DMA pieces issued in front of the tile's LAST MFMA run, so that their HBM latency hides under
 // that run without holding registers (the kernel has none to spare: a register version spilled 20-30 VGPRs);
@@ -305,32 +250,25 @@ constexpr int WINO_EPILOGUE_STORES = 2 * 4;
 static_assert(WINO_EPILOGUE_STORES == WINO_EPILOGUE_STORES_LIT, "the literal of the s_waitcnt string");
 #define WINO_STR2(x) #x
 #define WINO_STR(x) WINO_STR2(x)
-template <bool HAS_R, bool PRE = false, bool PRE0 = false, bool PIN = false>
+template <bool HAS_R, bool PRE0 = false, bool PIN = false>
 __device__ __forceinline__ void wino_epilogue(const f32x4 (&acc)[16][2], const WinoTile& q, int H, int W,
                                               int COUT, const float* __restrict__ shift,
                                               const float* __restrict__ R, float* __restrict__ Y,
                                               int relu, int t, int g, int wr, int wc, float m1,
-                                              const int* off_pre = nullptr, f32x4 (*rv_pre)[4] = nullptr,
                                               const float* rbuf = nullptr) {
   const __amdgpu_buffer_rsrc_t ysrd = __builtin_amdgcn_make_buffer_rsrc(
       Y + (long)q.b * H * W * COUT, 0, H * W * COUT * 4, 0x00020000);
   const __amdgpu_buffer_rsrc_t rsrd = __builtin_amdgcn_make_buffer_rsrc(
       const_cast<float*>(HAS_R ? R + (long)q.b * H * W * COUT : Y), 0, H * W * COUT * 4, 0x00020000);
   int off[4];
-  if (PRE) {
-#pragma unroll
-    for (int e = 0; e < 4; ++e) off[e] = off_pre[e];
-  } else {
-    wino_out_offsets(off, q, W, COUT, t, g, wr, wc);
-  }
+  wino_out_offsets(off, q, W, COUT, t, g, wr, wc);
   f32x4 rv[2][4];
 #pragma unroll
   for (int cgi = 0; cgi < 2; ++cgi)
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
       const int cg = (PRE0 && HAS_R) ? 1 - cgi : cgi;   // PRE0: the global loads of group 1 go out first
-      if (PRE && HAS_R) rv[cg][e] = rv_pre[cg][e];
-      else if (PRE0 && HAS_R && cg == 0) {
+      if (PRE0 && HAS_R && cg == 0) {
         if (e == 0) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");   // the 4 loads of cg = 1 are newer
         rv[0][e] = *reinterpret_cast<const f32x4*>(rbuf + 256 * e);
       } else
@@ -361,7 +299,7 @@ __device__ __forceinline__ void wino_epilogue(const f32x4 (&acc)[16][2], const W
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
       const f32x4 vv = __builtin_elementwise_max(o4[e] + sh + rv[cg][e], lo4);
-      __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, vv), ysrd, off[e] + 64 * cg, 0, PA_WINO_STORE_AUX);
+      __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, vv), ysrd, off[e] + 64 * cg, 0, 0);
     }
   }
 }
@@ -387,13 +325,13 @@ __global__ __launch_bounds__(256, 2) void k_conv3x3_wino(
   // 64-channel layers (few stages per tile: the residual's latency was 14 % / 8 % of a tile).  Measured per
   // launch (B = 512, profiles/r3_wino_residual_prefetch.txt): 80x998x32 4.91 -> 4.44 ms, 40x499x64 3.77 -> 3.55;
   // on the 4 x 64-pixel tiles (128 channels) it LOSES 1 % and the 2 x 128-pixel tiles have no LDS left for it.
-  constexpr bool RPRE = PA_WINO_RPRE && HAS_R && TCG == 1;
+  constexpr bool RPRE = HAS_R && TCG == 1;
   float* rbuf = smem + G::LDS_FLOATS + 4 + 1024 * slw;
   // the 2 x 128-pixel tiles (256 channels) only TOUCH their residual lines ahead of the tile's last MFMA run (one
   // 4-byte DMA piece per wave into a 256-B scratch row that nobody reads): the epilogue's loads then hit L2.
   // Measured (B = 512, profiles/r3_wino_residual_touch.txt): 10x125x256 3.157 -> 3.099 ms; the 4 x 64-pixel tiles
   // (128 channels) LOSE 2 % with it (3.18 -> 3.24 ms), like they lose with the LDS staging above.
-  constexpr bool RTOUCH = PA_WINO_RTOUCH && HAS_R && TCG == 4;
+  constexpr bool RTOUCH = HAS_R && TCG == 4;
   // tiles are CLAIMED, not statically strided (common.h: TileQueue): thread 0 claims the next tile while
   // the current one is processed and publishes it through LDS at the tile boundary
   int* s_next = reinterpret_cast<int*>(smem + G::LDS_FLOATS);
@@ -412,17 +350,13 @@ __global__ __launch_bounds__(256, 2) void k_conv3x3_wino(
   // 20x250x128 + residual, two runs on one box): 3.169 -> 3.136 ms and 3.177 -> 3.127 ms (-1.3 %), results identical
   // (tests/test_emb_gpu.py); tools/build_variants.py "norefresh" builds the old form.  The other instantiations do
   // not change.
-  constexpr bool REFRESH = PA_WINO_REFRESH && HAS_R && TR == 2 && TCG == 2;
+  constexpr bool REFRESH = HAS_R && TR == 2 && TCG == 2;
   int prel[G::NPP];
   if (!REFRESH) wino_patch_lanes<TR, TCG>(prel, W, CIN, lane, slw, x0_last);
   f32x4 acc[16][2];
   int pbase[8];
   if (!REFRESH) wino_patch_bases<TR, TCG>(pbase, t, g, wr, wc);
   const float m1 = wino_minus_one();
-#if PA_WINO_STAMP
-  unsigned long long st_[STAMP_PH] = {0, 0, 0, 0, 0, 0, 0, 0};
-  int st_iter = 0;
-#endif
   {
     while (q >= 0) {
       if (REFRESH) {
@@ -437,22 +371,13 @@ __global__ __launch_bounds__(256, 2) void k_conv3x3_wino(
       const WinoTile cur = wino_decode(q, tiles_w, tiles_hw, n_tiles, 2 * TR, 32 * TCG, num_pb, y_first, xranges);
       if (tid == 0) ahead = tq_claim_own(tq);
       for (int c0 = 0; c0 < CIN; c0 += WCB) {
-        WINO_STAMP(0);
         wino_barrier();  // every wave is done reading the previous stage
-        WINO_STAMP(1);
         wino_issue_patch<TR, TCG>(X, H, W, CIN, cur, c0, patch, prel, slw, x0_last);
         wino_issue_u(U, CIN, COUT, cur.n0, c0, uslab, lane, slw);
-        WINO_STAMP(2);
         __builtin_amdgcn_s_waitcnt(0x0F70);
-        WINO_STAMP(3);
         wino_barrier();
-        WINO_STAMP(4);
         f32x4 v[4][4];
         wino_transform<TR, TCG, !HAS_R>(patch, pbase, v, m1);
-#if PA_WINO_STAMP
-        asm volatile("s_nop 0" ::"v"(v[3][3]), "v"(v[0][0]));   // the transform is complete here
-#endif
-        WINO_STAMP(5);
         if (RPRE && c0 + WCB >= CIN) {
           // last stage of the tile: the residual vectors of the first channel group leave for LDS now, ahead
           // of the MFMA run that hides their latency (wino_epilogue<.., PRE0>)
@@ -478,19 +403,11 @@ __global__ __launch_bounds__(256, 2) void k_conv3x3_wino(
         }
         if (c0 == 0) wino_mfma<true>(uslab, v, acc, t, g);
         else wino_mfma<false>(uslab, v, acc, t, g);
-        WINO_STAMP(6);
-        if (c0 + WCB < CIN) {
-          WINO_STAMP(7);
-          WINO_STAMP_FLUSH();
-        }
       }
       // (Issuing the NEXT tile's first stage in front of this epilogue, so that the epilogue hides its flight
       // time, was measured 3-8 % SLOWER on every layer shape: profiles/r3_wino_next_tile_prefetch.txt -- the
       // extra DMA issue lands in the phase where the other workgroup's MFMA stream owns the SIMD.)
-      wino_epilogue<HAS_R, false, RPRE, REFRESH && PA_WINO_RPIN>(acc, cur, H, W, COUT, shift, R, Y, relu, t, g, wr, wc,
-                                                                 m1, nullptr, nullptr, rbuf + 4 * lane);
-      WINO_STAMP(7);
-      WINO_STAMP_FLUSH();
+      wino_epilogue<HAS_R, RPRE, REFRESH>(acc, cur, H, W, COUT, shift, R, Y, relu, t, g, wr, wc, m1, rbuf + 4 * lane);
       if (tid == 0) *s_next = tq_resolve(tq, ahead);
       __syncthreads();
       q = *s_next;
@@ -508,7 +425,7 @@ static int launch_wino_r(const float* X, int B, int H, int W, int CIN, const flo
   const int tiles_w = cdiv(W, 32 * TCG), tiles_h = cdiv(H - y_first, 2 * TR);
   // + the claimed-tile mailbox (+ 16 KB of residual staging where it is used: k_conv3x3_wino RPRE)
   const size_t lds = (size_t)G::LDS_FLOATS * sizeof(float) + 16 +
-                     ((PA_WINO_RPRE && HAS_R && TCG == 1) ? 4 * 4096 : (PA_WINO_RTOUCH && HAS_R && TCG == 4 ? 4 * 256 : 0));
+                     ((HAS_R && TCG == 1) ? 4 * 4096 : (HAS_R && TCG == 4 ? 4 * 256 : 0));
   auto kernel = k_conv3x3_wino<TR, TCG, HAS_R>;
   // per-device launch state (the attribute and the CU count belong to a device, not to the process)
   constexpr int MAXDEV = 16;
@@ -636,7 +553,6 @@ __global__ __launch_bounds__(512) void k_conv3x3_wino32(
     } else if (step >= half) {
       // PREPARE: epilogue of the tile computed in the previous step, then the patch of the next one
       const int qn = done_q >= 0 ? mail[half] : -1;   // (published by the barrier that closed the COMPUTE step)
-#if PA_WINO32_PATCH_FIRST
       // the next tile's patch goes out FIRST (its buffers are free: this half's COMPUTE step has read them), so that its
       // flight overlaps the epilogue instead of following it: the layer is at 60-65 % of both of its bounds for lack of
       // loads in flight (profiles/r5_hbm_bw.txt)
@@ -652,24 +568,11 @@ __global__ __launch_bounds__(512) void k_conv3x3_wino32(
         done_q = -1;
         stored = true;
       }
-#else
-      if (done_q >= 0) {
-        wino_epilogue<HAS_R>(acc, fin, H, W, COUT, shift, R, Y, relu, t, g, wr, wc, m1);
-        done_q = -1;
-      }
-      q = qn;
-      if (q >= 0) {
-        cur = wino_decode(q, tiles_w, tiles_hw, 1, 8, 32, num_pb, 0, xranges);
-        wino_issue_patch<4, 1>(X, H, W, CIN, cur, 0, patch, prel, slw, x0_last);
-        wino_issue_patch<4, 1>(X, H, W, CIN, cur, WCB, patch + G::PATCH, prel, slw, x0_last);
-        if (leader) ahead = tq_claim_own(tq);
-      }
-#endif
     }
     // what the barrier needs is this half's patch in LDS.  The epilogue's 8 stores per lane are the NEWEST vector memory
     // operations of a PREPARE step (the patch pieces and the residual loads are older) and complete in order: leaving
     // them in flight across the barrier takes their acknowledgement latency off every step's critical path.
-    if (PA_WINO32_PATCH_FIRST && !PA_WINO32_WAIT_STORES && stored)
+    if (stored)
       asm volatile("s_waitcnt vmcnt(" WINO_STR(WINO_EPILOGUE_STORES_LIT) ") lgkmcnt(0)" ::: "memory");
     else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
     wino_barrier();
@@ -722,20 +625,6 @@ static int launch_wino(const float* X, int B, int H, int W, int CIN, const float
 }  // namespace pa
 
 extern "C" {
-
-#if PA_WINO_STAMP
-int pa_wino_read_stamps(unsigned long long* host, int zero) {
-  const size_t n = sizeof(unsigned long long) * pa::STAMP_WG * 4 * pa::STAMP_IT * pa::STAMP_PH;
-  (void)hipDeviceSynchronize();
-  if (hipMemcpyFromSymbol(host, HIP_SYMBOL(pa::g_wino_stamps), n) != hipSuccess) return 1;
-  if (zero) {
-    void* d = nullptr;
-    (void)hipGetSymbolAddress(&d, HIP_SYMBOL(pa::g_wino_stamps));
-    (void)hipMemset(d, 0, n);
-  }
-  return 0;
-}
-#endif
 
 // conv3x3, stride 1, pad 1, via Winograd F(2x2,3x3): Y = [relu](conv(X) + shift [+ R]).
 // U: G g G^T (BatchNorm scale folded) in the slab layout of weights.winograd_pack:

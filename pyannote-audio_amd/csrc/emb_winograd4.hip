@@ -162,45 +162,12 @@ __device__ __forceinline__ Wino4Stage wino4_stage(const Wino4Ctx& c, const float
   return st;
 }
 
-#ifndef PA_W4_STAMP
-#define PA_W4_STAMP 0
-#endif
-#ifndef PA_W4_DEFER_STORES   // stores of channel group 0 issued from inside the column arithmetic of group 1:
-#define PA_W4_DEFER_STORES 1 // 0 = never, 1 = instantiation without residual only, 2 = both (spills: slower)
-#endif
-// cache-policy bits of the output stores / the residual loads (gfx942+: 1 = sc0, 2 = nt, 16 = sc1).  The outputs are
-// written once and read by the NEXT kernel, 9 GB later: non-temporal stores leave the L2 to the patches, whose lines are
-// touched by four consecutive stages (8 of a pixel's 32 channels each): -2 % per launch on average, -4 % at 256 channels
-// (profiles/r5_xcd_ranges.txt, section 4).  Non-temporal residual loads measured slower.
-#ifndef PA_W4_STORE_AUX
-#define PA_W4_STORE_AUX 2
-#endif
-#ifndef PA_W4_RES_AUX
-#define PA_W4_RES_AUX 0
-#endif
-#ifndef PA_W4_STORES_IN_FLIGHT   // a tile's first stage does not wait for the previous tile's stores (0: vmcnt(0) as in round 4)
-#define PA_W4_STORES_IN_FLIGHT 1
-#endif
-#ifndef PA_W4_LATE_BARRIER   // the stage barrier behind most of the input transform (0: in front of it, as in round 4)
-#define PA_W4_LATE_BARRIER 1
-#endif
-#if PA_W4_STAMP
-// development instrumentation (never in the product build): s_memtime at the phases of the first 64 stages of
-// workgroups 0 .. 7, per wave; read back with pa_wino4_read_stamps
-__device__ unsigned long long g_w4_stamps[8 * 4 * 64 * 10];
-#define W4_STAMP(p) st_[p] = __builtin_amdgcn_s_memtime()
-#define W4_STAMP_FLUSH()                                                                      \
-  do {                                                                                        \
-    if (blockIdx.x < 8 && st_iter < 64 && lane == 0) {                                         \
-      _Pragma("unroll") for (int p_ = 0; p_ < 10; ++p_)                                        \
-          g_w4_stamps[((blockIdx.x * 4 + slw) * 64 + st_iter) * 10 + p_] = st_[p_];            \
-    }                                                                                         \
-    ++st_iter;                                                                                \
-  } while (0)
-#else
-#define W4_STAMP(p)
-#define W4_STAMP_FLUSH()
-#endif
+// cache-policy bits of the output stores (gfx942+: 1 = sc0, 2 = nt, 16 = sc1).  The outputs are written once and read
+// by the NEXT kernel, 9 GB later: non-temporal stores leave the L2 to the patches, whose lines are touched by four
+// consecutive stages (8 of a pixel's 32 channels each): -2 % per launch on average, -4 % at 256 channels
+// (profiles/r5_xcd_ranges.txt, section 4).  The residual loads keep the default policy (0): non-temporal ones
+// measured slower (same profile).
+constexpr int W4_STORE_AUX = 2;
 
 constexpr int W4_AGPR_POINTS = 32;   // 256 AccVGPRs; 4 points (32 registers) stay architectural
 // The partial waits of the stage loop count vector-memory operations (they complete in order): the numbers below are
@@ -342,7 +309,7 @@ __global__ __launch_bounds__(256, 1) void k_conv3x3_wino4(
   // the late stage barrier pays for the row-shaped units only (-0.8 %; the linear forms: +0.4 .. +1.3 %), and with the
   // barrier in FRONT of the transform the linear forms learn their next unit early enough to compute its lane offsets
   // before the transform's 144 live registers exist
-  constexpr bool LATE = PA_W4_LATE_BARRIER && MODE == 0;
+  constexpr bool LATE = MODE == 0;
   constexpr bool LIN = MODE != 0;    // a unit = 16 consecutive tiles of the raster order (per-lane tiles)
   constexpr bool RUN = MODE == 2;    // ... whose patch keeps the row-shaped layout, run by run
   using G = std::conditional_t<MODE == 0, Wino4Geom, std::conditional_t<MODE == 1, Wino4LinGeom, Wino4RunGeom>>;
@@ -425,20 +392,15 @@ __global__ __launch_bounds__(256, 1) void k_conv3x3_wino4(
   f32x4 acca[W4_AGPR_POINTS][2];        // points 0 .. 31: AccVGPRs
   f32x4 accv[36 - W4_AGPR_POINTS][2];   // points 32 .. 35: architectural registers
 
-#if PA_W4_STAMP
-  unsigned long long st_[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-  int st_iter = 0;
-#endif
   while (true) {
     for (int s = 0; s < nstages; ++s) {
-      W4_STAMP(0);
       // LATE BARRIER (round 5).  A stage needs its own PATCH for the input transform and everybody's U pieces only for
       // the MFMA run.  The patch pieces of a stage are issued in front of its U pieces and loads complete in order, so
       // vmcnt(9) -- this wave's 9 U pieces may still fly -- is "my patch has landed"; the full wait and the workgroup
       // barrier (everybody's U pieces have landed, everybody is done with the other U buffer) move behind the
       // transform's column pass and first rows, which hide what is left of the U flight and of the waves' skew.  A
       // tile's first stage still waits for everything here: the epilogue's stores and residual loads were issued
-      // behind its staging.  (PA_W4_LATE_BARRIER=0: round 4's order, barrier in front of the transform.)
+      // behind its staging.  (The linear forms keep round 4's order, the barrier in front of the transform.)
       if constexpr (LATE) {
       if (s == 0) {
         // A tile's first stage: its staging was issued from inside the PREVIOUS tile's last MFMA run, i.e. in front of
@@ -447,7 +409,7 @@ __global__ __launch_bounds__(256, 1) void k_conv3x3_wino4(
         // operations complete in order: vmcnt(32) = "the staging has landed" without waiting for the acknowledgement of
         // the stores (~2 k cycles per tile).  (The next group's claim -- an atomic of thread 0 -- is issued in FRONT of
         // the epilogue for that reason.)  The first tile of a workgroup has nothing but its staging in flight.
-        if (PA_W4_STORES_IN_FLIGHT && !first_tile) asm volatile("s_waitcnt vmcnt(" W4_STR(W4_TAIL_WAIT_LIT) ")" ::: "memory");
+        if (!first_tile) asm volatile("s_waitcnt vmcnt(" W4_STR(W4_TAIL_WAIT_LIT) ")" ::: "memory");
         else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       } else {
         asm volatile("s_waitcnt vmcnt(" W4_STR(W4_U_PIECES_LIT) ")" ::: "memory");   // (the U pieces are the NEWEST of the stage)
@@ -455,7 +417,6 @@ __global__ __launch_bounds__(256, 1) void k_conv3x3_wino4(
       } else {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this stage's images have landed (issued a stage ago)
       }
-      W4_STAMP(1);
       // the claim of the NEXT group was issued at the start of this tile: its value is picked up here, behind the
       // wait above (anywhere else the compiler's own vmcnt wait for it would also wait for staging in flight), and
       // published by the barrier of the tile's last stage
@@ -477,7 +438,6 @@ __global__ __launch_bounds__(256, 1) void k_conv3x3_wino4(
         if constexpr (LATE) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's U pieces
         __builtin_amdgcn_s_barrier();                       // ... everybody's; and everybody is done with the other buffer
         asm volatile("" ::: "memory");
-        W4_STAMP(2);
         if (s + 1 < nstages) {
           nst = wino4_stage(cctx, U, COUT, CIN, s + 1, my_patch, uother);
         } else {
@@ -552,10 +512,6 @@ __global__ __launch_bounds__(256, 1) void k_conv3x3_wino4(
           __builtin_amdgcn_sched_barrier(0);
         }
       }
-#if PA_W4_STAMP
-      asm volatile("s_nop 0" ::"v"(v[5][5]), "v"(v[0][0]));   // the transform is complete here
-#endif
-      W4_STAMP(3);
       // ---- 36 points x 2 channel groups x 2 k-steps, two points at a time (a dependent MFMA is four MFMAs behind
       // its producer); U fragments of the next pair are read while this pair's MFMAs issue.  The MFMAs are inline
       // assembly because the accumulators must be PINNED: 32 points in the 256 AccVGPRs, 4 in architectural
@@ -617,12 +573,7 @@ __global__ __launch_bounds__(256, 1) void k_conv3x3_wino4(
       };
       if (s == 0) mfma_run(std::true_type{});
       else mfma_run(std::false_type{});
-      W4_STAMP(4);
       buf ^= 1;
-      if (s + 1 < nstages) {
-        W4_STAMP(5);
-        W4_STAMP_FLUSH();
-      }
     }
     // (the claim of the group after the next one: an atomic -- in front of the epilogue's stores, see the first-stage wait)
     if (tid == 0 && nq >= 0) claim = tq_claim_own(tq);
@@ -677,11 +628,11 @@ __global__ __launch_bounds__(256, 1) void k_conv3x3_wino4(
       // where those cycles are filled with vector work; group 1's own stores have nothing left to hide under.  (With a
       // residual the 64 held registers spill; an epilogue in four half passes over output rows {0,1} / {2,3} -- 8 held
       // stores at a time -- fits but reads every accumulator twice: measured 3-5 % SLOWER, profiles/r4_wino4_held_stores.txt.)
-      constexpr bool DEFER = PA_W4_DEFER_STORES == 2 || (PA_W4_DEFER_STORES == 1 && !HAS_R);
+      constexpr bool DEFER = !HAS_R;
       f32x4 held[4][4];
       auto store_held = [&](const int k) {   // (k: compile-time after unrolling)
         __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, held[k >> 2][k & 3]), ysrd,
-                                               ooff(k >> 2, k & 3, 0), 0, PA_W4_STORE_AUX);
+                                               ooff(k >> 2, k & 3, 0), 0, W4_STORE_AUX);
       };
 #pragma unroll
       for (int cg = 0; cg < 2; ++cg) {
@@ -704,7 +655,7 @@ __global__ __launch_bounds__(256, 1) void k_conv3x3_wino4(
 #pragma unroll
             for (int qq = 0; qq < 4; ++qq)
               rv[p][qq] = __builtin_bit_cast(
-                  f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsrd, ooff(p, qq, cg), 0, PA_W4_RES_AUX));
+                  f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsrd, ooff(p, qq, cg), 0, 0));
         }
         __builtin_amdgcn_sched_barrier(0);
         f32x4 o[4][4];
@@ -764,14 +715,10 @@ __global__ __launch_bounds__(256, 1) void k_conv3x3_wino4(
 #pragma unroll
               for (int qq = 0; qq < 4; ++qq)
                 rv[p][qq] = __builtin_bit_cast(
-                    f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsrd, ooff(p, qq, cg), 0, PA_W4_RES_AUX));
+                    f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsrd, ooff(p, qq, cg), 0, 0));
             __builtin_amdgcn_sched_barrier(0);
           }
         }
-#if PA_W4_STAMP
-        asm volatile("s_nop 0" ::"v"(o[3][3]), "v"(o[0][0]));
-        st_[6 + 2 * cg] = __builtin_amdgcn_s_memtime();
-#endif
         // all 16 outputs of the channel group are finished FIRST and then stored from 16 different register quads: a
         // store reads its data when the memory pipe gets to it, and a vector write that recycles the same registers
         // for the next output waits for that (first build: one quad for all 16 stores, 3 300 cycles per group)
@@ -795,17 +742,12 @@ __global__ __launch_bounds__(256, 1) void k_conv3x3_wino4(
 #pragma unroll
             for (int qq = 0; qq < 4; ++qq)
               __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, o[p][qq]), ysrd, ooff(p, qq, cg), 0,
-                                                     PA_W4_STORE_AUX);
+                                                     W4_STORE_AUX);
         }
         __builtin_amdgcn_sched_barrier(0);
-#if PA_W4_STAMP
-        st_[7 + 2 * cg] = __builtin_amdgcn_s_memtime();
-#endif
       }
 #undef W4_ACC
     }
-    W4_STAMP(5);
-    W4_STAMP_FLUSH();
     if (nq < 0) break;
     cur = nxt;
     if constexpr (LIN) {
@@ -895,16 +837,6 @@ static int launch_wino4(const float* X, int B, int H, int W, int CIN, const floa
 }  // namespace pa
 
 extern "C" {
-
-#if PA_W4_STAMP
-int pa_wino4_read_stamps(unsigned long long* host) {
-  (void)hipDeviceSynchronize();
-  return hipMemcpyFromSymbol(host, HIP_SYMBOL(pa::g_w4_stamps), sizeof(unsigned long long) * 8 * 4 * 64 * 10) ==
-                 hipSuccess
-             ? 0
-             : 1;
-}
-#endif
 
 // conv3x3, stride 1, pad 1, via Winograd F(4x4,3x3): Y = [relu](conv(X) + shift [+ R]).  X, R, Y: NHWC float32.
 // U: G g G^T (BatchNorm scale folded) in the slab layout of weights.winograd4_pack / pa_winograd4_pack_host:

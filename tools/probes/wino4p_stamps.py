@@ -1,8 +1,11 @@
 """Phase anatomy of k_conv3x3_wino4p (development aid): runs one layer shape with the instrumented library
-(tools/build_variants.py: libpa_w4pstamp.so) and prints, per wave of workgroup 0, the mean cycles of a stage spent
+libpa_w4pstamp.so and prints, per wave of workgroup 0, the mean cycles of a stage spent
 in the ticks: input transform | sync | MFMA run (with the interleaved DMA issue) | sync; and for a tile's last
 stage the epilogue marks.
-usage: PA_LIB=pyannote-audio_amd/build/variants/libpa_w4pstamp.so python tools/wino4p_stamps.py [cin H W B]"""
+The variant tag was `w4pstamp` (round 4); tools/build_variants.py no longer lists it, because the paired kernel is an
+archived probe: the library is the product library with tools/probes/emb_winograd4_paired.hip.txt compiled with
+-DPA_W4P_STAMP=1 and linked in.
+usage: PA_LIB=pyannote-audio_amd/build/variants/libpa_w4pstamp.so python tools/probes/wino4p_stamps.py [cin H W B]"""
 import ctypes as C, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
@@ -12,6 +15,9 @@ from pyannote_audio_amd.weights import winograd4_pack, winograd4_weights
 cin, H, W, B = (int(a) for a in sys.argv[1:5]) if len(sys.argv) >= 5 else (128, 20, 250, 512)
 dev = torch.device("cuda:0")
 lib = ffi.load()
+if not hasattr(lib, "pa_wino4p_read_stamps"):
+    raise SystemExit("the loaded library has no pa_wino4p_read_stamps: it is not the `w4pstamp` build of the paired "
+                     "probe kernel (see the docstring); point PA_LIB at that library")
 X = torch.randn(B, H, W, cin, device=dev)
 U = winograd4_pack(winograd4_weights(torch.randn(cin, cin, 3, 3) * 0.05)).to(dev)
 sh = torch.randn(cin, device=dev)

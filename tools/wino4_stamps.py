@@ -1,5 +1,6 @@
-"""Phase anatomy of k_conv3x3_wino4 (development aid): runs one layer shape with the instrumented library
-(tools/build_variants.py: libpa_w4stamp.so) and prints, per wave of workgroup 0, the mean cycles of a stage spent
+"""Phase anatomy of k_conv3x3_wino4 (development aid): runs one layer shape with the instrumented library that
+`python tools/build_variants.py w4stamp` builds (emb_winograd4.hip of revision 2a90f5a with -DPA_W4_STAMP=1; the
+product sources carry no stamps) and prints, per wave of workgroup 0, the mean cycles of a stage spent
 in: wait for the stage's DMA | barrier | next-stage setup + input transform | MFMA run (with the interleaved DMA
 issue) | rest (epilogue at a tile's last stage).
 usage: PA_LIB=pyannote-audio_amd/build/variants/libpa_w4stamp.so python tools/wino4_stamps.py [cin H W B]"""
@@ -12,6 +13,9 @@ from pyannote_audio_amd.weights import winograd4_pack, winograd4_weights
 cin, H, W, B = (int(a) for a in sys.argv[1:5]) if len(sys.argv) >= 5 else (128, 20, 250, 512)
 dev = torch.device("cuda:0")
 lib = ffi.load()
+if not hasattr(lib, "pa_wino4_read_stamps"):
+    raise SystemExit("the loaded library has no pa_wino4_read_stamps: build the `w4stamp` variant "
+                     "(python tools/build_variants.py w4stamp) and point PA_LIB at build/variants/libpa_w4stamp.so")
 X = torch.randn(B, H, W, cin, device=dev)
 U = winograd4_pack(winograd4_weights(torch.randn(cin, cin, 3, 3) * 0.05)).to(dev)
 sh = torch.randn(cin, device=dev)

@@ -1,6 +1,7 @@
-"""Phase timeline of k_conv3x3_wino from an instrumented build (-DPA_WINO_STAMP=1 -DPA_WINO_PF=0,
-tools/build_variants.py tag `stamp`): s_memtime stamps per wave and stage of the first 16 workgroups.
-usage: PA_LIB=.../libpa_stamp.so python tools/wino_stamps.py out.npz"""
+"""Phase timeline of k_conv3x3_wino from the instrumented library that `python tools/build_variants.py stamp`
+builds (emb_winograd.hip of revision 2a90f5a with -DPA_WINO_STAMP=1; the product sources carry no stamps): s_memtime
+stamps per wave and stage of the first 16 workgroups.
+usage: PA_LIB=pyannote-audio_amd/build/variants/libpa_stamp.so python tools/wino_stamps.py out.npz"""
 import ctypes as C, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -10,6 +11,9 @@ from pyannote_audio_amd.weights import winograd_pack, winograd_weights
 
 dev = torch.device("cuda:0")
 lib = ffi.load()
+if not hasattr(lib, "pa_wino_read_stamps"):
+    raise SystemExit("the loaded library has no pa_wino_read_stamps: build the `stamp` variant "
+                     "(python tools/build_variants.py stamp) and point PA_LIB at build/variants/libpa_stamp.so")
 lib.pa_wino_read_stamps.argtypes = [C.c_void_p, C.c_int]
 B = int(os.environ.get("B", "256"))
 shapes = [(80, 998, 32, True), (40, 499, 64, True), (20, 250, 128, True), (10, 125, 256, True), (80, 998, 32, False)]
