@@ -526,6 +526,38 @@ int pa_linkage_centroid_f64_ex(double* D, int n, double* Z, void* workspace, siz
                                void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Single, complete, average, weighted and Ward linkage (csrc/linkage_chain.hip), bit-identical to
+ * scipy.cluster.hierarchy.linkage(y, method): the other values of AgglomerativeClustering.method
+ * (pipelines/clustering.py:292-480).  What runs where: these five and centroid on the device; median -- and any size
+ * whose square matrix exceeds the cap below -- on the host in SciPy.
+ * ---------------------------------------------------------------------------------------- */
+enum {
+  PA_LINKAGE_SINGLE = 0,   /* _hierarchy.mst_single_linkage */
+  PA_LINKAGE_COMPLETE = 1, /* _hierarchy.nn_chain with max(a, b) */
+  PA_LINKAGE_AVERAGE = 2,  /* ... (nx a + ny b) / (nx + ny) */
+  PA_LINKAGE_WEIGHTED = 3, /* ... 0.5 (a + b) */
+  PA_LINKAGE_WARD = 4      /* ... sqrt(((ni + nx) a^2 + (ni + ny) b^2 - ni c^2) / (nx + ny + ni)) */
+};
+/* scipy.spatial.distance.pdist(X, "cosine") with the arithmetic of the cosine cdist above.  out: condensed, the
+ * layout of the Euclidean pdist;  norms: scratch of N doubles.  A zero row yields NaN, as in SciPy. */
+int pa_pdist_cosine_f64(const double* X, int N, int D, double* out, double* norms, void* stream);
+/* *flag (one int in device memory) = 1 when any of the `count` doubles is NaN or infinite, else 0: the check SciPy's
+ * linkage makes on its input ("The condensed distance matrix must contain only finite values."), to be read by the
+ * caller BEFORE the merge is launched. */
+int pa_nonfinite_flag_f64(const double* v, long count, int* flag, void* stream);
+/* The unsorted merge list of SciPy's algorithm from a condensed matrix D (n*(n-1)/2 doubles, left intact).
+ * raw: (n-1, 4) doubles [x, y, height, size of the merger], x < y cluster slots in merge order for the chain
+ * methods; [x, y, height, 0] in Prim's order for single.  SciPy's dendrogram is the stable sort of these rows by
+ * height followed by its union-find relabelling (distance.linkage_finish).  One persistent workgroup on a square
+ * copy of the matrix in the workspace (8 n^2 bytes; PA_LINKAGE_FAST_MAX_GB caps it, default 96: the workspace query
+ * returns 0 for n < 2 or above the cap).  After the kernel the first int of the workspace is 0; anything else means
+ * that a loop bound of the algorithm was exceeded and `raw` is incomplete.  Refused with return code 3, nothing
+ * written: n < 2, unknown method, null pointer, workspace too small, square matrix above the cap. */
+size_t pa_linkage_chain_workspace_bytes(int n);
+int pa_linkage_chain_f64(const double* D, int n, int method, double* raw, void* workspace, size_t workspace_bytes,
+                         void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Frame-domain stages (uint8 hard segmentations in, per-frame decisions out).  Replace the Python
  * loops of Inference.aggregate (core/inference.py:589-611), speaker_count
  * (pipelines/utils/diarization.py:150-185), SpeakerDiarization.reconstruct

@@ -234,6 +234,15 @@ class AgglomerativeClustering(BaseClustering):
             Z = distance.linkage_centroid(embeddings, self.device)
             self.timings.update(pdist=0.0, linkage=time.perf_counter() - t0, num_embeddings=len(embeddings))
             return Z
+        if (self.method in distance.CHAIN_METHODS and self.metric in ("cosine", "euclidean") and on_gpu
+                and len(embeddings) >= 2):
+            # single / complete / average / weighted / ward: pdist, SciPy's finite check and the merge loop on the
+            # device (csrc/linkage_chain.hip); ward on cosine embeddings is geometric (normalised above)
+            metric = "euclidean" if geometric else self.metric
+            Z = distance.linkage_chain(embeddings, self.method, metric, self.device)
+            if Z is not None:    # (None: the square matrix exceeds the cap -> the host path below)
+                self.timings.update(pdist=0.0, linkage=time.perf_counter() - t0, num_embeddings=len(embeddings))
+                return Z
         if geometric or self.metric == "euclidean":
             condensed = distance.pdist_euclidean(embeddings, device=self.device)
             t1 = time.perf_counter()

@@ -1,5 +1,6 @@
-"""float64 distance kernels for clustering: GPU (`pa_pdist_f64`, `pa_cdist_cosine_f64`) with results
-bit-identical to SciPy's `pdist(X, "euclidean")` / `cdist(A, B, "cosine")`.
+"""float64 distance kernels for clustering: GPU (`pa_pdist_f64`, `pa_pdist_cosine_f64`, `pa_cdist_cosine_f64`) with
+results bit-identical to SciPy's `pdist(X, "euclidean")` / `pdist(X, "cosine")` / `cdist(A, B, "cosine")`, and the
+dendrograms on top of them (`linkage_centroid`, `linkage_chain`), bit-identical to SciPy's `linkage`.
 
 SciPy computes Euclidean distances as a sequential-k sum of (u_k - v_k)^2 in double without FMA
 contraction, then sqrt; cosine as 1 - <u,v> / (|u| |v|) with sequential dot products.  The kernels
@@ -141,6 +142,101 @@ def linkage_centroid(X: np.ndarray, device) -> np.ndarray:
 
 last_linkage_stats = None
 last_linkage_phases = None
+
+
+# PA_LINKAGE_* of include/pyannote_amd.h: the methods of csrc/linkage_chain.hip
+# (all five beat the former pdist + download + SciPy path at n = 7 176: profiles/linkage_methods_timing.txt)
+CHAIN_METHODS = {"single": 0, "complete": 1, "average": 2, "weighted": 3, "ward": 4}
+
+
+
+def linkage_finish(raw: np.ndarray, n: int, single: bool = False) -> np.ndarray:
+    """SciPy's dendrogram from the unsorted merge list of `nn_chain` / `mst_single_linkage` (`pa_linkage_chain_f64`):
+    the stable sort of the rows by height, then `_hierarchy.label` -- a union-find over the sorted rows that names
+    every merge by the two current roots of its entries (smaller first), joins them under the new id n + i and
+    recomputes the size column.  `single`: the rows come from the single-linkage kernel, which leaves the fourth
+    column unused and writes 0 there -- anything else means the rows are not what the caller says they are.
+    Host work: O(n log n) plus n - 1 union-find steps."""
+    raw = np.asarray(raw, dtype=np.float64).reshape(n - 1, 4)
+    if single and raw[:, 3].any():
+        raise ValueError("linkage_finish: single-linkage merges carry 0 in their fourth column")
+    Z = raw[np.argsort(raw[:, 2], kind="mergesort")]
+    parent = list(range(2 * n - 1))
+    size = [1] * (2 * n - 1)
+    left, right = Z[:, 0].astype(np.int64).tolist(), Z[:, 1].astype(np.int64).tolist()
+    ids = np.empty((n - 1, 2), dtype=np.float64)
+    sizes = np.empty(n - 1, dtype=np.float64)
+
+    def find(x):
+        root = x
+        while parent[root] != root:
+            root = parent[root]
+        while parent[x] != root:      # path compression
+            parent[x], x = root, parent[x]
+        return root
+
+    for i in range(n - 1):
+        a, b = find(left[i]), find(right[i])
+        if a > b:
+            a, b = b, a
+        ids[i, 0], ids[i, 1] = a, b
+        parent[a] = parent[b] = n + i
+        size[n + i] = size[a] + size[b]
+        sizes[i] = size[n + i]
+    Z[:, :2] = ids
+    Z[:, 3] = sizes
+    return Z
+
+
+@ffi.on_device(lambda X, method, metric, device, raw=None: device)
+def linkage_chain(X: np.ndarray, method: str, metric: str, device, raw: torch.Tensor = None):
+    """scipy.cluster.hierarchy.linkage(pdist(X, metric), method) for method in CHAIN_METHODS and metric "euclidean" or
+    "cosine", on the GPU: float64 pdist (`pa_pdist_f64` / `pa_pdist_cosine_f64`), SciPy's finite check
+    (`pa_nonfinite_flag_f64`) and the persistent merge kernel (`pa_linkage_chain_f64`) without leaving HBM; the
+    32 (n - 1) bytes of the unsorted merge list come back and `linkage_finish` sorts and labels them.  Bit-identical
+    to SciPy.  Returns None when the square copy of the matrix exceeds PA_LINKAGE_FAST_MAX_GB (the caller keeps the
+    host path).  `raw`: see `linkage_chain_condensed`."""
+    n = X.shape[0]
+    if method not in CHAIN_METHODS or metric not in ("euclidean", "cosine") or n < 2:
+        raise ValueError(f"linkage_chain: method {method!r}, metric {metric!r}, {n} points")
+    ffi.require_gpu()
+    lib = ffi.load()
+    ws_bytes = lib.pa_linkage_chain_workspace_bytes(n)
+    if ws_bytes == 0:
+        return None
+    Xd = torch.from_numpy(np.ascontiguousarray(X, dtype=np.float64)).to(device)
+    cond = torch.empty(n * (n - 1) // 2, dtype=torch.float64, device=device)
+    if metric == "cosine":
+        norms = torch.empty(n, dtype=torch.float64, device=device)
+        ffi.check(lib.pa_pdist_cosine_f64(ffi.ptr(Xd), n, X.shape[1], ffi.ptr(cond), ffi.ptr(norms), ffi.stream()),
+                  "pa_pdist_cosine_f64")
+    else:
+        ffi.check(lib.pa_pdist_f64(ffi.ptr(Xd), n, X.shape[1], ffi.ptr(cond), ffi.stream()), "pa_pdist_f64")
+    flag = torch.empty(1, dtype=torch.int32, device=device)
+    ffi.check(lib.pa_nonfinite_flag_f64(ffi.ptr(cond), cond.numel(), ffi.ptr(flag), ffi.stream()),
+              "pa_nonfinite_flag_f64")
+    if int(flag.item()) != 0:
+        # scipy.cluster.hierarchy.linkage validates its condensed input the same way
+        raise ValueError("The condensed distance matrix must contain only finite values.")
+    return linkage_chain_condensed(cond, n, method, device, raw)
+
+
+def linkage_chain_condensed(cond: torch.Tensor, n: int, method: str, device, raw: torch.Tensor = None) -> np.ndarray:
+    """the merge of `linkage_chain` for a finite condensed float64 matrix that already lives on `device` (left
+    intact); `raw`: where the (n - 1, 4) merge list goes on the device (allocated when None)."""
+    lib = ffi.load()
+    if raw is None:
+        raw = torch.empty((n - 1, 4), dtype=torch.float64, device=device)
+    ws = torch.empty(lib.pa_linkage_chain_workspace_bytes(n), dtype=torch.uint8, device=device)
+    ffi.check(lib.pa_linkage_chain_f64(ffi.ptr(cond), n, CHAIN_METHODS[method], ffi.ptr(raw), ffi.ptr(ws), ws.numel(),
+                                       ffi.stream()), "pa_linkage_chain_f64")
+    # the merge list and the status word (first int of the workspace) in ONE synchronising copy
+    packed = torch.cat([raw.reshape(-1), ws[:8].view(torch.float64)]).cpu().numpy()
+    merges, status = packed[:-1], int(packed[-1:].view(np.int32)[0])
+    if status != 0:
+        raise RuntimeError(f"pa_linkage_chain_f64: the merge kernel ended with status {status} "
+                           "(1: chain bound exceeded, 2: no neighbour found, -1: it did not run to its end)")
+    return linkage_finish(merges, n, single=method == "single")
 
 
 @ffi.on_device(lambda A, B, metric="cosine", device=None: device)
