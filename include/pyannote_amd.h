@@ -711,6 +711,31 @@ int pa_det_curve_f64(const double* sorted_keys, const uint8_t* labels, long T, i
                      int32_t* tps, double* thresholds, double* fpr, double* fnr, int64_t* status, void* workspace,
                      size_t workspace_bytes, void* stream);
 
+/* ---- time-based diarization and detection error rates on segments in seconds (pyannote.metrics'
+ *      DiarizationErrorRate / IdentificationErrorRate / DetectionErrorRate, restated: DESIGN.md section 21) ---- */
+
+/* bytes of `ws` below (0: a negative count, or more cuts than the quadratic sort accepts) */
+size_t pa_annot_counts_workspace_bytes(int Nr, int Nh, int Nu);
+/* ref_seg (Nr, 2), hyp_seg (Nh, 2), uem_seg (Nu, 2) fp64 start / end in seconds, in any order; ref_label (Nr),
+ * hyp_label (Nh) int32 in 0..Kr-1 / 0..Kh-1 (a label outside is ignored), 0 <= Kr, Kh <= 64; every N may be 0.
+ * A label is on or off at a time t (overlapping tracks of one label count once).  Evaluated time = the union of
+ * the uem segments, minus, when collar > 0, the intervals (t - collar/2, t + collar/2) around the start and the end
+ * of every reference segment as given, minus, when skip_overlap, every instant at which two reference segments with
+ * different labels are on.  With Nr(t), Nh(t) the numbers of labels on at t and all integrals over the evaluated
+ * time, out, fp64, Kr*Kh + Kr + Kh + 7 values, overwritten:
+ *   cooc (Kr, Kh)   seconds in which reference label i and hypothesis label j are both on
+ *   ref_dur (Kr), hyp_dur (Kh)
+ *   total = int Nr, false_alarm = int max(0, Nh - Nr), missed = int max(0, Nr - Nh), both = int min(Nr, Nh),
+ *   ref_speech = int [Nr > 0], hyp_speech = int [Nh > 0], both_speech = int [Nr > 0 and Nh > 0]
+ * Under a one-to-one mapping pi of hypothesis labels onto reference labels, correct = sum_j cooc[pi(j)][j] and
+ * confusion = both - correct (the identity of pa_der_counts).  Intervals are taken exactly (no 1e-6 rule); the
+ * additions have a fixed order (no floating-point atomics), so results are bit-reproducible, and exact whenever
+ * every boundary is a multiple of one power of two.  The caller refuses NaN and end < start: the kernels stay in
+ * bounds for them but the result is meaningless.  Four launches on `stream`; nothing is copied back. */
+int pa_annot_counts(const double* ref_seg, const int32_t* ref_label, int Nr, int Kr, const double* hyp_seg,
+                    const int32_t* hyp_label, int Nh, int Kh, const double* uem_seg, int Nu, double collar,
+                    int skip_overlap, double* out, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

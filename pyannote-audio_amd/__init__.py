@@ -21,5 +21,6 @@ from .multilabel import MultiLabelSegmentation  # noqa: E402,F401
 from .hook import ArtifactHook, Hooks, ProgressHook, TimingHook  # noqa: E402,F401
 from . import metrics  # noqa: E402,F401
 from . import verification  # noqa: E402,F401
+from . import annotation_metrics  # noqa: E402,F401
 from .metrics import (DiscreteDiarizationErrorRate, diarization_error_rate,  # noqa: E402,F401
                       discrete_diarization_error_rate, optimal_diarization_error_rate)

@@ -1,0 +1,425 @@
+"""Time-based diarization and detection error rates on `Annotation`s in seconds: what the reference's pipelines
+return from `get_metric()` (pipelines/speaker_diarization.py:786, pipelines/voice_activity_detection.py:207) and
+what `pipelines/utils/diarization.py:104-148` maps speakers with.
+
+pyannote.metrics is not a dependency of this package and its source was not at hand where this was written: the
+classes below are a restatement of its published behaviour (as `core.py` is for pyannote.core), unpinned.  The
+contract is the one written down in include/pyannote_amd.h (`pa_annot_counts`) and DESIGN.md section 21, and the
+tests hold it to an independent exact-arithmetic computation (tests/annotation_metrics_truth.py).  Two deliberate
+differences from pyannote.metrics: overlapping tracks of ONE label count once (pyannote.metrics counts them twice;
+the pipelines never produce such tracks), and intervals are taken exactly (no 1e-6 "segment precision" rule: pieces
+of zero length contribute 0, shorter-than-a-microsecond pieces their length).  `MacroAverageFMeasure` follows the
+reference's own class (utils/metric.py:289-377).
+
+`annotation_counts` is the one place the integrals are taken: on a `cuda` device by the kernels of
+csrc/annot_metrics.hip, otherwise (or with more than 64 labels on a side) by a numpy sweep over the same elementary
+intervals.  The names here are this module's own: `metrics.DiarizationErrorRate` is the torchmetrics class."""
+from __future__ import annotations
+
+import warnings
+from typing import Mapping, Optional
+
+import numpy as np
+import torch
+from scipy.optimize import linear_sum_assignment
+
+from . import ffi
+from .core import Annotation
+from .metrics import BaseMetric
+
+MAX_LABELS = 64          # a side's labels travel as one 64-bit mask on the device
+
+_SCALARS = ("total", "false_alarm", "missed", "both", "ref_speech", "hyp_speech", "both_speech")
+
+
+# -------------------------------------------------------------------------------------------------- inputs
+def _rows(annotation) -> tuple:
+    """(labels in `labels()` order, (N, 2) float64 start / end, (N,) int32 label index)"""
+    labels = annotation.labels()
+    index = {label: i for i, label in enumerate(labels)}
+    if hasattr(annotation, "flat_rows"):
+        rows = [(a, b, l) for a, b, _, l in annotation.flat_rows()]
+    else:  # pragma: no cover - pyannote.core's own Annotation
+        rows = [(s.start, s.end, l) for s, _, l in annotation.itertracks(yield_label=True)]
+    seg = np.array([(a, b) for a, b, _ in rows], dtype=np.float64).reshape(-1, 2)
+    lab = np.array([index[l] for _, _, l in rows], dtype=np.int32)
+    return labels, seg, lab
+
+
+def _uem_rows(uem) -> np.ndarray:
+    return np.array([(s.start, s.end) for s in uem], dtype=np.float64).reshape(-1, 2)
+
+
+def _check(name: str, seg: np.ndarray):
+    if np.isnan(seg).any():
+        raise ValueError(f"{name}: a segment boundary is NaN")
+    if (seg[:, 1] < seg[:, 0]).any():
+        raise ValueError(f"{name}: a segment ends before it starts")
+
+
+def _split(reference, uem):
+    """a file mapping as `reference` ("annotation", optional "annotated") -> (annotation, uem)"""
+    if isinstance(reference, Mapping):
+        if uem is None and "annotated" in reference:
+            uem = reference["annotated"]
+        reference = reference["annotation"]
+    return reference, uem
+
+
+def _device(device) -> Optional[torch.device]:
+    if device is None:
+        return None
+    device = torch.device(device)
+    if device.type != "cuda":
+        return None
+    if device.index is None:
+        ffi.require_gpu()
+        device = torch.device("cuda", torch.cuda.current_device())
+    return device
+
+
+# -------------------------------------------------------------------------------------------------- counts
+def _host_counts(ref_seg, ref_lab, Kr, hyp_seg, hyp_lab, Kh, uem_seg, collar, skip_overlap) -> np.ndarray:
+    """The kernel's sums by a numpy sweep: cut the axis at every boundary, mark per elementary interval which
+    labels are on and whether it is evaluated, sum the lengths."""
+    half = 0.5 * collar
+    bounds = np.concatenate([ref_seg.ravel(), ref_seg.ravel() - half, ref_seg.ravel() + half])
+    cuts = np.unique(np.concatenate([bounds if collar > 0 else ref_seg.ravel(), hyp_seg.ravel(), uem_seg.ravel()]))
+    n = max(len(cuts) - 1, 0)
+    out = np.zeros(Kr * Kh + Kr + Kh + len(_SCALARS))
+    if n == 0:
+        return out
+
+    def coverage(seg, columns, width):
+        """(n, width) number of segments of every column that cover every interval"""
+        delta = np.zeros((n + 1, width), dtype=np.int64)
+        np.add.at(delta, (np.searchsorted(cuts, seg[:, 0]), columns), 1)
+        np.add.at(delta, (np.searchsorted(cuts, seg[:, 1]), columns), -1)
+        return np.cumsum(delta, axis=0)[:n]
+
+    R = coverage(ref_seg, ref_lab, Kr) > 0
+    H = coverage(hyp_seg, hyp_lab, Kh) > 0
+    nr, nh = R.sum(axis=1), H.sum(axis=1)
+    evaluated = coverage(uem_seg, np.zeros(len(uem_seg), dtype=np.int64), 1)[:, 0] > 0
+    if collar > 0:
+        b = ref_seg.ravel()
+        around = np.stack([b - half, b + half], axis=1)
+        evaluated &= coverage(around, np.zeros(len(b), dtype=np.int64), 1)[:, 0] == 0
+    if skip_overlap:
+        evaluated &= nr < 2
+    d = np.where(evaluated, np.diff(cuts), 0.0)
+    Rd = R * d[:, None]
+    n0 = Kr * Kh
+    out[:n0] = (Rd.T @ H.astype(np.float64)).ravel()
+    out[n0:n0 + Kr] = Rd.sum(axis=0)
+    out[n0 + Kr:n0 + Kr + Kh] = (H * d[:, None]).sum(axis=0)
+    out[n0 + Kr + Kh:] = [np.sum(w * d) for w in (nr, np.maximum(0, nh - nr), np.maximum(0, nr - nh),
+                                                 np.minimum(nr, nh), nr > 0, nh > 0, (nr > 0) & (nh > 0))]
+    return out
+
+
+def device_counts(ref_seg, ref_lab, Kr, hyp_seg, hyp_lab, Kh, uem_seg, collar, skip_overlap,
+                  device: torch.device) -> torch.Tensor:
+    """`pa_annot_counts` on host arrays: one upload, four launches; -> the (Kr*Kh + Kr + Kh + 7,) float64 device
+    tensor (nothing is copied back here)."""
+    Nr, Nh, Nu = len(ref_seg), len(hyp_seg), len(uem_seg)
+    # one upload: [ref_seg][hyp_seg][uem_seg] float64, then the labels as int32 in the same buffer
+    f64 = np.concatenate([ref_seg.ravel(), hyp_seg.ravel(), uem_seg.ravel()]).astype(np.float64)
+    i32 = np.concatenate([ref_lab, hyp_lab]).astype(np.int32)
+    if len(i32) % 2:
+        i32 = np.concatenate([i32, np.zeros(1, dtype=np.int32)])
+    packed = torch.from_numpy(np.concatenate([f64, i32.view(np.float64)])).to(device)
+    segs, labs = packed[:len(f64)], packed[len(f64):].view(torch.int32)
+    lib = ffi.load()
+    ws_bytes = int(lib.pa_annot_counts_workspace_bytes(Nr, Nh, Nu))
+    if ws_bytes == 0:
+        raise ValueError(f"{Nr} + {Nh} + {Nu} segments are more than the device sort accepts")
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=device)
+    out = torch.empty(Kr * Kh + Kr + Kh + len(_SCALARS), dtype=torch.float64, device=device)
+
+    def at(t, offset, n):
+        return ffi.ptr(t[offset:offset + n]) if n else None
+
+    with torch.cuda.device(device):
+        ffi.check(lib.pa_annot_counts(at(segs, 0, 2 * Nr), at(labs, 0, Nr), Nr, Kr,
+                                      at(segs, 2 * Nr, 2 * Nh), at(labs, Nr, Nh), Nh, Kh,
+                                      at(segs, 2 * (Nr + Nh), 2 * Nu), Nu, float(collar), int(bool(skip_overlap)),
+                                      ffi.ptr(out), ffi.ptr(ws), ws_bytes, ffi.stream()), "pa_annot_counts")
+    return out
+
+
+def annotation_counts(reference: Annotation, hypothesis: Annotation, uem=None, collar: float = 0.0,
+                      skip_overlap: bool = False, device=None, _warn: bool = True) -> dict:
+    """The integrals every class below is made of (include/pyannote_amd.h, `pa_annot_counts`).  Labels are indexed
+    in `labels()` order on each side.  `uem`: a `Timeline`, a list of `Segment`s, or None -- then the evaluated
+    region is the one segment from the earliest start to the latest end over both annotations, with a warning, as
+    pyannote.metrics does.  A `cuda` device runs the kernels; None, `cpu`, or more than 64 labels on a side the
+    numpy sweep.  -> `ref_labels`, `hyp_labels`, float64 numpy `cooc` (Kr, Kh), `ref_dur`, `hyp_dur`, and floats
+    `total`, `false_alarm`, `missed`, `both`, `ref_speech`, `hyp_speech`, `both_speech`."""
+    reference, uem = _split(reference, uem)
+    ref_labels, ref_seg, ref_lab = _rows(reference)
+    hyp_labels, hyp_seg, hyp_lab = _rows(hypothesis)
+    _check("reference", ref_seg)
+    _check("hypothesis", hyp_seg)
+    if not collar >= 0.0:
+        raise ValueError(f"collar must be >= 0, got {collar}")
+    if uem is None:
+        if _warn:       # (`diarization.cooccurrence` means the whole extent)
+            warnings.warn("'uem' was approximated by the union of 'reference' and 'hypothesis' extents.",
+                          UserWarning, stacklevel=2)
+        both = np.concatenate([ref_seg, hyp_seg])
+        uem_seg = np.array([[both[:, 0].min(), both[:, 1].max()]]) if len(both) else np.zeros((0, 2))
+    else:
+        uem_seg = _uem_rows(uem)
+        _check("uem", uem_seg)
+    Kr, Kh = len(ref_labels), len(hyp_labels)
+    dev = _device(device) if Kr <= MAX_LABELS and Kh <= MAX_LABELS else None
+    if dev is not None:
+        flat = device_counts(ref_seg, ref_lab, Kr, hyp_seg, hyp_lab, Kh, uem_seg, collar, skip_overlap,
+                             dev).cpu().numpy()
+    else:
+        flat = _host_counts(ref_seg, ref_lab, Kr, hyp_seg, hyp_lab, Kh, uem_seg, float(collar), bool(skip_overlap))
+    n0 = Kr * Kh
+    counts = {"ref_labels": ref_labels, "hyp_labels": hyp_labels, "cooc": flat[:n0].reshape(Kr, Kh),
+              "ref_dur": flat[n0:n0 + Kr], "hyp_dur": flat[n0 + Kr:n0 + Kr + Kh]}
+    counts.update({name: float(v) for name, v in zip(_SCALARS, flat[n0 + Kr + Kh:])})
+    return counts
+
+
+# ------------------------------------------------------------------------------------------------- mappings
+def optimal_mapping(cooc) -> dict:
+    """{hypothesis index: reference index} of the one-to-one mapping with the largest matched duration, from the
+    (Kr, Kh) `cooc` of `annotation_counts`: `linear_sum_assignment` on the negated (hypothesis, reference) matrix;
+    pairs that never overlap stay unmapped."""
+    together = np.asarray(cooc, dtype=np.float64).T
+    if not together.size:
+        return {}
+    return {int(j): int(i) for j, i in zip(*linear_sum_assignment(-together)) if together[j, i] > 0}
+
+
+def greedy_mapping(cooc) -> dict:
+    """{hypothesis index: reference index}: repeatedly the first maximum, in row-major order of the (hypothesis,
+    reference) matrix, then its row and column are out, while the maximum is > 0."""
+    together = np.array(cooc, dtype=np.float64).T
+    mapping = {}
+    while together.size:
+        j, i = np.unravel_index(np.argmax(together), together.shape)   # (argmax: the first of equal maxima)
+        if not together[j, i] > 0:
+            break
+        mapping[int(j)] = int(i)
+        together[j, :] = -np.inf
+        together[:, i] = -np.inf
+    return mapping
+
+
+# -------------------------------------------------------------------------------------------------- classes
+class _AnnotationMetric(BaseMetric):
+    """what the classes share: the variant (`collar`, `skip_overlap`), where the counting runs (`device`), and the
+    `uem=` keyword of a call"""
+
+    def __init__(self, collar: float = 0.0, skip_overlap: bool = False, device=None, **kwargs):
+        super().__init__(**kwargs)
+        self.collar = collar
+        self.skip_overlap = skip_overlap
+        self.device = device
+
+    def counts(self, reference, hypothesis, uem=None) -> dict:
+        return annotation_counts(reference, hypothesis, uem=uem, collar=self.collar,
+                                 skip_overlap=self.skip_overlap, device=self.device)
+
+
+def _error_rate(components: dict) -> float:
+    """(false alarm + missed detection + confusion) / total; an empty reference gives 0 without errors, else 1"""
+    errors = components["false alarm"] + components["missed detection"] + components["confusion"]
+    total = components["total"]
+    if total == 0:
+        return 0.0 if errors == 0 else 1.0
+    return float(errors / total)
+
+
+class DiarizationErrorRate(_AnnotationMetric):
+    """pyannote.metrics.diarization.DiarizationErrorRate: hypothesis labels are mapped one-to-one onto reference
+    labels so that the matched duration is largest (Hungarian), then
+    (false alarm + missed detection + confusion) / total.  `metric(reference, hypothesis, uem=None)`."""
+
+    _mapper = staticmethod(optimal_mapping)
+
+    @classmethod
+    def metric_name(cls):
+        return "diarization error rate"
+
+    @classmethod
+    def metric_components(cls):
+        return ["total", "correct", "false alarm", "missed detection", "confusion"]
+
+    def _mapping(self, reference, hypothesis, uem=None, mapper=None) -> dict:
+        counts = self.counts(reference, hypothesis, uem=uem)
+        pairs = (mapper or self._mapper)(counts["cooc"])
+        return {counts["hyp_labels"][j]: counts["ref_labels"][i] for j, i in pairs.items()}
+
+    def optimal_mapping(self, reference, hypothesis, uem=None) -> dict:
+        """{hypothesis label: reference label}"""
+        return self._mapping(reference, hypothesis, uem=uem, mapper=optimal_mapping)
+
+    def compute_components(self, reference, hypothesis, uem=None, **kwargs) -> dict:
+        counts = self.counts(reference, hypothesis, uem=uem)
+        cooc = counts["cooc"]
+        # the mapping works on indices: a hypothesis label that is left unmapped is nobody, even when a reference
+        # label carries the same name
+        correct = float(sum(cooc[i, j] for j, i in sorted(self._mapper(cooc).items())))
+        return {"total": counts["total"], "correct": correct, "false alarm": counts["false_alarm"],
+                "missed detection": counts["missed"], "confusion": counts["both"] - correct}
+
+    def compute_metric(self, components):
+        return _error_rate(components)
+
+
+class GreedyDiarizationErrorRate(DiarizationErrorRate):
+    """pyannote.metrics.diarization.GreedyDiarizationErrorRate: the mapping is found greedily (`greedy_mapping`)"""
+
+    _mapper = staticmethod(greedy_mapping)
+
+    def greedy_mapping(self, reference, hypothesis, uem=None) -> dict:
+        """{hypothesis label: reference label}"""
+        return self._mapping(reference, hypothesis, uem=uem, mapper=greedy_mapping)
+
+
+class IdentificationErrorRate(_AnnotationMetric):
+    """pyannote.metrics.identification.IdentificationErrorRate: labels are matched by name, no mapping"""
+
+    @classmethod
+    def metric_name(cls):
+        return "identification error rate"
+
+    @classmethod
+    def metric_components(cls):
+        return ["total", "correct", "false alarm", "missed detection", "confusion"]
+
+    def compute_components(self, reference, hypothesis, uem=None, **kwargs) -> dict:
+        counts = self.counts(reference, hypothesis, uem=uem)
+        column = {label: j for j, label in enumerate(counts["hyp_labels"])}
+        correct = float(sum(counts["cooc"][i, column[label]] for i, label in enumerate(counts["ref_labels"])
+                            if label in column))
+        return {"total": counts["total"], "correct": correct, "false alarm": counts["false_alarm"],
+                "missed detection": counts["missed"], "confusion": counts["both"] - correct}
+
+    def compute_metric(self, components):
+        return _error_rate(components)
+
+
+class DetectionErrorRate(_AnnotationMetric):
+    """pyannote.metrics.detection.DetectionErrorRate: (false alarm + miss) / total on speech / non-speech"""
+
+    @classmethod
+    def metric_name(cls):
+        return "detection error rate"
+
+    @classmethod
+    def metric_components(cls):
+        return ["total", "false alarm", "miss"]
+
+    def compute_components(self, reference, hypothesis, uem=None, **kwargs) -> dict:
+        counts = self.counts(reference, hypothesis, uem=uem)
+        return {"total": counts["ref_speech"], "false alarm": counts["hyp_speech"] - counts["both_speech"],
+                "miss": counts["ref_speech"] - counts["both_speech"]}
+
+    def compute_metric(self, components):
+        errors = components["false alarm"] + components["miss"]
+        if components["total"] == 0:
+            return 0.0 if errors == 0 else 1.0
+        return float(errors / components["total"])
+
+
+class DetectionPrecisionRecallFMeasure(_AnnotationMetric):
+    """pyannote.metrics.detection.DetectionPrecisionRecallFMeasure: the value is the F-measure of detected speech;
+    `compute_metrics()` returns (precision, recall, f)"""
+
+    @classmethod
+    def metric_name(cls):
+        return "F[precision|recall]"
+
+    @classmethod
+    def metric_components(cls):
+        return ["retrieved", "relevant", "relevant retrieved"]
+
+    def __init__(self, collar: float = 0.0, skip_overlap: bool = False, beta: float = 1.0, device=None, **kwargs):
+        super().__init__(collar=collar, skip_overlap=skip_overlap, device=device, **kwargs)
+        self.beta = beta
+
+    def compute_components(self, reference, hypothesis, uem=None, **kwargs) -> dict:
+        counts = self.counts(reference, hypothesis, uem=uem)
+        return {"retrieved": counts["hyp_speech"], "relevant": counts["ref_speech"],
+                "relevant retrieved": counts["both_speech"]}
+
+    def compute_metrics(self, components: Optional[dict] = None) -> tuple:
+        """-> (precision, recall, f) of `components` (default: everything accumulated); a side without speech
+        has precision / recall 1"""
+        if components is None:
+            components = self.accumulated_
+        both = components["relevant retrieved"]
+        precision = 1.0 if components["retrieved"] == 0 else float(both / components["retrieved"])
+        recall = 1.0 if components["relevant"] == 0 else float(both / components["relevant"])
+        if precision + recall == 0.0:
+            return precision, recall, 0.0
+        b2 = self.beta * self.beta
+        return precision, recall, (1.0 + b2) * precision * recall / (b2 * precision + recall)
+
+    def compute_metric(self, components):
+        return self.compute_metrics(components)[2]
+
+
+class MacroAverageFMeasure(BaseMetric):
+    """Mean over `classes` of the detection F-measure of each class by itself (utils/metric.py:289-377): one
+    `DetectionPrecisionRecallFMeasure` per class on the tracks of that class, a component per class."""
+
+    @classmethod
+    def metric_name(cls):
+        return "Macro F-measure"
+
+    def metric_components(self):
+        return self.classes
+
+    def __init__(self, classes: list, collar: float = 0.0, beta: float = 1.0, **kwargs):
+        self.metric_name_ = self.metric_name()
+        self.classes = classes
+        self.components_ = set(self.metric_components())
+        self.collar = collar
+        self.beta = beta
+        self._sub_metrics = {label: DetectionPrecisionRecallFMeasure(collar=collar, beta=beta, **kwargs)
+                             for label in self.classes}
+        self.reset()
+
+    def reset(self):
+        super().reset()
+        for sub_metric in self._sub_metrics.values():
+            sub_metric.reset()
+
+    @staticmethod
+    def _subset(annotation, label) -> Annotation:
+        out = Annotation(uri=getattr(annotation, "uri", None))
+        for segment, track, l in annotation.itertracks(yield_label=True):
+            if l == label:
+                out[segment, track] = l
+        return out
+
+    def compute_components(self, reference, hypothesis, uem=None, **kwargs) -> dict:
+        reference, uem = _split(reference, uem)
+        details = self.init_components()
+        for label, sub_metric in self._sub_metrics.items():
+            details[label] = sub_metric(self._subset(reference, label), self._subset(hypothesis, label), uem=uem,
+                                        **kwargs)
+        return details
+
+    def compute_metric(self, detail: dict):
+        return float(np.mean([detail[label] for label in self.classes]))
+
+    def report(self) -> dict:
+        """{uri: {class: F-measure of that file, ..., "Macro F-measure": ...}, ..., "TOTAL": {class: F-measure
+        over everything accumulated, ...}} (the reference's data frame, as a dict)"""
+        table = {uri: dict(components) for uri, components in self.results_}
+        table["TOTAL"] = {label: abs(sub_metric) for label, sub_metric in self._sub_metrics.items()}
+        table["TOTAL"][self.metric_name_] = abs(self)
+        return table
+
+    def __abs__(self):
+        return float(np.mean([abs(sub_metric) for sub_metric in self._sub_metrics.values()]))

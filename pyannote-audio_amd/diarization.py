@@ -137,41 +137,28 @@ def to_annotation(discrete_diarization: SlidingWindowFeature, min_duration_on: f
                     min_duration_off=min_duration_off)(discrete_diarization)
 
 
-def cooccurrence(a: Annotation, b: Annotation, annotated=None) -> Tuple[list, list, np.ndarray]:
+def cooccurrence(a: Annotation, b: Annotation, annotated=None, device=None) -> Tuple[list, list, np.ndarray]:
     """(labels of a, labels of b, seconds during which label i of `a` and label j of `b` are both on) --
-    the co-occurrence matrix `a * b` of pyannote.core, optionally restricted to the `annotated` regions."""
-    la, lb = a.labels(), b.labels()
-    ia, ib = {l: i for i, l in enumerate(la)}, {l: j for j, l in enumerate(lb)}
-    regions = None if annotated is None else [(r.start, r.end) for r in annotated]
-    tb = [(s.start, s.end, ib[l]) for s, _, l in b.itertracks(yield_label=True)]
-    out = np.zeros((len(la), len(lb)))
-    for s, _, l in a.itertracks(yield_label=True):
-        for start, end, j in tb:
-            lo, hi = max(s.start, start), min(s.end, end)
-            if hi <= lo:
-                continue
-            if regions is None:
-                out[ia[l], j] += hi - lo
-            else:
-                out[ia[l], j] += sum(max(0.0, min(hi, r1) - max(lo, r0)) for r0, r1 in regions)
-    return la, lb, out
+    the co-occurrence matrix `a * b` of pyannote.core, optionally restricted to the `annotated` regions (their
+    union: regions that overlap each other count once, as do overlapping tracks of one label).  One call of `annotation_metrics.annotation_counts` (on `device` when it is a GPU)."""
+    from .annotation_metrics import annotation_counts
+    # (without `annotated` everything counts: the region from the earliest start to the latest end)
+    counts = annotation_counts(a, b, uem=annotated, device=device, _warn=False)
+    return counts["ref_labels"], counts["hyp_labels"], counts["cooc"]
 
 
-def optimal_mapping(reference, hypothesis: Annotation, return_mapping: bool = False):
+def optimal_mapping(reference, hypothesis: Annotation, return_mapping: bool = False, device=None):
     """Hypothesis labels renamed to the reference labels they overlap most with, one-to-one (Hungarian on the
     co-occurrence durations; pairs that never overlap stay unmapped) -- pipelines/utils/diarization.py:104-148,
     which delegates to pyannote.metrics' DiarizationErrorRate().optimal_mapping (not installed: restated,
-    unpinned).  `reference` may be the annotation or a file mapping with "annotation" [and "annotated"]."""
-    from scipy.optimize import linear_sum_assignment
+    unpinned, in `annotation_metrics`).  `reference` may be the annotation or a file mapping with "annotation"
+    [and "annotated"]; `device`: where the co-occurrence is counted (a GPU, or the host)."""
+    from . import annotation_metrics
     annotated = None
     if isinstance(reference, Mapping):
         annotated = reference["annotated"] if "annotated" in reference else None
         reference = reference["annotation"]
-    hyp_labels, ref_labels, together = cooccurrence(hypothesis, reference, annotated)
-    mapping = {}
-    if together.size:
-        for i, j in zip(*linear_sum_assignment(-together)):
-            if together[i, j] > 0:
-                mapping[hyp_labels[i]] = ref_labels[j]
+    hyp_labels, ref_labels, together = cooccurrence(hypothesis, reference, annotated, device=device)
+    mapping = {hyp_labels[i]: ref_labels[j] for i, j in annotation_metrics.optimal_mapping(together.T).items()}
     mapped = hypothesis.rename_labels(mapping=mapping)
     return (mapped, mapping) if return_mapping else mapped

@@ -286,6 +286,9 @@ _OPTIONAL: list[tuple] = [
     ("pa_det_workspace_bytes", [C.c_long], C.c_size_t),
     ("pa_det_curve_f64", [c_fp, c_fp, C.c_long, C.c_int, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, C.c_size_t,
                           c_fp], C.c_int),
+    ("pa_annot_counts_workspace_bytes", [C.c_int, C.c_int, C.c_int], C.c_size_t),
+    ("pa_annot_counts", [c_fp, c_fp, C.c_int, C.c_int, c_fp, c_fp, C.c_int, C.c_int, c_fp, C.c_int, C.c_double,
+                         C.c_int, c_fp, c_fp, C.c_size_t, c_fp], C.c_int),
 ]
 
 

@@ -141,7 +141,9 @@ class MultiLabelSegmentation(Pipeline):
     def get_metric(self):
         raise NotImplementedError(
             "MultiLabelSegmentation.get_metric returns pyannote.metrics' IdentificationErrorRate (or "
-            "MacroAverageFMeasure with fscore=True): pyannote.metrics is not installed and not restated here.")
+            "MacroAverageFMeasure with fscore=True): pyannote.metrics is not installed; its restatements "
+            "`annotation_metrics.IdentificationErrorRate` and `annotation_metrics.MacroAverageFMeasure` are "
+            "available stand-alone.")
 
     def get_direction(self):
         return "maximize" if self.fscore else "minimize"

@@ -439,9 +439,23 @@ class SpeakerDiarization(Pipeline):
 
     def _label_names(self, file, diarization: Annotation, labels: list) -> dict:
         if isinstance(file, Mapping) and "annotation" in file and file["annotation"]:
-            _, mapping = optimal_mapping(file["annotation"], diarization, return_mapping=True)
+            _, mapping = optimal_mapping(file["annotation"], diarization, return_mapping=True,
+                                         device=self._metric_device())
             return {label: mapping.get(label, label) for label in labels}   # extra speakers keep their id
         return dict(zip(labels, self.classes()))
+
+    def _metric_device(self):
+        """where the time-based metrics count: the pipeline's GPU when it runs on one, else the host"""
+        device = getattr(self, "device", None)
+        return device if device is not None and device.type == "cuda" else None
+
+    def get_metric(self):
+        """speaker_diarization.py:786: the metric the pipeline is scored (and tuned) with"""
+        from . import annotation_metrics
+        return annotation_metrics.GreedyDiarizationErrorRate(**self.der_variant, device=self._metric_device())
+
+    def get_direction(self) -> str:
+        return "minimize"
 
     def _speaker_bounds(self, num_speakers, min_speakers, max_speakers, kwargs, file=None):
         """(:565-590) unknown keyword arguments are ignored with a warning; a clustering that needs the

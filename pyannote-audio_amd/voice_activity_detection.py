@@ -55,6 +55,18 @@ class VoiceActivityDetection(Pipeline):
     def classes(self):
         return ["SPEECH"]
 
+    def get_metric(self):
+        """voice_activity_detection.py:207-215"""
+        from . import annotation_metrics
+        device = getattr(self, "device", None)
+        device = device if device is not None and device.type == "cuda" else None
+        if self.fscore:
+            return annotation_metrics.DetectionPrecisionRecallFMeasure(collar=0.0, skip_overlap=False, device=device)
+        return annotation_metrics.DetectionErrorRate(collar=0.0, skip_overlap=False, device=device)
+
+    def get_direction(self) -> str:
+        return "maximize" if self.fscore else "minimize"
+
     def initialize(self):
         self._binarize = Binarize(onset=self.onset, offset=self.offset,
                                   min_duration_on=self.min_duration_on,
