@@ -736,6 +736,52 @@ int pa_annot_counts(const double* ref_seg, const int32_t* ref_label, int Nr, int
                     const int32_t* hyp_label, int Nh, int Kh, const double* uem_seg, int Nu, double collar,
                     int skip_overlap, double* out, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- a corpus of files at once, with the within-speaker gaps of every hypothesis filled on the device (the
+ *      reference's MinDurationOffOptimizer, __main__.py:430-510, evaluates all files again for every candidate gap:
+ *      the turns are uploaded once and only `fill` changes between calls) ---- */
+
+/* The turns of F files, concatenated file after file.  Everything but the h_* tables lies on the DEVICE and is only
+ * read; the h_* tables are HOST copies of the device tables of the same name, from which the call checks the sizes
+ * and sizes its launches before anything runs (the caller keeps both equal: the kernels trust the device tables).
+ * Offsets are int32 with F + 1 entries, offset[0] = 0, file f owns [offset[f], offset[f + 1]).
+ *   ref_seg / hyp_seg / uem_seg   (N, 2) fp64 start / end, as in pa_annot_counts, in any order within a file
+ *   ref_label / hyp_label         int32 label index WITHIN the file, 0..Kr[f]-1 / 0..Kh[f]-1
+ *   cut_off[f + 1] - cut_off[f] = 2 (Nr + Nh + Nu) + 4 Nr of file f (its cuts with a collar and no row merged)
+ *   out_off[f + 1] - out_off[f] = Kr Kh + Kr + Kh + 7 of file f
+ *   run_first                     F + 1: run_first[f] = Kh[0] + .. + Kh[f - 1]; run run_first[f] + j holds the
+ *                                 hypothesis rows of label j of file f; R = run_first[F]
+ *   run_off                       R + 1 offsets into run_rows (a file's runs follow each other, files in order)
+ *   run_rows                      per run, the indices into hyp_seg (rows of ALL files counted from 0) of its rows
+ *                                 sorted by (start, end); every hypothesis row appears once */
+typedef struct {
+  int32_t F, R;
+  const double *ref_seg, *hyp_seg, *uem_seg;
+  const int32_t *ref_label, *hyp_label;
+  const int32_t *ref_off, *hyp_off, *uem_off, *cut_off, *out_off;
+  const int32_t *Kr, *Kh;
+  const int32_t *run_first, *run_off, *run_rows;
+  const int32_t *h_ref_off, *h_hyp_off, *h_uem_off, *h_Kr, *h_Kh;
+} pa_annot_corpus;
+
+/* bytes of `ws` below, from the host tables (0 for what pa_annot_corpus_counts refuses: missing host tables, more
+ * than 65535 files, a K above 64, a file with more cuts than the quadratic sort accepts, R != sum of Kh) */
+size_t pa_annot_corpus_workspace_bytes(const pa_annot_corpus* corpus);
+/* For every file f: replace its hypothesis by `Annotation.support(fill)` of it, then the sums of pa_annot_counts.
+ * support, per label, rows sorted by (start, end), with the current merged turn (a, E) and the next row (c, d), in
+ * float64: lo = min(E, d); the rows MERGE (E = max(E, d)) iff lo - c > 1e-6, or g < fill with g = c - lo taken as 0
+ * unless g > 1e-6; otherwise (a, E) is emitted -- if E - a > 1e-6: a shorter turn is no segment and is dropped, as
+ * an Annotation drops it -- and (c, d) becomes the current turn.  (Strict: touching turns merge
+ * for every fill > 0 and never for fill = 0; E is the largest end of the current turn, not of the label.)
+ * merged_rows (F) int32, device, overwritten: the rows of each supported hypothesis.
+ * out, device, overwritten: at out_off[f] the Kr Kh + Kr + Kh + 7 values of pa_annot_counts for file f, BIT FOR BIT
+ * what pa_annot_counts writes for (the file's reference rows, its supported hypothesis rows in any order, its uem
+ * rows, collar, skip_overlap): the same device functions on the same multiset of cuts.
+ * fill or collar negative or NaN and everything pa_annot_corpus_workspace_bytes answers 0 for are refused before any
+ * launch.  Six launches on `stream` (two when no file has a cut), none waits for another workgroup, no
+ * floating-point atomics, nothing is copied back. */
+int pa_annot_corpus_counts(const pa_annot_corpus* corpus, double fill, double collar, int skip_overlap, double* out,
+                           int32_t* merged_rows, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -9,7 +9,11 @@ tests hold it to an independent exact-arithmetic computation (tests/annotation_m
 differences from pyannote.metrics: overlapping tracks of ONE label count once (pyannote.metrics counts them twice;
 the pipelines never produce such tracks), and intervals are taken exactly (no 1e-6 "segment precision" rule: pieces
 of zero length contribute 0, shorter-than-a-microsecond pieces their length).  `MacroAverageFMeasure` follows the
-reference's own class (utils/metric.py:289-377).
+reference's own class (utils/metric.py:289-377).  `JaccardErrorRate` (the other metric the reference's command line
+offers, __main__.py:46) is restated and unpinned like the rest.
+
+Every class splits into "the counts of a file" and `components_from_counts(counts)`: `evaluation.Corpus` takes the
+counts of all files of a corpus in one device call and hands them to `add_counts`.
 
 `annotation_counts` is the one place the integrals are taken: on a `cuda` device by the kernels of
 csrc/annot_metrics.hip, otherwise (or with more than 64 labels on a side) by a numpy sweep over the same elementary
@@ -179,6 +183,12 @@ def annotation_counts(reference: Annotation, hypothesis: Annotation, uem=None, c
                              dev).cpu().numpy()
     else:
         flat = _host_counts(ref_seg, ref_lab, Kr, hyp_seg, hyp_lab, Kh, uem_seg, float(collar), bool(skip_overlap))
+    return counts_dict(ref_labels, hyp_labels, flat)
+
+
+def counts_dict(ref_labels: list, hyp_labels: list, flat: np.ndarray) -> dict:
+    """the Kr*Kh + Kr + Kh + 7 values of `pa_annot_counts` as the dict `annotation_counts` returns"""
+    Kr, Kh = len(ref_labels), len(hyp_labels)
     n0 = Kr * Kh
     counts = {"ref_labels": ref_labels, "hyp_labels": hyp_labels, "cooc": flat[:n0].reshape(Kr, Kh),
               "ref_dur": flat[n0:n0 + Kr], "hyp_dur": flat[n0 + Kr:n0 + Kr + Kh]}
@@ -227,6 +237,31 @@ class _AnnotationMetric(BaseMetric):
         return annotation_counts(reference, hypothesis, uem=uem, collar=self.collar,
                                  skip_overlap=self.skip_overlap, device=self.device)
 
+    def components_from_counts(self, counts: dict) -> dict:
+        """the components of one file from its `annotation_counts`"""
+        raise NotImplementedError
+
+    def compute_components(self, reference, hypothesis, uem=None, **kwargs) -> dict:
+        return self.components_from_counts(self.counts(reference, hypothesis, uem=uem))
+
+    def add_counts(self, counts: dict, uri: Optional[str] = None, detailed: bool = False):
+        """what `metric(reference, hypothesis, uri=uri)` does after the counting, for counts taken elsewhere
+        (`evaluation.Corpus.counts` takes those of all files in one device call)"""
+        components = self.components_from_counts(counts)
+        components[self.metric_name_] = self.compute_metric(components)
+        self.results_.append((uri or "NA", components))
+        for name in self.components_:
+            self.accumulated_[name] += components[name]
+        return components if detailed else components[self.metric_name_]
+
+    def report(self) -> dict:
+        """{uri: {component: value, ..., metric name: the file's value}, ..., "TOTAL": the same over everything
+        accumulated} (the reference's data frame, as a dict; `MacroAverageFMeasure.report` has the same shape)"""
+        table = {uri: dict(components) for uri, components in self.results_}
+        table["TOTAL"] = dict(self.accumulated_)
+        table["TOTAL"][self.metric_name_] = abs(self)
+        return table
+
 
 def _error_rate(components: dict) -> float:
     """(false alarm + missed detection + confusion) / total; an empty reference gives 0 without errors, else 1"""
@@ -261,8 +296,7 @@ class DiarizationErrorRate(_AnnotationMetric):
         """{hypothesis label: reference label}"""
         return self._mapping(reference, hypothesis, uem=uem, mapper=optimal_mapping)
 
-    def compute_components(self, reference, hypothesis, uem=None, **kwargs) -> dict:
-        counts = self.counts(reference, hypothesis, uem=uem)
+    def components_from_counts(self, counts: dict) -> dict:
         cooc = counts["cooc"]
         # the mapping works on indices: a hypothesis label that is left unmapped is nobody, even when a reference
         # label carries the same name
@@ -284,6 +318,46 @@ class GreedyDiarizationErrorRate(DiarizationErrorRate):
         return self._mapping(reference, hypothesis, uem=uem, mapper=greedy_mapping)
 
 
+class JaccardErrorRate(_AnnotationMetric):
+    """pyannote.metrics.diarization.JaccardErrorRate, restated from its published behaviour like its siblings
+    (unpinned: pyannote.metrics was not at hand).  Speakers are mapped as for `DiarizationErrorRate`
+    (`optimal_mapping`); every reference speaker with speech inside the evaluated region counts once, and its error
+    is 1 when no hypothesis speaker is mapped to it, else (false alarm + missed) / (union) of the pair:
+    fa = hyp_dur[j] - cooc[i, j], miss = ref_dur[i] - cooc[i, j], union = ref_dur[i] + hyp_dur[j] - cooc[i, j].
+    The value is "speaker error" / "speaker count" (0 without a counted speaker).  `collar`, `skip_overlap`, `uem` and
+    `device` as for `DiarizationErrorRate`."""
+
+    @classmethod
+    def metric_name(cls):
+        return "jaccard error rate"
+
+    @classmethod
+    def metric_components(cls):
+        return ["speaker count", "speaker error"]
+
+    def components_from_counts(self, counts: dict) -> dict:
+        cooc, ref_dur, hyp_dur = counts["cooc"], counts["ref_dur"], counts["hyp_dur"]
+        mapped = {i: j for j, i in optimal_mapping(cooc).items()}
+        count, error = 0, 0.0
+        for i in range(len(ref_dur)):
+            if not ref_dur[i] > 0:
+                continue
+            count += 1
+            if i not in mapped:
+                error += 1.0
+                continue
+            j = mapped[i]
+            fa, miss = hyp_dur[j] - cooc[i, j], ref_dur[i] - cooc[i, j]
+            total = ref_dur[i] + hyp_dur[j] - cooc[i, j]
+            error += float((fa + miss) / total)
+        return {"speaker count": count, "speaker error": error}
+
+    def compute_metric(self, components):
+        if components["speaker count"] == 0:
+            return 0.0
+        return float(components["speaker error"] / components["speaker count"])
+
+
 class IdentificationErrorRate(_AnnotationMetric):
     """pyannote.metrics.identification.IdentificationErrorRate: labels are matched by name, no mapping"""
 
@@ -295,8 +369,7 @@ class IdentificationErrorRate(_AnnotationMetric):
     def metric_components(cls):
         return ["total", "correct", "false alarm", "missed detection", "confusion"]
 
-    def compute_components(self, reference, hypothesis, uem=None, **kwargs) -> dict:
-        counts = self.counts(reference, hypothesis, uem=uem)
+    def components_from_counts(self, counts: dict) -> dict:
         column = {label: j for j, label in enumerate(counts["hyp_labels"])}
         correct = float(sum(counts["cooc"][i, column[label]] for i, label in enumerate(counts["ref_labels"])
                             if label in column))
@@ -318,8 +391,7 @@ class DetectionErrorRate(_AnnotationMetric):
     def metric_components(cls):
         return ["total", "false alarm", "miss"]
 
-    def compute_components(self, reference, hypothesis, uem=None, **kwargs) -> dict:
-        counts = self.counts(reference, hypothesis, uem=uem)
+    def components_from_counts(self, counts: dict) -> dict:
         return {"total": counts["ref_speech"], "false alarm": counts["hyp_speech"] - counts["both_speech"],
                 "miss": counts["ref_speech"] - counts["both_speech"]}
 
@@ -346,8 +418,7 @@ class DetectionPrecisionRecallFMeasure(_AnnotationMetric):
         super().__init__(collar=collar, skip_overlap=skip_overlap, device=device, **kwargs)
         self.beta = beta
 
-    def compute_components(self, reference, hypothesis, uem=None, **kwargs) -> dict:
-        counts = self.counts(reference, hypothesis, uem=uem)
+    def components_from_counts(self, counts: dict) -> dict:
         return {"retrieved": counts["hyp_speech"], "relevant": counts["ref_speech"],
                 "relevant retrieved": counts["both_speech"]}
 

@@ -5,7 +5,8 @@ package is importable we re-export it (true drop-in); otherwise these restatemen
 semantics are used (pyannote-core 6.0.1 is not installed in the build / GPU containers).  Only the
 subset the diarization path touches is provided: Segment, SlidingWindow (closest_frame, indexing,
 crop, range_to_segment), SlidingWindowFeature (iteration, extent, crop, numpy protocol), Annotation
-(track insertion, itertracks, labels, rename_labels, support, RTTM)."""
+(track insertion, itertracks, labels, rename_labels, support, RTTM).  `load_rttm` / `load_uem` at the end read RTTM and
+UEM files back, with either package's classes."""
 from __future__ import annotations
 
 import itertools
@@ -450,3 +451,57 @@ if not HAVE_PYANNOTE_CORE:
 
         def __str__(self):
             return "\n".join(f"{s} {t} {l}" for s, t, l in self.itertracks(yield_label=True))
+
+
+# -- RTTM / UEM readers (the wire formats `to_rttm` writes and pyannote.database reads)
+def _numbers(path, number: int, line: str, *fields) -> list:
+    try:
+        values = [float(field) for field in fields]
+    except ValueError:
+        values = [float("nan")]
+    if not all(np.isfinite(values)):
+        raise ValueError(f"{path}:{number}: not a number in {line!r}")
+    return values
+
+
+def load_rttm(path) -> dict:
+    """{uri: Annotation} of an RTTM file: lines `SPEAKER uri 1 start duration <NA> <NA> label <NA> <NA>` (only the
+    first eight fields are required; blank lines and lines starting with `;` are skipped).  Tracks are numbered per
+    file in the order of the lines.  A malformed line raises ValueError."""
+    annotations: dict = {}
+    tracks: dict = {}
+    with open(path, "r") as fp:
+        for number, line in enumerate(fp, 1):
+            fields = line.split()
+            if not fields or fields[0].startswith(";"):
+                continue
+            if fields[0] != "SPEAKER" or len(fields) < 8:
+                raise ValueError(f"{path}:{number}: expected 'SPEAKER uri 1 start duration <NA> <NA> label', "
+                                 f"got {line!r}")
+            start, duration = _numbers(path, number, line, fields[3], fields[4])
+            if duration < 0:
+                raise ValueError(f"{path}:{number}: negative duration in {line!r}")
+            uri = fields[1]
+            if uri not in annotations:
+                annotations[uri], tracks[uri] = Annotation(uri=uri), 0
+            annotations[uri][Segment(start, start + duration), tracks[uri]] = fields[7]
+            tracks[uri] += 1
+    return annotations
+
+
+def load_uem(path) -> dict:
+    """{uri: Timeline} of a UEM file: lines `uri 1 start end`.  A malformed line raises ValueError."""
+    from .metrics import Timeline
+    segments: dict = {}
+    with open(path, "r") as fp:
+        for number, line in enumerate(fp, 1):
+            fields = line.split()
+            if not fields or fields[0].startswith(";"):
+                continue
+            if len(fields) < 4:
+                raise ValueError(f"{path}:{number}: expected 'uri 1 start end', got {line!r}")
+            start, end = _numbers(path, number, line, fields[2], fields[3])
+            if end < start:
+                raise ValueError(f"{path}:{number}: end before start in {line!r}")
+            segments.setdefault(fields[0], []).append(Segment(start, end))
+    return {uri: Timeline(rows, uri=uri) for uri, rows in segments.items()}

@@ -18,6 +18,9 @@
 //                      xor butterfly, four wave partials added as (p0 + p1) + (p2 + p3).  No floating-point atomics:
 //                      the same input gives the same bits, and inputs whose boundaries are dyadic give exact sums.
 //
+// pa_annot_corpus_counts (second half of this file) runs the same four steps for all files of a corpus in one call,
+// after filling the within-label gaps of every hypothesis on the device (k_annot_support).
+//
 // Every rank lies in 0..M-1 whatever the values are (NaN included: its rank is then meaningless, not out of
 // range), a label outside 0..K-1 is ignored, a segment with end < start covers nothing: bad VALUES cannot make a
 // kernel address out of bounds; the Python wrapper refuses them before the launch.
@@ -39,11 +42,12 @@ struct AnnotShape {
 
 // cut layout: [ref start Nr][ref end Nr][hyp start Nh][hyp end Nh][uem start Nu][uem end Nu]
 //             [collar lo 2 Nr][collar hi 2 Nr]   (collar u < Nr: around ref start u; u >= Nr: around ref end u - Nr)
-__global__ __launch_bounds__(ANN_THREADS) void k_annot_cuts(const double* __restrict__ ref_seg,
-                                                            const double* __restrict__ hyp_seg,
-                                                            const double* __restrict__ uem_seg, AnnotShape sh,
-                                                            double half_collar, double* __restrict__ cuts) {
-  const int i = blockIdx.x * ANN_THREADS + threadIdx.x;
+// (the four steps are device functions of the workgroup index `blk`: the one-file kernels below and the corpus
+// kernels further down run the same instructions on a file's arrays, which is what makes their bits equal)
+__device__ __forceinline__ void annot_cuts(int blk, const double* __restrict__ ref_seg,
+                                           const double* __restrict__ hyp_seg, const double* __restrict__ uem_seg,
+                                           const AnnotShape& sh, double half_collar, double* __restrict__ cuts) {
+  const int i = blk * ANN_THREADS + threadIdx.x;
   if (i >= sh.cuts()) return;
   const int Nr = sh.Nr, Nh = sh.Nh, Nu = sh.Nu;
   double v;
@@ -63,10 +67,17 @@ __global__ __launch_bounds__(ANN_THREADS) void k_annot_cuts(const double* __rest
   cuts[i] = v;
 }
 
-__global__ __launch_bounds__(ANN_THREADS) void k_annot_rank(const double* __restrict__ cuts, int M,
-                                                            double* __restrict__ sorted, int* __restrict__ rank) {
+__global__ __launch_bounds__(ANN_THREADS) void k_annot_cuts(const double* __restrict__ ref_seg,
+                                                            const double* __restrict__ hyp_seg,
+                                                            const double* __restrict__ uem_seg, AnnotShape sh,
+                                                            double half_collar, double* __restrict__ cuts) {
+  annot_cuts(blockIdx.x, ref_seg, hyp_seg, uem_seg, sh, half_collar, cuts);
+}
+
+__device__ __forceinline__ void annot_rank(int blk, const double* __restrict__ cuts, int M,
+                                           double* __restrict__ sorted, int* __restrict__ rank) {
   __shared__ double s_c[ANN_THREADS];
-  const int tid = threadIdx.x, i = blockIdx.x * ANN_THREADS + tid;
+  const int tid = threadIdx.x, i = blk * ANN_THREADS + tid;
   const double ci = i < M ? cuts[i] : 0.0;
   int r = 0;
   for (int base = 0; base < M; base += ANN_THREADS) {
@@ -83,6 +94,11 @@ __global__ __launch_bounds__(ANN_THREADS) void k_annot_rank(const double* __rest
     rank[i] = r;
     sorted[r] = ci;
   }
+}
+
+__global__ __launch_bounds__(ANN_THREADS) void k_annot_rank(const double* __restrict__ cuts, int M,
+                                                            double* __restrict__ sorted, int* __restrict__ rank) {
+  annot_rank(blockIdx.x, cuts, M, sorted, rank);
 }
 
 // item t of the sweep -> the cut indices of its start and end, the bit it sets and its kind
@@ -110,13 +126,13 @@ __device__ __forceinline__ void annot_item(int t, const AnnotShape& sh, const in
   }
 }
 
-__global__ __launch_bounds__(ANN_THREADS) void k_annot_intervals(
-    const double* __restrict__ sorted, const int* __restrict__ rank, const int32_t* __restrict__ ref_label,
-    const int32_t* __restrict__ hyp_label, AnnotShape sh, int Kr, int Kh, int skip_overlap,
+__device__ __forceinline__ void annot_intervals(
+    int blk, const double* __restrict__ sorted, const int* __restrict__ rank, const int32_t* __restrict__ ref_label,
+    const int32_t* __restrict__ hyp_label, const AnnotShape& sh, int Kr, int Kh, int skip_overlap,
     unsigned long long* __restrict__ rec_r, unsigned long long* __restrict__ rec_h, double* __restrict__ rec_d) {
   __shared__ unsigned long long s_rbit[ANN_THREADS], s_hbit[ANN_THREADS];
   __shared__ int s_lo[ANN_THREADS], s_hi[ANN_THREADS], s_flag[ANN_THREADS];
-  const int tid = threadIdx.x, k = blockIdx.x * ANN_THREADS + tid;
+  const int tid = threadIdx.x, k = blk * ANN_THREADS + tid;
   const int nint = sh.cuts() - 1, nitems = sh.items();
   unsigned long long r = 0, h = 0;
   int flags = 0;
@@ -148,13 +164,20 @@ __global__ __launch_bounds__(ANN_THREADS) void k_annot_intervals(
   rec_d[k] = evaluated ? sorted[k + 1] - sorted[k] : 0.0;
 }
 
+__global__ __launch_bounds__(ANN_THREADS) void k_annot_intervals(
+    const double* __restrict__ sorted, const int* __restrict__ rank, const int32_t* __restrict__ ref_label,
+    const int32_t* __restrict__ hyp_label, AnnotShape sh, int Kr, int Kh, int skip_overlap,
+    unsigned long long* __restrict__ rec_r, unsigned long long* __restrict__ rec_h, double* __restrict__ rec_d) {
+  annot_intervals(blockIdx.x, sorted, rank, ref_label, hyp_label, sh, Kr, Kh, skip_overlap, rec_r, rec_h, rec_d);
+}
+
 // out: [cooc Kr*Kh][ref_dur Kr][hyp_dur Kh][total, false_alarm, missed, both, ref_speech, hyp_speech, both_speech]
-__global__ __launch_bounds__(ANN_THREADS) void k_annot_reduce(const unsigned long long* __restrict__ rec_r,
-                                                              const unsigned long long* __restrict__ rec_h,
-                                                              const double* __restrict__ rec_d, int nint, int Kr,
-                                                              int Kh, double* __restrict__ out) {
+__device__ __forceinline__ void annot_reduce(int o, const unsigned long long* __restrict__ rec_r,
+                                             const unsigned long long* __restrict__ rec_h,
+                                             const double* __restrict__ rec_d, int nint, int Kr, int Kh,
+                                             double* __restrict__ out) {
   __shared__ double s_part[ANN_THREADS / 64];
-  const int tid = threadIdx.x, o = blockIdx.x;
+  const int tid = threadIdx.x;
   const int ncooc = Kr * Kh;
   // what this workgroup sums: kind 0 cooc (i, j), 1 reference label i, 2 hypothesis label j, 3 + s scalar s
   int kind, i = 0, j = 0;
@@ -187,6 +210,13 @@ __global__ __launch_bounds__(ANN_THREADS) void k_annot_reduce(const unsigned lon
   if (tid == 0) out[o] = (s_part[0] + s_part[1]) + (s_part[2] + s_part[3]);
 }
 
+__global__ __launch_bounds__(ANN_THREADS) void k_annot_reduce(const unsigned long long* __restrict__ rec_r,
+                                                              const unsigned long long* __restrict__ rec_h,
+                                                              const double* __restrict__ rec_d, int nint, int Kr,
+                                                              int Kh, double* __restrict__ out) {
+  annot_reduce(blockIdx.x, rec_r, rec_h, rec_d, nint, Kr, Kh, out);
+}
+
 static bool annot_cut_count(int Nr, int Nh, int Nu, bool collar, long* M) {
   if (Nr < 0 || Nh < 0 || Nu < 0) return false;
   *M = 2 * ((long)Nr + Nh + Nu) + (collar ? 4 * (long)Nr : 0);
@@ -195,6 +225,175 @@ static bool annot_cut_count(int Nr, int Nh, int Nu, bool collar, long* M) {
 
 // workspace: [cuts M f64][sorted M f64][rec_r M u64][rec_h M u64][rec_d M f64][rank M i32]
 static size_t annot_workspace(long M) { return 256 + (size_t)M * (5 * 8 + 4); }
+
+// ------------------------------------------------------------------------------------------------ a corpus
+// F files in one call (pa_annot_corpus_counts).  Stage A fills the within-label gaps of every file's hypothesis
+// (core.Annotation.support) and compacts the merged rows per file; stage B is the four steps above with the file
+// as blockIdx.y.  A file's arrays start at its offsets; its cuts, ranks and interval records at cut_off[f], sized
+// for the UNMERGED rows with a collar, so launches can be sized on the host; the merged row count is read on the
+// device and workgroups beyond it leave at once.
+
+// Timeline.support's rule for the current merged turn (.., E) and the next row (c, d) of the label, rows sorted by
+// (start, end): merge when they intersect by more than the segment precision or the gap between them, taken as 0
+// up to that precision, is < fill.  The float64 operations of core.Annotation.support, in its order.
+__device__ __forceinline__ bool annot_merges(double E, double c, double d, double fill) {
+  const double lo = d < E ? d : E;
+  const double inter = lo - c, g = c - lo;
+  return inter > 1e-6 || (g > 1e-6 ? g : 0.0) < fill;
+}
+
+// One workgroup per file, one wave per run (the rows of one label, listed in sorted order by run_rows).  The wave
+// loads 64 rows at a time, one per lane, and walks them in order with every lane holding the same (a, E): the
+// walk is the definition, the loads are what it would otherwise wait for.  Lane 0 writes the merged rows of the run
+// to tmp_seg at the run's own positions; after the barrier the runs' counts are scanned and the rows copied to the
+// file's first merged[f] hypothesis slots (run after run: any order serves stage B).
+__global__ __launch_bounds__(ANN_THREADS) void k_annot_support(pa_annot_corpus c, double fill,
+                                                               double* __restrict__ tmp_seg,
+                                                               double* __restrict__ m_seg,
+                                                               int32_t* __restrict__ m_lab,
+                                                               int32_t* __restrict__ merged) {
+  __shared__ int s_pre[ANN_MAXK + 1];
+  const int f = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int r0 = c.run_first[f], nrun = min(c.run_first[f + 1] - r0, ANN_MAXK);
+  for (int q = wave; q < nrun; q += ANN_THREADS / 64) {
+    const int base = c.run_off[r0 + q], n = c.run_off[r0 + q + 1] - base;
+    double a = 0.0, E = 0.0;
+    int cnt = 0;
+    // (a turn no longer than the segment precision is not a segment: `annotation[segment] = label` drops it)
+    auto emit = [&]() {
+      if (!(E - a > 1e-6)) return;
+      if (lane == 0) tmp_seg[2 * (long)(base + cnt)] = a, tmp_seg[2 * (long)(base + cnt) + 1] = E;
+      ++cnt;
+    };
+    for (int i0 = 0; i0 < n; i0 += 64) {
+      double cl = 0.0, dl = 0.0;
+      if (i0 + lane < n) {
+        const int row = c.run_rows[base + i0 + lane];
+        cl = c.hyp_seg[2 * (long)row];
+        dl = c.hyp_seg[2 * (long)row + 1];
+      }
+      const int m = min(64, n - i0);
+      for (int j = 0; j < m; ++j) {
+        const double cj = __shfl(cl, j, 64), dj = __shfl(dl, j, 64);
+        if (i0 + j == 0) {
+          a = cj, E = dj;
+        } else if (annot_merges(E, cj, dj, fill)) {
+          E = dj > E ? dj : E;
+        } else {
+          emit();
+          a = cj, E = dj;
+        }
+      }
+    }
+    if (n > 0) emit();
+    if (lane == 0) s_pre[q + 1] = cnt;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    s_pre[0] = 0;
+    for (int q = 0; q < nrun; ++q) s_pre[q + 1] += s_pre[q];
+    merged[f] = s_pre[nrun];
+  }
+  __syncthreads();
+  const int h0 = c.hyp_off[f];
+  for (int q = 0; q < nrun; ++q) {
+    const int src = c.run_off[r0 + q], dst = h0 + s_pre[q], cnt = s_pre[q + 1] - s_pre[q];
+    for (int k = tid; k < cnt; k += ANN_THREADS) {
+      m_seg[2 * (long)(dst + k)] = tmp_seg[2 * (long)(src + k)];
+      m_seg[2 * (long)(dst + k) + 1] = tmp_seg[2 * (long)(src + k) + 1];
+      m_lab[dst + k] = q;
+    }
+  }
+}
+
+__device__ __forceinline__ AnnotShape corpus_shape(const pa_annot_corpus& c, const int32_t* __restrict__ merged,
+                                                   int f, int collar) {
+  return AnnotShape{c.ref_off[f + 1] - c.ref_off[f], merged[f], c.uem_off[f + 1] - c.uem_off[f], collar};
+}
+
+__global__ __launch_bounds__(ANN_THREADS) void k_annot_corpus_cuts(pa_annot_corpus c,
+                                                                   const int32_t* __restrict__ merged,
+                                                                   const double* __restrict__ m_seg, int collar,
+                                                                   double half_collar, double* __restrict__ cuts) {
+  const int f = blockIdx.y;
+  const AnnotShape sh = corpus_shape(c, merged, f, collar);
+  if ((int)blockIdx.x * ANN_THREADS >= sh.cuts()) return;
+  annot_cuts(blockIdx.x, c.ref_seg + 2 * (long)c.ref_off[f], m_seg + 2 * (long)c.hyp_off[f],
+             c.uem_seg + 2 * (long)c.uem_off[f], sh, half_collar, cuts + c.cut_off[f]);
+}
+
+__global__ __launch_bounds__(ANN_THREADS) void k_annot_corpus_rank(pa_annot_corpus c,
+                                                                   const int32_t* __restrict__ merged, int collar,
+                                                                   const double* __restrict__ cuts,
+                                                                   double* __restrict__ sorted,
+                                                                   int* __restrict__ rank) {
+  const int f = blockIdx.y, M = corpus_shape(c, merged, f, collar).cuts();
+  if ((int)blockIdx.x * ANN_THREADS >= M) return;          // (the whole workgroup: no barrier is left waiting)
+  const int o = c.cut_off[f];
+  annot_rank(blockIdx.x, cuts + o, M, sorted + o, rank + o);
+}
+
+__global__ __launch_bounds__(ANN_THREADS) void k_annot_corpus_intervals(
+    pa_annot_corpus c, const int32_t* __restrict__ merged, const int32_t* __restrict__ m_lab, int collar,
+    int skip_overlap, const double* __restrict__ sorted, const int* __restrict__ rank,
+    unsigned long long* __restrict__ rec_r, unsigned long long* __restrict__ rec_h, double* __restrict__ rec_d) {
+  const int f = blockIdx.y;
+  const AnnotShape sh = corpus_shape(c, merged, f, collar);
+  if ((int)blockIdx.x * ANN_THREADS >= sh.cuts() - 1) return;
+  const int o = c.cut_off[f];
+  annot_intervals(blockIdx.x, sorted + o, rank + o, c.ref_label + c.ref_off[f], m_lab + c.hyp_off[f], sh, c.Kr[f],
+                  c.Kh[f], skip_overlap, rec_r + o, rec_h + o, rec_d + o);
+}
+
+__global__ __launch_bounds__(ANN_THREADS) void k_annot_corpus_reduce(
+    pa_annot_corpus c, const int32_t* __restrict__ merged, int collar, const unsigned long long* __restrict__ rec_r,
+    const unsigned long long* __restrict__ rec_h, const double* __restrict__ rec_d, double* __restrict__ out) {
+  const int f = blockIdx.y, Kr = c.Kr[f], Kh = c.Kh[f];
+  if ((int)blockIdx.x >= Kr * Kh + Kr + Kh + ANN_SCALARS) return;
+  const int M = corpus_shape(c, merged, f, collar).cuts(), o = c.cut_off[f];
+  annot_reduce(blockIdx.x, rec_r + o, rec_h + o, rec_d + o, M > 0 ? M - 1 : 0, Kr, Kh, out + c.out_off[f]);
+}
+
+// what the host tables allow: the totals, the largest file's cuts (with the collar asked for) and outputs
+struct CorpusPlan {
+  long NhT, Mt;         // hypothesis rows of all files; cut slots of all files (sized with a collar)
+  int max_cuts, max_out;
+};
+
+static bool annot_corpus_plan(const pa_annot_corpus* c, bool collar, CorpusPlan* p) {
+  if (!c || c->F < 0 || c->F > 65535 || c->R < 0) return false;
+  if (c->F == 0) {
+    *p = CorpusPlan{0, 0, 0, 0};
+    return c->R == 0;
+  }
+  if (!c->h_ref_off || !c->h_hyp_off || !c->h_uem_off || !c->h_Kr || !c->h_Kh) return false;
+  if (c->h_ref_off[0] != 0 || c->h_hyp_off[0] != 0 || c->h_uem_off[0] != 0) return false;
+  long Mt = 0, runs = 0, nout = 0;
+  int max_cuts = 0, max_out = 0;
+  for (int f = 0; f < c->F; ++f) {
+    const long Nr = (long)c->h_ref_off[f + 1] - c->h_ref_off[f], Nh = (long)c->h_hyp_off[f + 1] - c->h_hyp_off[f],
+               Nu = (long)c->h_uem_off[f + 1] - c->h_uem_off[f];
+    const int Kr = c->h_Kr[f], Kh = c->h_Kh[f];
+    if (Nr < 0 || Nh < 0 || Nu < 0 || Kr < 0 || Kr > ANN_MAXK || Kh < 0 || Kh > ANN_MAXK) return false;
+    const long cap = 2 * (Nr + Nh + Nu) + 4 * Nr, M = collar ? cap : cap - 4 * Nr;
+    if (M > ANN_MAX_CUTS) return false;
+    Mt += cap;
+    runs += Kh;
+    const int no = Kr * Kh + Kr + Kh + ANN_SCALARS;
+    nout += no;
+    max_cuts = max(max_cuts, (int)M);
+    max_out = max(max_out, no);
+  }
+  if (Mt > 0x7fffffffL || nout > 0x7fffffffL || runs != c->R) return false;
+  *p = CorpusPlan{(long)c->h_hyp_off[c->F], Mt, max_cuts, max_out};
+  return true;
+}
+
+// workspace: [tmp_seg 2 NhT f64][m_seg 2 NhT f64][cuts Mt f64][sorted Mt f64][rec_r Mt u64][rec_h Mt u64]
+//            [rec_d Mt f64][rank Mt i32][m_lab NhT i32]
+static size_t annot_corpus_workspace(const CorpusPlan& p) {
+  return 256 + (size_t)p.NhT * (4 * 8 + 4) + (size_t)p.Mt * (5 * 8 + 4);
+}
 
 }  // namespace pa
 
@@ -246,6 +445,59 @@ int pa_annot_counts(const double* ref_seg, const int32_t* ref_label, int Nr, int
   hipLaunchKernelGGL(pa::k_annot_reduce, dim3(nout), dim3(pa::ANN_THREADS), 0, s, rec_r, rec_h, rec_d, nint, Kr, Kh,
                      out);
   PA_CHECK_LAUNCH("pa_annot_counts");
+  return 0;
+}
+
+size_t pa_annot_corpus_workspace_bytes(const pa_annot_corpus* corpus) {
+  pa::CorpusPlan p;
+  if (!pa::annot_corpus_plan(corpus, true, &p)) return 0;
+  return pa::annot_corpus_workspace(p);
+}
+
+int pa_annot_corpus_counts(const pa_annot_corpus* corpus, double fill, double collar, int skip_overlap, double* out,
+                           int32_t* merged_rows, void* ws, size_t ws_bytes, void* stream) {
+  PA_REQUIRE(fill >= 0.0, "pa_annot_corpus_counts: fill %g is negative or NaN", fill);
+  PA_REQUIRE(collar >= 0.0, "pa_annot_corpus_counts: collar %g is negative or NaN", collar);
+  const bool with_collar = collar > 0.0;
+  pa::CorpusPlan p;
+  PA_REQUIRE(pa::annot_corpus_plan(corpus, with_collar, &p),
+             "pa_annot_corpus_counts: the host tables are missing or not offsets, more than 65535 files, a file with "
+             "more than %d labels on a side or more than %ld cuts, or R is not the sum of Kh",
+             pa::ANN_MAXK, pa::ANN_MAX_CUTS);
+  const pa_annot_corpus& c = *corpus;
+  if (c.F == 0) return 0;
+  PA_REQUIRE(out && merged_rows && c.ref_off && c.hyp_off && c.uem_off && c.cut_off && c.out_off && c.Kr && c.Kh &&
+                 c.run_first && c.run_off &&
+                 (c.h_ref_off[c.F] == 0 || (c.ref_seg && c.ref_label)) &&
+                 (p.NhT == 0 || (c.hyp_seg && c.run_rows)) && (c.h_uem_off[c.F] == 0 || c.uem_seg),
+             "pa_annot_corpus_counts: null array");
+  PA_REQUIRE(ws && ws_bytes >= pa::annot_corpus_workspace(p),
+             "pa_annot_corpus_counts: workspace of %zu bytes, %zu needed", ws_bytes, pa::annot_corpus_workspace(p));
+  hipStream_t s = (hipStream_t)stream;
+  char* base = (char*)(((uintptr_t)ws + 255) & ~(uintptr_t)255);
+  double* tmp_seg = (double*)base;
+  double* m_seg = tmp_seg + 2 * p.NhT;
+  double* cuts = m_seg + 2 * p.NhT;
+  double* sorted = cuts + p.Mt;
+  unsigned long long* rec_r = (unsigned long long*)(sorted + p.Mt);
+  unsigned long long* rec_h = rec_r + p.Mt;
+  double* rec_d = (double*)(rec_h + p.Mt);
+  int* rank = (int*)(rec_d + p.Mt);
+  int32_t* m_lab = rank + p.Mt;
+  const int col = with_collar ? 1 : 0;
+  pa::ProfScope prof("k_annot_corpus_counts", stream, 0.0, 44.0 * p.Mt + 68.0 * p.NhT);
+  const dim3 block(pa::ANN_THREADS);
+  hipLaunchKernelGGL(pa::k_annot_support, dim3(c.F), block, 0, s, c, fill, tmp_seg, m_seg, m_lab, merged_rows);
+  if (p.max_cuts > 1) {
+    const dim3 grid(pa::cdiv(p.max_cuts, pa::ANN_THREADS), c.F);
+    hipLaunchKernelGGL(pa::k_annot_corpus_cuts, grid, block, 0, s, c, merged_rows, m_seg, col, 0.5 * collar, cuts);
+    hipLaunchKernelGGL(pa::k_annot_corpus_rank, grid, block, 0, s, c, merged_rows, col, cuts, sorted, rank);
+    hipLaunchKernelGGL(pa::k_annot_corpus_intervals, dim3(pa::cdiv(p.max_cuts - 1, pa::ANN_THREADS), c.F), block, 0,
+                       s, c, merged_rows, m_lab, col, skip_overlap ? 1 : 0, sorted, rank, rec_r, rec_h, rec_d);
+  }
+  hipLaunchKernelGGL(pa::k_annot_corpus_reduce, dim3(p.max_out, c.F), block, 0, s, c, merged_rows, col, rec_r, rec_h,
+                     rec_d, out);
+  PA_CHECK_LAUNCH("pa_annot_corpus_counts");
   return 0;
 }
 

@@ -116,6 +116,14 @@ class XvecMfccWeights(C.Structure):
     ]
 
 
+class AnnotCorpus(C.Structure):
+    """pa_annot_corpus (include/pyannote_amd.h): device arrays and tables, then host copies of five tables"""
+    _fields_ = [("F", C.c_int32), ("R", C.c_int32)] + \
+               [(n, c_fp) for n in ("ref_seg", "hyp_seg", "uem_seg", "ref_label", "hyp_label", "ref_off", "hyp_off",
+                                    "uem_off", "cut_off", "out_off", "Kr", "Kh", "run_first", "run_off", "run_rows",
+                                    "h_ref_off", "h_hyp_off", "h_uem_off", "h_Kr", "h_Kh")]
+
+
 class LibraryNotBuilt(RuntimeError):
     pass
 
@@ -289,6 +297,9 @@ _OPTIONAL: list[tuple] = [
     ("pa_annot_counts_workspace_bytes", [C.c_int, C.c_int, C.c_int], C.c_size_t),
     ("pa_annot_counts", [c_fp, c_fp, C.c_int, C.c_int, c_fp, c_fp, C.c_int, C.c_int, c_fp, C.c_int, C.c_double,
                          C.c_int, c_fp, c_fp, C.c_size_t, c_fp], C.c_int),
+    ("pa_annot_corpus_workspace_bytes", [C.POINTER(AnnotCorpus)], C.c_size_t),
+    ("pa_annot_corpus_counts", [C.POINTER(AnnotCorpus), C.c_double, C.c_double, C.c_int, c_fp, c_fp, c_fp, C.c_size_t,
+                                c_fp], C.c_int),
 ]
 
 
