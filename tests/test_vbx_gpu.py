@@ -44,15 +44,40 @@ def test_plda_transform_matches_oracle(plda_dir, gpu_device):
     assert np.abs(got - want).max() <= 1e-11 * np.abs(want).max()
 
 
-@pytest.mark.parametrize("C,K,noise,seed,kw", [
+DEFAULT_PARAMS = {"threshold": 0.6, "Fa": 0.07, "Fb": 0.8}
+#: (chunks, speakers, noise, seed, kw); kw["params"]: hyper-parameters other than DEFAULT_PARAMS, towards both corners
+#: of Fa / Fb (4 clusters kept in 3 iterations; 5 clusters collapsing into 1 over 16 iterations)
+CASES = [
     (400, 4, 0.9, 0, {}), (900, 7, 1.2, 1, {}), (250, 3, 0.8, 2, {"num_clusters": 5}),
-    (300, 5, 1.0, 3, {"max_clusters": 2}), (60, 2, 0.7, 4, {})])
+    (300, 5, 1.0, 3, {"max_clusters": 2}), (60, 2, 0.7, 4, {}),
+    (300, 4, 0.3, 5, {"params": {"threshold": 0.6, "Fa": 0.4, "Fb": 0.05}}),
+    (350, 5, 0.45, 5, {"params": {"threshold": 0.6, "Fa": 0.02, "Fb": 12.0}})]
+
+
+def oracle_elbos(emb, seg, plda, threshold, Fa, Fb):
+    """ELBO after every iteration of the oracle's cluster_vbx on these embeddings: the front of
+    oracle.vbx.vbx_clustering (filter, centroid-linkage cut, PLDA projection) up to the VB loop"""
+    from scipy.cluster.hierarchy import fcluster, linkage
+    from oracle.pipeline import filter_embeddings
+    from oracle.vbx import cluster_vbx
+    train, _, _ = filter_embeddings(emb, seg)
+    normed = train / np.linalg.norm(train, axis=1, keepdims=True)
+    ahc = fcluster(linkage(normed, method="centroid", metric="euclidean"), threshold, criterion="distance") - 1
+    _, ahc = np.unique(ahc, return_inverse=True)
+    _, _, Li = cluster_vbx(ahc, plda(train), plda.phi, Fa=Fa, Fb=Fb, maxIters=20)
+    return [float(e[0]) for e in Li]
+
+
+@pytest.mark.parametrize("C,K,noise,seed,kw", CASES)
 def test_vbx_clustering_matches_oracle(plda_dir, gpu_device, C, K, noise, seed, kw):
+    """Also the ELBO-driven stop: the driver runs as many VB iterations as the oracle.  Checked on the CPU
+    (tests/test_vbx_truth_cpu.py::test_driver_cases_stop_off_the_knife_edge) that no case sits on a knife edge: no
+    consecutive ELBO difference of the oracle lies within 1e-8 of the 1e-4 threshold (the nearest is 3.1e-5 away)."""
     import pyannote_audio_amd as pa
     from pyannote_audio_amd.core import SlidingWindow, SlidingWindowFeature
     from oracle.vbx import PLDA as OraclePLDA, vbx_clustering
     emb, seg = _embeddings(C, K, noise, seed)
-    params = {"threshold": 0.6, "Fa": 0.07, "Fb": 0.8}
+    params = kw.get("params", DEFAULT_PARAMS)
     clu = pa.VBxClustering(plda=plda_dir).instantiate(params).to(gpu_device)
     chunks = SlidingWindow(start=0.0, duration=10.0, step=1.0)
     hard, soft, cen = clu(embeddings=emb.copy(), segmentations=SlidingWindowFeature(seg, chunks),
@@ -67,9 +92,10 @@ def test_vbx_clustering_matches_oracle(plda_dir, gpu_device, C, K, noise, seed, 
     assert np.allclose(cen, rc, rtol=1e-9, atol=1e-12)
     assert np.array_equal(hard, rh)
     assert np.allclose(soft, rs, rtol=1e-9, atol=1e-12, equal_nan=True)
+    assert clu.timings["vbx_iterations"] == len(oracle_elbos(emb.copy(), seg, ref, **params))
     with open("gpurun_out/parity.log", "a") as fp:
-        fp.write(f"vbx[C={C},K={K}]: {cen.shape[0]} speakers, {clu.timings.get('vbx_iterations')} VB "
-                 f"iterations, max|dcentroid| = {np.abs(cen - rc).max():.2e}\n")
+        fp.write(f"vbx[C={C},K={K},Fa={params['Fa']},Fb={params['Fb']}]: {cen.shape[0]} speakers, "
+                 f"{clu.timings.get('vbx_iterations')} VB iterations, max|dcentroid| = {np.abs(cen - rc).max():.2e}\n")
 
 
 def test_pipeline_with_vbx_clustering(tmp_path, synthetic_models, plda_dir, gpu_device):
