@@ -782,6 +782,36 @@ size_t pa_annot_corpus_workspace_bytes(const pa_annot_corpus* corpus);
 int pa_annot_corpus_counts(const pa_annot_corpus* corpus, double fill, double collar, int skip_overlap, double* out,
                            int32_t* merged_rows, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- every flat cut of one dendrogram (scipy.cluster.hierarchy.fcluster(Z, t, "distance") for many t: what tuning
+ *      `clustering.threshold` on a corpus asks for, __main__.py:116-283) ---- */
+
+/* HOST function, once per dendrogram.  Z: (n - 1, 4) float64 SciPy linkage matrix in host memory, 2 <= n <= 2^30.
+ * Nodes 0..n-1 are the leaves, n + i is merge i.  With MD[i] the largest height in the subtree of merge i (SciPy's
+ * get_max_dist_for_each_cluster), own_md = MD for a merge and -inf for a leaf, parent_md = own_md of the parent and
+ * +inf for the root, the outputs (host, written in full) list the 2n - 1 nodes by their slot on the timeline on
+ * which SciPy's cluster_monocrit hands out cluster numbers -- a merge when the depth-first walk (left internal child,
+ * then right internal child) enters it, a leaf when the walk leaves its parent, left leaf before right leaf:
+ *   tl_own, tl_parent (2n - 1) float64;  tl_lo (2n - 1) int32 = first position of the node's leaves in left-first leaf
+ *   order;  leaf_lo (n) int32 = the position of leaf l.  Every position lies in 0..n-1.
+ * No recursion (a chain is n - 1 deep).  Returns 3 when Z is no tree (a child id that is no integer, out of range,
+ * not yet formed or used twice). */
+int pa_dendrogram_plan(const double* Z, int n, double* tl_own, double* tl_parent, int32_t* tl_lo, int32_t* leaf_lo);
+/* thresholds per launch of pa_dendrogram_cuts; a longer list is cut in several launches */
+int pa_dendrogram_cuts_chunk(void);
+/* bytes of `ws` below: one int32 row of n positions per threshold of a launch (0: n or T out of range) */
+size_t pa_dendrogram_cuts_workspace_bytes(int n, long T);
+/* The four plan arrays on the DEVICE, thresholds (T) float64 on the device, none NaN (the caller checks).
+ * labels (T, n) int32, row k = fcluster(Z, thresholds[k], "distance") - 1, numbering included; num_clusters (T) int32.
+ * Node v starts a flat cluster iff own_md[v] <= t < parent_md[v] (float64 comparisons; a threshold of +inf counts as
+ * the largest finite double, so that the root, whose parent_md is +inf, starts the one cluster); its number is the inclusive
+ * prefix sum of those flags along the timeline, written at tl_lo; a second scan over the leaf positions ("last
+ * non-zero wins") carries it across the node's leaves.  One workgroup per threshold, O(n) each, no atomics, no
+ * workgroup waits for another; `ws` may be smaller than pa_dendrogram_cuts_workspace_bytes says (at least one row):
+ * the launches then take fewer thresholds each.  Nothing is copied back. */
+int pa_dendrogram_cuts(const double* tl_own, const double* tl_parent, const int32_t* tl_lo, const int32_t* leaf_lo,
+                       int n, const double* thresholds, long T, int32_t* labels, int32_t* num_clusters, void* ws,
+                       size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -19,6 +19,9 @@ What runs where
                                  EVERY merge from one O(N) scan of the merge sizes, which turns the
                                  reference's forced-number search (one `fcluster` per candidate cut,
                                  clustering.py:405-451) into a lookup + ONE `fcluster`
+                               * `Dendrogram.cuts`: every candidate cut of one tree from one plan (built on
+                                 the host by `pa_dendrogram_plan`), on a GPU by `pa_dendrogram_cuts` -- what
+                                 tuning the threshold on a corpus asks for (tuning.py)
 Arithmetic contract: embeddings are float32; the AHC training copy is
 L2-normalised in float32; distances are float64 with SciPy's summation order; centroids are float32 row
 sums in row order divided in float32.  Cluster ids are bit-identical to the reference's given identical
@@ -90,6 +93,74 @@ class Dendrogram:
         ranked = self.Z.copy()
         ranked[:, 2] = np.arange(self.num_leaves - 1)
         return fcluster(ranked, index, criterion="distance") - 1
+
+    def plan(self) -> Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
+        """what every cut of this tree shares (`pa_dendrogram_plan`, csrc/dendrogram_plan.h; built once): the nodes
+        in the order in which SciPy hands out cluster numbers, each with the largest height of its subtree (-inf for a
+        leaf), that of its parent (+inf for the root) and the first position of its leaves in left-first leaf order;
+        and the position of every leaf."""
+        cached = self.__dict__.get("_plan")
+        if cached is None:
+            from . import ffi
+            n = self.num_leaves
+            Z = np.ascontiguousarray(self.Z, dtype=np.float64)
+            own, parent = np.empty(2 * n - 1), np.empty(2 * n - 1)
+            lo, leaf_lo = np.empty(2 * n - 1, dtype=np.int32), np.empty(n, dtype=np.int32)
+            ffi.check(ffi.load().pa_dendrogram_plan(Z.ctypes.data, n, own.ctypes.data, parent.ctypes.data,
+                                                    lo.ctypes.data, leaf_lo.ctypes.data), "pa_dendrogram_plan")
+            cached = self._plan = (own, parent, lo, leaf_lo)
+        return cached
+
+    def cuts(self, heights, device=None) -> np.ndarray:
+        """(T, n) int32: row k = `fcluster(Z, heights[k], "distance") - 1`, numbering included, for all heights at
+        once.  On a GPU `device`: `pa_dendrogram_cuts` (csrc/dendrogram.hip; the plan is uploaded once per tree and
+        device); `device` None or the host: the same plan through numpy.  `last_num_clusters` (T) = clusters per row."""
+        heights = np.ascontiguousarray(np.atleast_1d(np.asarray(heights, dtype=np.float64)).reshape(-1))
+        if np.isnan(heights).any():
+            raise ValueError("Dendrogram.cuts: a threshold is NaN")
+        # (the root has no parent: its `parent_md` is +inf, which a threshold of +inf must still lie under)
+        heights = np.minimum(heights, np.finfo(np.float64).max)
+        T, n = len(heights), self.num_leaves
+        if n == 1 or T == 0:
+            self.last_num_clusters = np.ones(T, dtype=np.int32)
+            return np.zeros((T, n), dtype=np.int32)
+        if getattr(device, "type", None) == "cuda":
+            return self._cuts_on_device(heights, device)
+        own, parent, lo, leaf_lo = self.plan()
+        labels = np.empty((T, n), dtype=np.int32)
+        counts = np.empty(T, dtype=np.int32)
+        positions = np.arange(n)
+        for k, t in enumerate(heights):
+            starts = np.nonzero((own <= t) & (t < parent))[0]          # in timeline order: cluster k + 1 is starts[k]
+            numbers = np.zeros(n, dtype=np.int32)
+            numbers[lo[starts]] = np.arange(1, len(starts) + 1)
+            # "last non-zero wins" prefix scan: every position takes the number at the latest start before it
+            latest = np.maximum.accumulate(np.where(numbers > 0, positions, 0))
+            labels[k] = numbers[latest][leaf_lo] - 1
+            counts[k] = len(starts)
+        self.last_num_clusters = counts
+        return labels
+
+    def _cuts_on_device(self, heights: np.ndarray, device) -> np.ndarray:
+        from . import ffi
+        ffi.require_gpu()
+        lib = ffi.load()
+        T, n = len(heights), self.num_leaves
+        with torch.cuda.device(device):
+            key = (device.type, torch.cuda.current_device() if device.index is None else device.index)
+            cache = self.__dict__.setdefault("_device_plans", {})
+            if key not in cache:
+                cache[key] = tuple(torch.from_numpy(a).to(device) for a in self.plan())
+            own, parent, lo, leaf_lo = cache[key]
+            t_dev = torch.from_numpy(heights).to(device)
+            labels = torch.empty((T, n), dtype=torch.int32, device=device)
+            counts = torch.empty(T, dtype=torch.int32, device=device)
+            ws = torch.empty(lib.pa_dendrogram_cuts_workspace_bytes(n, T), dtype=torch.uint8, device=device)
+            ffi.check(lib.pa_dendrogram_cuts(ffi.ptr(own), ffi.ptr(parent), ffi.ptr(lo), ffi.ptr(leaf_lo), n,
+                                             ffi.ptr(t_dev), T, ffi.ptr(labels), ffi.ptr(counts), ffi.ptr(ws),
+                                             ws.numel(), ffi.stream()), "pa_dendrogram_cuts")
+            self.last_num_clusters = counts.cpu().numpy()
+            return labels.cpu().numpy()
 
     def large_cluster_counts(self, min_size: int) -> np.ndarray:
         """counts[i] = number of clusters with >= min_size members after merges 0..i."""
@@ -273,9 +344,19 @@ class AgglomerativeClustering(BaseClustering):
         n = embeddings.shape[0]
         if n == 1:
             return np.zeros((1,), dtype=np.uint8)
-        min_size = min(self.min_cluster_size, max(1, round(0.1 * n)))
         tree = Dendrogram(self.dendrogram(embeddings))
-        labels = tree.cut(self.threshold)
+        return self.cluster_from_cut(embeddings, tree, tree.cut(self.threshold), min_clusters=min_clusters,
+                                     max_clusters=max_clusters, num_clusters=num_clusters)
+
+    def cluster_from_cut(self, embeddings: np.ndarray, tree: Dendrogram, labels: np.ndarray,
+                         min_clusters: Optional[int] = None, max_clusters: Optional[int] = None,
+                         num_clusters: Optional[int] = None):
+        """the rest of `cluster` once `tree` = the dendrogram of `embeddings` and `labels` = its cut at
+        `self.threshold` are known (:390-476): the size test, the forced-number walk and the reassignment of the small
+        clusters.  `embeddings` is the copy the tree was built from (normalised by `dendrogram` for the geometric
+        methods: the small-cluster centroids are its means)."""
+        n = embeddings.shape[0]
+        min_size = min(self.min_cluster_size, max(1, round(0.1 * n)))
         sizes = np.bincount(labels)
         num_large = int((sizes >= min_size).sum())
         # a bound that the threshold cut violates becomes the target (:394-403)

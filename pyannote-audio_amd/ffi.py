@@ -300,6 +300,11 @@ _OPTIONAL: list[tuple] = [
     ("pa_annot_corpus_workspace_bytes", [C.POINTER(AnnotCorpus)], C.c_size_t),
     ("pa_annot_corpus_counts", [C.POINTER(AnnotCorpus), C.c_double, C.c_double, C.c_int, c_fp, c_fp, c_fp, C.c_size_t,
                                 c_fp], C.c_int),
+    ("pa_dendrogram_plan", [c_fp, C.c_int, c_fp, c_fp, c_fp, c_fp], C.c_int),
+    ("pa_dendrogram_cuts_chunk", [], C.c_int),
+    ("pa_dendrogram_cuts_workspace_bytes", [C.c_int, C.c_long], C.c_size_t),
+    ("pa_dendrogram_cuts", [c_fp, c_fp, c_fp, c_fp, C.c_int, c_fp, C.c_long, c_fp, c_fp, c_fp, C.c_size_t, c_fp],
+     C.c_int),
 ]
 
 

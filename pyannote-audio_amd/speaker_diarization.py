@@ -24,8 +24,8 @@ import os
 import textwrap
 import time
 import warnings
-from dataclasses import dataclass, field
-from typing import Any, Callable, Iterable, Iterator, List, Mapping, Optional, Tuple
+from dataclasses import dataclass, field, replace
+from typing import Any, Callable, Iterable, Iterator, List, Mapping, MutableMapping, Optional, Tuple
 
 import numpy as np
 import torch
@@ -79,7 +79,28 @@ class _FrontEnd:
     enqueued: dict = field(default_factory=dict)   # host clock when a stage's launches were all queued
 
 
+class _TrainingFile(dict):
+    """The validated copy of a file dict (`Audio.validate_file` copies) while `pipeline.training` is set: what is
+    stored under `training_cache/...` also goes into the caller's own dict, where the next trial finds it."""
+
+    def __init__(self, validated: Mapping, origin: MutableMapping):
+        super().__init__(validated)
+        self._origin = origin
+
+    def __setitem__(self, key, value):
+        super().__setitem__(key, value)
+        if isinstance(key, str) and key.startswith("training_cache/"):
+            self._origin[key] = value
+
+
 class SpeakerDiarization(Pipeline):
+    # While `training` is set (hyper-parameter search: the same files again and again) `apply` keeps what the front end
+    # produced in the file dict, under the reference's keys (speaker_diarization.py:301-330, 357-370, 465-476), and a
+    # later call reuses it; a third key of this package's own keeps the `_FrontEnd` whose tensors are still in HBM.
+    CACHED_SEGMENTATION = "training_cache/segmentation"      # SlidingWindowFeature as the model gave it
+    CACHED_EMBEDDINGS = "training_cache/embeddings"          # {"embeddings": (C, S, D)[, "segmentation.threshold"]}
+    CACHED_FRONT_END = "training_cache/front_end"            # _FrontEnd (dev_seg, dev_emb, count, active, clean)
+
     # pipelined batches: longest wait (s) of a file's tail for the next file's segmentation stage (a safety net:
     # the gate is opened in a `finally`)
     TAIL_GATE_TIMEOUT = 5.0
@@ -373,6 +394,42 @@ class SpeakerDiarization(Pipeline):
         hook("embeddings", front.embeddings)
         return front
 
+    # --------------------------------------------------------------------------- training cache
+    def prepare_one(self, file: AudioFile, preload: bool = False) -> Mapping:
+        prepared = super().prepare_one(file, preload=preload)
+        if self.training and isinstance(file, MutableMapping) and prepared is not file:
+            return _TrainingFile(prepared, file)
+        return prepared
+
+    def _cached_front_end(self, file: MutableMapping, hook: Callable) -> _FrontEnd:
+        """`_front_end` while `training` is set: the cached one when the file dict has it and the reference's rule
+        allows it (a powerset model always, otherwise only while `segmentation.threshold` is what the embeddings
+        were extracted with) -- neither network runs then -- else a fresh one, which is stored."""
+        powerset = self._segmentation.model.specifications.powerset
+        cached = file.get(self.CACHED_FRONT_END)
+        embeddings = file.get(self.CACHED_EMBEDDINGS, {})
+        if isinstance(cached, _FrontEnd) and self.CACHED_SEGMENTATION in file \
+                and (cached.embeddings is None or "embeddings" in embeddings) \
+                and (powerset or embeddings.get("segmentation.threshold") == self.segmentation.threshold):
+            front = replace(cached, file=file, marks=[("start", time.perf_counter())], enqueued={})
+            hook("segmentation", front.segmentations)
+            hook("speaker_counting", front.count)
+            if front.embeddings is not None:
+                hook("embeddings", front.embeddings)
+            return front
+        front = self._front_end(file, hook)
+        raw = front.segmentations
+        if front.dev_scores is not None:       # (the reference caches the scores, not their binarized form)
+            raw = SlidingWindowFeature(front.dev_scores.cpu().numpy(), front.chunks)
+        file[self.CACHED_SEGMENTATION] = raw
+        if front.embeddings is not None:
+            entry = {"embeddings": front.embeddings}
+            if not powerset:
+                entry = {"segmentation.threshold": self.segmentation.threshold, **entry}
+            file[self.CACHED_EMBEDDINGS] = entry
+        file[self.CACHED_FRONT_END] = replace(front, file=None, marks=[], enqueued={})
+        return front
+
     # ----------------------------------------------------------------------------------- back end
     def _empty_output(self, file: dict):
         output = DiarizeOutput(speaker_diarization=Annotation(uri=file["uri"]),
@@ -480,7 +537,7 @@ class SpeakerDiarization(Pipeline):
                                                                         max_speakers, kwargs, file=file)
         hook = self.setup_hook(file, hook=hook)
         self._require_device()
-        front = self._front_end(file, hook)
+        front = self._cached_front_end(file, hook) if self.training else self._front_end(file, hook)
         if front.silent:
             return self._empty_output(file)
         with distance.device_to_ourselves():      # one file on its own: no front end runs beside its clustering
