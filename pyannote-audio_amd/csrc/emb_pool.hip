@@ -259,7 +259,9 @@ constexpr int POOLR_LONG_LDS = 144 * 1024;   // bytes of weights k_stats_pool_ro
 
 // calibration of the Winograd paths (pa_emb_calibrate_winograd): out[0] = max(out[0], max |ref|),
 // out[1] = max(out[1], max |got - ref|) over n floats.  Non-negative floats order like their bit patterns, so the
-// cross-workgroup maximum is an integer atomicMax; NaN in `got` counts as +inf.
+// cross-workgroup maximum is an integer atomicMax; NaN in `got` counts as +inf.  So does every other difference that
+// is not a number or not finite (+-inf in `got`, NaN in `ref`, inf on both sides); max |ref| is taken over the elements
+// of `ref` that are not NaN (fmaxf drops a NaN operand).
 __global__ __launch_bounds__(256) void k_absmax_diff(const float* __restrict__ got, const float* __restrict__ ref,
                                                      long n, float* __restrict__ out) {
   float mr = 0.f, md = 0.f;
