@@ -1,0 +1,126 @@
+// Integer geometry of the stride-2 3x3 convolution kernel (csrc/emb_conv_s2.hip): the LDS images and their bank
+// swizzle, the per-lane LDS-DMA source offsets, the fragment read addresses and the piece counts the kernel's waits
+// and issue slots are built from.  No HIP types: the header is also compiled for the HOST by
+// tests/test_conv_s2_geometry_cpu.py (tests/native/conv_s2_geom_harness.cpp), which replays the DMA of every piece and
+// lane and the fragment reads of every wave, lane and tap and checks that they agree and that the reads are
+// conflict-free under the hardware's lane-group rule.
+// Needs: __device__, __forceinline__.
+#pragma once
+
+namespace pa {
+
+constexpr int CS2_CB = 16;    // input channels per stage
+constexpr int CS2_BN = 64;    // output channels per workgroup
+constexpr int CS2_OOB = (int)0x80000000;   // a lane offset past every descriptor: the DMA writes zeros
+
+// A workgroup of 4 waves owns TH x (32 TWT) output pixels x 64 output channels; wave w owns the 32-pixel M-tile
+// mt = w (row mt / TWT, columns 32 (mt % TWT) ...) and BOTH 32-channel N-tiles.  A stage holds two LDS images, both
+// made of 64-byte ENTRIES (16 channels = four 16-byte quads):
+//   patch   (2 TH + 1) input rows x 2 column parities x (TW + 1) columns: entry e = (py * 2 + (px & 1)) * PWH + (px >> 1)
+//           (de-interleaved columns: the 32 lanes of an M-tile, two input columns apart, read consecutive entries);
+//   weights 9 taps x 64 output channels: entry e = tap * 64 + n.
+// Bank swizzle.  A fragment read is a ds_read_b128 of quad q = 2 (lane >> 5) + h of entry e0 + (lane & 31).  The
+// hardware serves it in four groups of 16 lanes -- {0-3, 12-15, 20-27}, {4-11, 16-19, 28-31} and the same + 32 --
+// on 64 banks (a 256-byte row = 4 entries).  Every group reads one quad of 16 entries that are distinct mod 16, so
+// with quad q of entry e stored in slot q ^ ((e >> 2) & 3) a group covers the 16 slots of a bank row once, whatever
+// e0 is: no padding, no conflicts.
+// The images are WRITTEN by LDS-DMA: piece i (one buffer_load_dwordx4 ... lds of one wave) fills the 1 KB at
+// 1024 i, lane l its 16-byte slot 64 i + l -- the layout is therefore made by the lanes' SOURCE offsets.
+template <int TH_, int TWT_>
+struct ConvS2Geom {
+  static constexpr int TH = TH_, TWT = TWT_, TW = 32 * TWT_;
+  static constexpr int PH = 2 * TH + 1, PW = 2 * TW + 1;
+  static constexpr int PWH = TW + 1;                       // entries per (row, column parity)
+  static constexpr int PENT = PH * 2 * PWH;                // patch entries
+  static constexpr int PPIECES = (PENT + 15) / 16;         // 1 KB pieces of the patch
+  static constexpr int WPIECES = 9 * CS2_BN / 16;          // ... of the weight slab: 36
+  static constexpr int PPW = (PPIECES + 3) / 4;            // patch pieces per wave (wave w: pieces w, w + 4, ...)
+  static constexpr int WPW = WPIECES / 4;                  // weight pieces per wave: 9
+  static constexpr int NPW = PPW + WPW;                    // pieces a wave issues per stage
+  static constexpr int PATCH_BYTES = PPIECES * 1024;
+  static constexpr int W_BYTES = WPIECES * 1024;
+  // [patch 0][patch 1][weights 0][weights 1]: a lane's read pointers move by PATCH_BYTES / W_BYTES between the buffers
+  static constexpr int W_BASE = 2 * PATCH_BYTES;
+  static constexpr int LDS_BYTES = 2 * (PATCH_BYTES + W_BYTES);
+  static constexpr int TILE_STORES = 2 * 16;               // output stores per lane and tile (two N-tiles x 16 pixels)
+  static_assert(TH * TWT == 4, "one M-tile per wave, four waves");
+  static_assert(WPIECES % 4 == 0 && PPW * 4 >= PPIECES, "pieces split over four waves");
+  static_assert(8 * 4096 + 2048 < 65536, "ds_read immediates of a B fragment: tap and N-tile");
+  static_assert(LDS_BYTES + 64 <= 160 * 1024, "two stages in LDS");
+};
+
+__device__ __forceinline__ int conv_s2_swz(int e) { return (e >> 2) & 3; }
+
+// patch piece number k of wave w (the last round is clamped: waves past the end write the last piece again, the same
+// bytes to the same place, so that every wave issues the same number of vector memory operations)
+template <class G>
+__device__ __forceinline__ int conv_s2_patch_piece(int w, int k) {
+  const int i = 4 * k + w;
+  return i < G::PPIECES ? i : G::PPIECES - 1;
+}
+
+// Source of a patch DMA lane, relative to the patch origin (input row 2 y0 - 1, column 2 x0 - 1): byte offset of its
+// (pixel, quad) from there and the patch row / column (to be tested against the image per tile); padding lanes carry a
+// column no image has.
+struct ConvS2Lane {
+  int rel, py, px;
+};
+constexpr int CS2_NO_COLUMN = 0x20000000;
+template <class G>
+__device__ __forceinline__ ConvS2Lane conv_s2_patch_lane(int piece, int lane, int W, int CIN) {
+  const int sl = 64 * piece + lane;
+  const int e = sl >> 2, q = (sl & 3) ^ conv_s2_swz(e);
+  const int plane = e / G::PWH, col = e % G::PWH;
+  const int py = plane >> 1, px = 2 * col + (plane & 1);
+  const bool real = e < G::PENT && px < G::PW;
+  ConvS2Lane L;
+  L.rel = ((py * W + px) * CIN + 4 * q) * 4;
+  L.py = py;
+  L.px = real ? px : CS2_NO_COLUMN;
+  return L;
+}
+// ... of tile (y0, x0): sy = 2 y0 - 1, sx = 2 x0 - 1, sbase = byte offset of the patch origin in the image (negative
+// for the first tile row / column).  Halo, out-of-image and padding lanes get the out-of-bounds offset.
+__device__ __forceinline__ int conv_s2_tile_base(int y0, int x0, int W, int CIN) {
+  return ((2 * y0 - 1) * W + 2 * x0 - 1) * CIN * 4;
+}
+__device__ __forceinline__ int conv_s2_patch_off(const ConvS2Lane& L, int sy, int sx, int sbase, int H, int W) {
+  const bool ok = (unsigned)(L.py + sy) < (unsigned)H && (unsigned)(L.px + sx) < (unsigned)W;
+  return ok ? sbase + L.rel : CS2_OOB;
+}
+// source of a weight DMA lane: byte offset in the slice Wg[tap][n0 + n][c0 + .] of the image [9][COUT][CIN]
+__device__ __forceinline__ int conv_s2_w_lane(int piece, int lane, int COUT, int CIN) {
+  const int sl = 64 * piece + lane;
+  const int e = sl >> 2, q = (sl & 3) ^ conv_s2_swz(e);
+  const int tap = e >> 6, n = e & 63;
+  return ((tap * COUT + n) * CIN + 4 * q) * 4;
+}
+
+// Fragment reads (byte address inside one buffer of the image): lane (li = lane & 31, kh = lane >> 5) of the wave
+// with M-tile mt reads, for tap = 3 dy + dx and half h, the channels 8 kh + 4 h .. + 3 of
+//   A: input pixel (2 yy + dy, 2 (32 xt + li) + dx) of the patch, yy = mt / TWT, xt = mt % TWT;
+//   B: output channel 32 j + li of the tap.
+template <class G>
+__device__ __forceinline__ int conv_s2_a_entry(int mt, int li, int tap) {
+  const int dy = tap / 3, dx = tap % 3;
+  const int yy = mt / G::TWT, xt = mt % G::TWT;
+  return ((2 * yy + dy) * 2 + (dx & 1)) * G::PWH + 32 * xt + li + (dx >> 1);
+}
+__device__ __forceinline__ int conv_s2_slot_addr(int e, int q) { return e * 64 + ((q ^ conv_s2_swz(e)) << 4); }
+template <class G>
+__device__ __forceinline__ int conv_s2_a_addr(int mt, int li, int kh, int h, int tap) {
+  return conv_s2_slot_addr(conv_s2_a_entry<G>(mt, li, tap), 2 * kh + h);
+}
+// (the swizzle of entry tap * 64 + 32 j + li depends on li alone: tap and j are ds_read immediates)
+__device__ __forceinline__ int conv_s2_b_addr(int j, int li, int kh, int h, int tap) {
+  return conv_s2_slot_addr(tap * 64 + 32 * j + li, 2 * kh + h);
+}
+
+// Issue slots of a stage's MFMA run: 9 taps x 16 MFMAs per wave; a DMA piece goes behind MFMAs 3, 9 and 15 of a tap
+// (never two back to back), piece n of the wave in slot n.
+constexpr int CS2_SLOTS = 9 * 3;
+__device__ __forceinline__ int conv_s2_slot_of(int tap, int m) {
+  return (m == 3 || m == 9 || m == 15) ? tap * 3 + (m - 3) / 6 : -1;
+}
+
+}  // namespace pa

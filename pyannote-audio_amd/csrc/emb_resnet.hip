@@ -6,9 +6,11 @@
 // host: weights carry gamma/sqrt(var+eps), the epilogue adds the shift, the residual and the ReLU.
 //
 //   k_stem         conv3x3(1 -> 32) + BN + ReLU straight from the (B,T,80) fbank   (HBM-write bound)
-//   k_conv3x3      implicit GEMM on v_mfma_f32_32x32x2_f32: a workgroup owns TH x (32*TWT) output
+//   k_conv3x3      stride 1: implicit GEMM on v_mfma_f32_32x32x2_f32: a workgroup owns TH x (32*TWT) output
 //                  pixels x BN output channels; per 16-channel input block the (halo'd) input patch
 //                  and the 9 x BN x 16 weight slab are staged in LDS once and reused by all 9 taps.
+//                  (Reference of the Winograd guard, fallback of the Winograd kernels, Bottleneck ResNets.
+//                  Stride 2 -- the three block-entry convolutions -- is k_conv3x3_s2, emb_conv_s2.hip.)
 #include "common.h"
 
 namespace pa {
@@ -115,32 +117,27 @@ __global__ __launch_bounds__(256) void k_stem(const float* __restrict__ fb, int 
 }
 
 // ---------------------------------------------------------------------------------------------
-// conv3x3 (pad 1, stride S) + shift (+ residual) (+ ReLU), f32 MFMA implicit GEMM.
+// conv3x3 (pad 1, stride 1) + shift (+ residual) (+ ReLU), f32 MFMA implicit GEMM.
 //   X  : [B][H][W][CIN]          Wg : [9][COUT][CIN]  (tap = 3*dy+dx, BN scale folded)
 //   Y  : [B][Ho][Wo][COUT]       R  : residual, same shape as Y, or nullptr
 //   grid = (ceil(Wo/TW) * ceil(Ho/TH), COUT/BN, B), block = 256.
 // LDS images (row stride CB+4 = 20 floats = 5 x 16-B slots, conflict-free ds_read_b128):
-//   patch: S=1: [PH][PW][20];  S=2: [PH][2 (column parity)][PWH][20]  (de-interleaved columns so that
-//          the 32 lanes of an M-tile read consecutive entries)
+//   patch: [PH][PW][20]
 //   wts  : [9][BN][20]
 // MFMA k-order inside a 16-channel block: step q uses channel (lane>>5)*8 + q  (A and B alike).
 // ---------------------------------------------------------------------------------------------
 constexpr int CB = 16;
 constexpr int CLD = CB + 4;
 
-template <int S, int TH, int TWT>
+template <int TH, int TWT>
 struct ConvGeom {
   static constexpr int TW = 32 * TWT;
-  static constexpr int PH = (TH - 1) * S + 3;
-  static constexpr int PW = (TW - 1) * S + 3;
-  // entries per column parity (S == 2): TW + 1, padded to 4 mod 8 -- the staging ds_write_b128 of 8 neighbouring lanes
-  // writes two pixels of DIFFERENT parity planes, PWH * 20 floats apart: 16 mod 32 banks apart only then (33 entries:
-  // 20 banks apart, 4 banks shared -- the 2-way conflicts of profiles/r3_pipeline_pmc_sq.txt)
-  static constexpr int PWH = ((TW + 1 + 3) / 8) * 8 + 4;
-  static constexpr int PATCH = S == 1 ? PH * PW * CLD : PH * 2 * PWH * CLD;
+  static constexpr int PH = TH + 2;
+  static constexpr int PW = TW + 2;
+  static constexpr int PATCH = PH * PW * CLD;
 };
 
-template <int S, int TH, int TWT, int BN, bool HAS_R>
+template <int TH, int TWT, int BN, bool HAS_R>
 __global__ __launch_bounds__(256, 2) void k_conv3x3(const float* __restrict__ X, int H, int W, int CIN,
                                                     const float* __restrict__ Wg,
                                                     const float* __restrict__ shift,
@@ -148,7 +145,7 @@ __global__ __launch_bounds__(256, 2) void k_conv3x3(const float* __restrict__ X,
                                                     int Ho, int Wo, int COUT, int relu, int tiles_w,
                                                     int tiles_hw, int n_tiles, int total_tiles, int xranges,
                                                     int* __restrict__ counters) {
-  using G = ConvGeom<S, TH, TWT>;
+  using G = ConvGeom<TH, TWT>;
   constexpr int MT = TH * TWT;   // 32-pixel M-tiles per workgroup
   constexpr int MPW = MT / 4;    // M-tiles per wave
   constexpr int NT = BN / 32;    // N-tiles (every wave covers all of them)
@@ -203,13 +200,10 @@ __global__ __launch_bounds__(256, 2) void k_conv3x3(const float* __restrict__ X,
     }
   };
   u32x4 rp[NP], rw[NW];
-  // Per-lane byte offsets of a tile's staging loads (halo / out-of-image / padding lanes out of bounds: the hardware
-  // bounds check writes the zeros).  They do not depend on the channel block -- that is the scalar offset of the load
-  // -- so they are computed once per TILE (the patch: two integer divisions and four compares per element) or once
-  // per KERNEL (the weight slab), not once per stage: ~150 vector-ALU instructions per stage that were paid in
-  // matrix time (the f32 MFMA shares the vector ALUs).  Stride 2 only: the stride-1 instantiations (fallback of the
-  // Winograd kernels, Bottleneck ResNets) sit at the register limit and keep computing them in place.
-  constexpr bool HOIST = S == 2;
+  // Per-lane byte offsets of the staging loads (halo / out-of-image / padding lanes out of bounds: the hardware
+  // bounds check writes the zeros).  Those of the weight slab do not depend on the tile or the channel block -- that
+  // is the scalar offset of the load -- and are computed once per kernel; those of the patch in place, stage by stage
+  // (the instantiations sit at the register limit: there is no room to keep them per tile).
   struct Offs {
     int p[NP];
   };
@@ -227,22 +221,21 @@ __global__ __launch_bounds__(256, 2) void k_conv3x3(const float* __restrict__ X,
       const int i = tid + 256 * e;
       const int c4 = i & 3, pp = i >> 2;
       const int py = pp / G::PW, px = pp % G::PW;
-      const int iy = q.y0 * S - 1 + py, ix = q.x0 * S - 1 + px;
+      const int iy = q.y0 - 1 + py, ix = q.x0 - 1 + px;
       o.p[e] = ((NPF4 % 256 == 0 || i < NPF4) && iy >= 0 && iy < H && ix >= 0 && ix < W)
                    ? ((iy * W + ix) * CIN + 4 * c4) * 4
                    : OOB;
     }
   };
-  auto gload = [&](const Tile& q, const Offs& o, int c0) {
+  auto gload = [&](const Tile& q, int c0) {
     const __amdgpu_buffer_rsrc_t xsrd = __builtin_amdgcn_make_buffer_rsrc(
         const_cast<float*>(X + (long)q.b * H * W * CIN), 0, H * W * CIN * 4, 0x00020000);
     const __amdgpu_buffer_rsrc_t wsrd = __builtin_amdgcn_make_buffer_rsrc(
         const_cast<float*>(Wg + (long)q.n0 * CIN), 0, (9 * COUT - q.n0) * CIN * 4, 0x00020000);
     Offs here;
-    if (!HOIST) tile_offsets(q, here);
+    tile_offsets(q, here);
 #pragma unroll
-    for (int e = 0; e < NP; ++e)
-      rp[e] = __builtin_amdgcn_raw_buffer_load_b128(xsrd, HOIST ? o.p[e] : here.p[e], c0 * 4, 0);
+    for (int e = 0; e < NP; ++e) rp[e] = __builtin_amdgcn_raw_buffer_load_b128(xsrd, here.p[e], c0 * 4, 0);
 #pragma unroll
     for (int e = 0; e < NW; ++e) rw[e] = __builtin_amdgcn_raw_buffer_load_b128(wsrd, offw[e], c0 * 4, 0);
   };
@@ -251,11 +244,7 @@ __global__ __launch_bounds__(256, 2) void k_conv3x3(const float* __restrict__ X,
     for (int e = 0; e < NP; ++e) {
       const int i = tid + 256 * e;
       const int c4 = i & 3, pp = i >> 2;
-      const int py = pp / G::PW, px = pp % G::PW;
-      int off;
-      if (S == 1) off = pp * CLD + 4 * c4;
-      else off = ((py * 2 + (px & 1)) * G::PWH + (px >> 1)) * CLD + 4 * c4;
-      if (NPF4 % 256 == 0 || i < NPF4) *reinterpret_cast<u32x4*>(patch + off) = rp[e];
+      if (NPF4 % 256 == 0 || i < NPF4) *reinterpret_cast<u32x4*>(patch + pp * CLD + 4 * c4) = rp[e];
     }
 #pragma unroll
     for (int e = 0; e < NW; ++e) {
@@ -278,10 +267,7 @@ __global__ __launch_bounds__(256, 2) void k_conv3x3(const float* __restrict__ X,
     return;
   }
   Tile cur = decode(t);
-  Offs oc, on;
-  if (HOIST) tile_offsets(cur, oc);
-  on = oc;
-  gload(cur, oc, 0);
+  gload(cur, 0);
   for (;;) {
     int ahead = 0;
     if (tid == 0) ahead = tq_claim_own(tq);
@@ -302,13 +288,10 @@ __global__ __launch_bounds__(256, 2) void k_conv3x3(const float* __restrict__ X,
       __syncthreads();
       if (c0 == 0) {     // CIN >= 2 channel blocks: the next tile is known before the last stage
         tn = s_next;
-        if (tn >= 0) {
-          nxt = decode(tn);
-          if (HOIST) tile_offsets(nxt, on);
-        }
+        if (tn >= 0) nxt = decode(tn);
       }
-      if (c0 + CB < CIN) gload(cur, oc, c0 + CB);
-      else if (tn >= 0) gload(nxt, on, 0);
+      if (c0 + CB < CIN) gload(cur, c0 + CB);
+      else if (tn >= 0) gload(nxt, 0);
       // ---- 9 taps x 8 k-steps (dy stays a real loop: unrolling all 9 taps only buys register pressure).
       // Prefetching the fragments of tap+1 under the MFMAs of tap with a pinned schedule -- what the
       // Winograd kernel needs -- was measured neutral here (79.4 vs 79.5 ms per audio-hour): two
@@ -320,9 +303,7 @@ __global__ __launch_bounds__(256, 2) void k_conv3x3(const float* __restrict__ X,
         for (int i = 0; i < MPW; ++i) {
           const int mt = wv * MPW + i;
           const int yy = mt / TWT, xt = mt % TWT;
-          int off;
-          if (S == 1) off = ((yy + dy) * G::PW + 32 * xt + li + dx) * CLD;
-          else off = (((yy * 2 + dy) * 2 + (dx & 1)) * G::PWH + 32 * xt + li + (dx >> 1)) * CLD;
+          const int off = ((yy + dy) * G::PW + 32 * xt + li + dx) * CLD;
           a[i][0] = *reinterpret_cast<const float4*>(patch + off + kh * 8);
           a[i][1] = *reinterpret_cast<const float4*>(patch + off + kh * 8 + 4);
         }
@@ -411,19 +392,21 @@ __global__ __launch_bounds__(256, 2) void k_conv3x3(const float* __restrict__ X,
     }
     if (tn < 0) break;
     cur = nxt;
-    oc = on;
   }
   if (tid == 0) tq_done(tq, gridDim.x);
 }
 
 int xcd_ranges_wanted(bool by_default);   // emb_winograd4.hip
+// stride 2 (emb_conv_s2.hip: k_conv3x3_s2)
+int launch_conv_s2(const float* X, int B, int H, int W, int CIN, const float* Wg, const float* shift, const float* R,
+                   float* Y, int COUT, int relu, hipStream_t st);
 
-template <int S, int TH, int TWT, int BN, bool HAS_R>
+template <int TH, int TWT, int BN, bool HAS_R>
 static int launch_conv_r(const float* X, int B, int H, int W, int CIN, const float* Wg,
                          const float* shift, const float* R, float* Y, int COUT, int relu,
                          hipStream_t st) {
-  using G = ConvGeom<S, TH, TWT>;
-  const int Ho = (H - 1) / S + 1, Wo = (W - 1) / S + 1;
+  using G = ConvGeom<TH, TWT>;
+  const int Ho = H, Wo = W;
   const int tiles_w = cdiv(Wo, G::TW), tiles_h = cdiv(Ho, TH);
   const size_t lds = (size_t)(G::PATCH + 9 * BN * CLD) * sizeof(float);
   // workgroups the chip holds at once (2 per CU: LDS- and VGPR-bound); per DEVICE, like the attribute
@@ -433,11 +416,11 @@ static int launch_conv_r(const float* X, int B, int H, int W, int CIN, const flo
   (void)hipGetDevice(&dev);
   if (dev < 0 || dev >= MAXDEV) dev = 0;
   if (!resident_of[dev]) {
-    (void)hipFuncSetAttribute((const void*)k_conv3x3<S, TH, TWT, BN, HAS_R>,
+    (void)hipFuncSetAttribute((const void*)k_conv3x3<TH, TWT, BN, HAS_R>,
                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     int cus = 256, per_cu = 2;
     (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_conv3x3<S, TH, TWT, BN, HAS_R>, 256, lds) !=
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_conv3x3<TH, TWT, BN, HAS_R>, 256, lds) !=
             hipSuccess || per_cu < 1)
       per_cu = 2;
     resident_of[dev] = cus * per_cu;
@@ -453,18 +436,18 @@ static int launch_conv_r(const float* X, int B, int H, int W, int CIN, const flo
     set_error("pa_conv3x3: cannot allocate the tile counters");
     return 2;
   }
-  hipLaunchKernelGGL((k_conv3x3<S, TH, TWT, BN, HAS_R>), dim3(grid), dim3(256), lds, st, X, H, W, CIN, Wg,
+  hipLaunchKernelGGL((k_conv3x3<TH, TWT, BN, HAS_R>), dim3(grid), dim3(256), lds, st, X, H, W, CIN, Wg,
                      shift, R, Y, Ho, Wo, COUT, relu, tiles_w, tiles_hw, n_tiles, (int)total, xcd_ranges_wanted(true),
                      counters);
   return 0;
 }
 
-template <int S, int TH, int TWT, int BN>
+template <int TH, int TWT, int BN>
 static int launch_conv(const float* X, int B, int H, int W, int CIN, const float* Wg,
                        const float* shift, const float* R, float* Y, int COUT, int relu,
                        hipStream_t st) {
-  return R != nullptr ? launch_conv_r<S, TH, TWT, BN, true>(X, B, H, W, CIN, Wg, shift, R, Y, COUT, relu, st)
-                      : launch_conv_r<S, TH, TWT, BN, false>(X, B, H, W, CIN, Wg, shift, R, Y, COUT, relu, st);
+  return R != nullptr ? launch_conv_r<TH, TWT, BN, true>(X, B, H, W, CIN, Wg, shift, R, Y, COUT, relu, st)
+                      : launch_conv_r<TH, TWT, BN, false>(X, B, H, W, CIN, Wg, shift, R, Y, COUT, relu, st);
 }
 
 }  // namespace pa
@@ -494,15 +477,13 @@ int pa_conv3x3(const float* X, int B, int H, int W, int cin, const float* Wg, co
   pa::ProfScope prof("k_conv3x3", stream, 2.0 * 9 * cin * cout * (double)B * Ho * Wo_,
                      4.0 * ((double)B * H * W * cin + (double)B * Ho * Wo_ * cout * (R ? 2 : 1) + 9.0 * cin * cout));
   if (stride == 1) {
-    if (cout == 32) pa::launch_conv<1, 8, 1, 32>(X, B, H, W, cin, Wg, shift, R, Y, cout, relu, st);
-    else if (Ho >= 32) pa::launch_conv<1, 8, 1, 64>(X, B, H, W, cin, Wg, shift, R, Y, cout, relu, st);
-    else if (Ho >= 16) pa::launch_conv<1, 4, 2, 64>(X, B, H, W, cin, Wg, shift, R, Y, cout, relu, st);
-    else pa::launch_conv<1, 2, 2, 64>(X, B, H, W, cin, Wg, shift, R, Y, cout, relu, st);
+    if (cout == 32) pa::launch_conv<8, 1, 32>(X, B, H, W, cin, Wg, shift, R, Y, cout, relu, st);
+    else if (Ho >= 32) pa::launch_conv<8, 1, 64>(X, B, H, W, cin, Wg, shift, R, Y, cout, relu, st);
+    else if (Ho >= 16) pa::launch_conv<4, 2, 64>(X, B, H, W, cin, Wg, shift, R, Y, cout, relu, st);
+    else pa::launch_conv<2, 2, 64>(X, B, H, W, cin, Wg, shift, R, Y, cout, relu, st);
   } else if (stride == 2) {
     PA_REQUIRE(cout % 64 == 0, "pa_conv3x3: stride 2 needs cout %% 64 == 0");
-    // 32-cout tiles: two workgroups per CU (+4-7 % over 64-cout tiles, measured in round 1)
-    if (Ho >= 16) pa::launch_conv<2, 4, 1, 32>(X, B, H, W, cin, Wg, shift, R, Y, cout, relu, st);
-    else pa::launch_conv<2, 2, 2, 32>(X, B, H, W, cin, Wg, shift, R, Y, cout, relu, st);
+    if (pa::launch_conv_s2(X, B, H, W, cin, Wg, shift, R, Y, cout, relu, st) != 0) return 2;
   } else {
     PA_REQUIRE(false, "pa_conv3x3: stride %d not supported", stride);
   }

@@ -1,5 +1,5 @@
 """Per-shape timing of pa_conv3x3 on the ResNet34 layer shapes (development aid; HIP events through
-the library profiler).  usage: [WINO=1|4] [ONLY_S1=1] [PA_LIB=variant.so] python tools/bench_conv.py [B] [reps]"""
+the library profiler).  usage: [WINO=1|4] [ONLY_S1=1|ONLY_S2=1] [PA_LIB=variant.so] python tools/bench_conv.py [B] [reps]"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -16,6 +16,8 @@ shapes = [  # (H, W, cin, cout, stride, residual)
     (10, 125, 256, 256, 1, True)]
 if os.environ.get("ONLY_S1") == "1":   # the stride-1 (Winograd) layers, with and without the residual input
     shapes = [(H, W, ci, co, s, r) for (H, W, ci, co, s, _) in shapes if s == 1 for r in (False, True)]
+if os.environ.get("ONLY_S2") == "1":   # the three block-entry convolutions (csrc/emb_conv_s2.hip)
+    shapes = [sh for sh in shapes if sh[4] == 2]
 if os.environ.get("ONLY_CIN"):         # one input width only (e.g. ONLY_CIN=32: layer 1)
     shapes = [sh for sh in shapes if sh[2] == int(os.environ["ONLY_CIN"])]
 for (H, W, ci, co, s, res) in shapes:

@@ -20,6 +20,7 @@ VARIANTS = {   # tag -> (source file, extra flags, git revision of the source or
     "lfstamp": ("linkage_fast.hip", "-DPA_LF_STAMP=1 -ffp-contract=off", SWITCHES),   # heap-free merge: cycles per phase of a round (printf)
     "w4defer2": ("emb_winograd4.hip", "-DPA_W4_DEFER_STORES=2", SWITCHES),   # F(4x4): held stores also with a residual (spills: slower)
     "conv_r4order": ("emb_resnet.hip", "", "59d35f4"),   # k_conv3x3 with the cout slice as the slowest tile index (round 4)
+    "conv_s2_parent": ("emb_resnet.hip", "", "56a8a7a"),   # stride 2 on k_conv3x3<2, ...> (register-staged, 32-cout tiles), before k_conv3x3_s2
     "conv_prev": ("emb_resnet.hip", "", "b01ddc8"),   # k_conv3x3 with the staging offsets recomputed every stage
     "w4tstores": ("emb_winograd4.hip", "-DPA_W4_STORE_AUX=0", SWITCHES),        # F(4x4): output stores with the default (temporal) policy
     "w4ntr": ("emb_winograd4.hip", "-DPA_W4_RES_AUX=2", SWITCHES),              # F(4x4): residual loads non-temporal
