@@ -630,6 +630,40 @@ int pa_binarize_regions(const float* scores, int T, int K, const float* onset, c
                         double duration, double step, int capacity, int32_t* counts, double* regions,
                         int32_t* tracks, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- the regions of many detectors from one pass over the scores (tuning onset / offset / min_duration_on /
+ *      min_duration_off of a detection pipeline on a corpus; csrc/regions_sweep.hip) ---- */
+
+/* scores (T,K) fp32 on the device, K <= 16, as for pa_binarize_regions.  HOST arrays: L LANES (lane_class int32 in
+ * 0..K-1, onset, offset fp32) and M JOBS (job_lane int32 in 0..L-1, min_duration_on / min_duration_off fp64), jobs in
+ * any order, any number of jobs per lane, lanes may repeat.  Job j's region list and track positions are, bit for
+ * bit, what pa_binarize_regions gives for column lane_class[job_lane[j]] with the job's four parameters.
+ * Lanes of one class are grouped sixteen to a map word (classes ascending, lanes in order): the scores are read per
+ * group, the hysteresis runs once per lane.  Two phases, because the row buffers are sized from counts:
+ *   pa_regions_sweep_count   n_raw (L) int32, HOST, overwritten: the regions of every lane before any clean-up.
+ *   pa_regions_sweep_emit    takes those counts back; regions (rows, 2) fp64 and tracks (rows) int32 (optional, NULL)
+ *                            on the device: job after job, each in time order; job_off (M + 1) int32 on the device:
+ *                            job j owns rows job_off[j] .. job_off[j + 1].  rows >= sum over jobs of
+ *                            n_raw[job_lane[j]] (the bound a job's list has before merging).
+ * `workspace` (device): pa_regions_sweep_workspace_bytes(T, groups, groups_per_launch, L, M, raw_rows, job_rows) with
+ * groups = pa_regions_sweep_groups(K, L, lane_class) (-1: K or a class out of range), raw_rows = sum of n_raw,
+ * job_rows as above (M = raw_rows = job_rows = 0 for the counting phase).  A workspace smaller than
+ * groups_per_launch = groups asks for (at least groups_per_launch = 1) splits the groups over several launch
+ * sequences; results do not depend on the split.  launches (optional, HOST): how many sequences ran.
+ * T < 2, L == 0 or M == 0 give zero counts / an all-zero offset table.  K outside 1..16, a lane's class outside
+ * 0..K-1, a job's lane outside 0..L-1 and NaN thresholds or durations are refused before any launch (3,
+ * pa_last_error).  No workgroup waits for another, no floating-point atomics.  Both calls wait for the stream. */
+int pa_regions_sweep_groups(int K, int L, const int32_t* lane_class);
+size_t pa_regions_sweep_workspace_bytes(int T, int groups, int groups_per_launch, int L, int M, long raw_rows,
+                                        long job_rows);
+int pa_regions_sweep_count(const float* scores, int T, int K, int L, const int32_t* lane_class, const float* onset,
+                           const float* offset, int32_t* n_raw, int32_t* launches, void* workspace,
+                           size_t workspace_bytes, void* stream);
+int pa_regions_sweep_emit(const float* scores, int T, int K, int L, const int32_t* lane_class, const float* onset,
+                          const float* offset, const int32_t* n_raw, int M, const int32_t* job_lane,
+                          const double* min_duration_on, const double* min_duration_off, double start, double duration,
+                          double step, long rows, double* regions, int32_t* tracks, int32_t* job_off,
+                          int32_t* launches, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- audio front door (core/io.py:223-265) ---- */
 
 /* Polyphase windowed-sinc resampling, replaces torchaudio.functional.resample in

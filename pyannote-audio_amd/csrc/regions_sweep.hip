@@ -1,0 +1,556 @@
+// hipcc-flags: -ffp-contract=off
+// The regions of MANY hysteresis detectors from one pass over an aggregated (T, K) score array: what tuning the
+// thresholds of VoiceActivityDetection / MultiLabelSegmentation on a corpus asks for (every candidate's region lists;
+// DESIGN.md section 24).  The rule is pa_binarize_regions' (regions.hip), bit for bit.
+//
+// A LANE is (class, onset, offset); a JOB is (lane, min_duration_on, min_duration_off).  Lanes of one class travel
+// sixteen to a map word -- the role the K classes play in regions.hip -- so a GROUP of up to 16 lanes reads its
+// column of the scores once, and the hysteresis of a lane runs once however many jobs read it.
+//
+// Per launch batch of groups (blockIdx.y = group; as many groups at a time as the workspace holds, results do not
+// depend on the split; NO workgroup ever waits for another one):
+//   k_sweep_reduce / k_sweep_scan / k_sweep_apply / k_sweep_offsets   as in regions.hip -> raw regions per lane
+//   (counting phase stops here: pa_regions_sweep_count reads the raw counts back, the caller sizes the row buffers)
+//   k_sweep_emit       region n of a lane runs from its n-th on-event to its n-th off-event
+//   k_sweep_clean      one workgroup per lane: drops the empty regions into a list that is only read from then on
+// then, over all jobs:
+//   k_sweep_merge      one workgroup per job: merges across short gaps into the job's own scratch, counts survivors
+//   k_sweep_job_offsets  one wave: exclusive scan of the jobs' counts -> the (M + 1) offset table
+//   k_sweep_remove     one workgroup per job: drops short regions, writes the job's slice of the packed output
+#include <algorithm>
+#include <vector>
+
+#include "common.h"
+#include "pyannote_amd.h"
+#include "regions.h"
+
+namespace pa {
+
+struct SweepGroup {
+  float onset[RG_MAXK], offset[RG_MAXK];   // unused slots: +inf / -inf, the identity map, never an event
+  int32_t lane[RG_MAXK];                   // lane id of every slot, -1: unused
+  int32_t cls;
+};
+
+__device__ __forceinline__ uint32_t sw_frame_map(const float* __restrict__ scores, long i, int T, int K,
+                                                 const SweepGroup& g) {
+  if (i >= T) return RG_IDENTITY;
+  const float y = scores[i * K + g.cls];            // NaN: both comparisons false -> identity
+  uint32_t f0 = 0, f1 = 0;
+#pragma unroll
+  for (int s = 0; s < RG_MAXK; ++s) {
+    f0 |= (uint32_t)(y > g.onset[s]) << s;
+    f1 |= (uint32_t)(!(y < g.offset[s])) << s;
+  }
+  if (i == 0) f1 = f0;
+  return f0 | (f1 << 16);
+}
+
+// rg_time with the grid as plain arguments (same operations, same order)
+__device__ __forceinline__ double sw_time(long i, double start, double duration, double step) {
+  const double s = __dadd_rn(start, __dmul_rn((double)i, step));
+  return __dmul_rn(0.5, __dadd_rn(s, __dadd_rn(s, duration)));
+}
+
+__global__ __launch_bounds__(RG_THREADS) void k_sweep_reduce(const float* __restrict__ scores, int T, int K,
+                                                             const SweepGroup* __restrict__ groups, int ntiles,
+                                                             uint32_t* __restrict__ tile_map) {
+  __shared__ uint32_t part[RG_PASSES * 4];
+  __shared__ SweepGroup g;
+  if (threadIdx.x == 0) g = groups[blockIdx.y];
+  __syncthreads();
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const long t0 = (long)blockIdx.x * RG_TILE;
+#pragma unroll
+  for (int q = 0; q < RG_PASSES; ++q) {
+    const uint32_t m = rg_wave_scan(sw_frame_map(scores, t0 + q * RG_THREADS + threadIdx.x, T, K, g), lane);
+    if (lane == 63) part[q * 4 + w] = m;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    uint32_t m = part[0];
+    for (int j = 1; j < RG_PASSES * 4; ++j) m = rg_compose(m, part[j]);
+    tile_map[(long)blockIdx.y * ntiles + blockIdx.x] = m;
+  }
+}
+
+__global__ __launch_bounds__(64) void k_sweep_scan(const uint32_t* __restrict__ tile_map_all, int ntiles,
+                                                   uint32_t* __restrict__ state_in_all) {
+  const int lane = threadIdx.x;
+  const uint32_t* tile_map = tile_map_all + (long)blockIdx.x * ntiles;
+  uint32_t* state_in = state_in_all + (long)blockIdx.x * ntiles;
+  uint32_t carry = RG_IDENTITY;
+  for (int base = 0; base < ntiles; base += 64) {
+    const int t = base + lane;
+    const uint32_t inc = rg_wave_scan(t < ntiles ? tile_map[t] : RG_IDENTITY, lane);
+    uint32_t exc = __shfl_up(inc, 1, 64);
+    if (lane == 0) exc = RG_IDENTITY;
+    if (t < ntiles) state_in[t] = rg_compose(carry, exc) & 0xffffu;
+    carry = rg_compose(carry, __shfl(inc, 63, 64));
+  }
+}
+
+// `events`: NULL in the counting phase (only the chunk counts are wanted)
+__global__ __launch_bounds__(RG_THREADS) void k_sweep_apply(const float* __restrict__ scores, int T, int K,
+                                                            const SweepGroup* __restrict__ groups, int ntiles,
+                                                            const uint32_t* __restrict__ state_in,
+                                                            uint32_t* __restrict__ events,
+                                                            int* __restrict__ chunk_cnt, int nchunks) {
+  __shared__ uint32_t part[4];
+  __shared__ SweepGroup g;
+  if (threadIdx.x == 0) g = groups[blockIdx.y];
+  __syncthreads();
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const long t0 = (long)blockIdx.x * RG_TILE;
+  uint32_t state = state_in[(long)blockIdx.y * ntiles + blockIdx.x];
+  for (int q = 0; q < RG_PASSES; ++q) {
+    const long i = t0 + q * RG_THREADS + threadIdx.x;
+    const uint32_t m = sw_frame_map(scores, i, T, K, g);
+    const uint32_t inc = rg_wave_scan(m, lane);
+    __syncthreads();                                // `part` of the previous pass has been read
+    if (lane == 63) part[w] = inc;
+    __syncthreads();
+    uint32_t exc = __shfl_up(inc, 1, 64);
+    if (lane == 0) exc = RG_IDENTITY;
+    uint32_t pre = RG_IDENTITY, total = part[0];
+    for (int j = 1; j < 4; ++j) {
+      if (j == w) pre = total;
+      total = rg_compose(total, part[j]);
+    }
+    if (w == 0) pre = RG_IDENTITY;
+    exc = rg_compose(pre, exc);
+    const uint32_t before = ((state & (exc >> 16)) | (~state & exc)) & 0xffffu;
+    const uint32_t after = ((before & (m >> 16)) | (~before & m)) & 0xffffu;
+    uint32_t on = ~before & after & 0xffffu, off = before & ~after;
+    if (i == T - 1) {   // a region still open closes on the last frame; one that would open there is empty
+      off = before;
+      on = 0;
+    }
+    if (i >= T) on = off = 0;
+    if (events && i < T) events[(long)blockIdx.y * T + i] = on | (off << 16);
+    const int chunk = blockIdx.x * (RG_TILE / RG_CHUNK) + q * 4 + w;
+#pragma unroll
+    for (int s = 0; s < RG_MAXK; ++s) {
+      const unsigned long long b = __ballot((on >> s) & 1u);
+      if (lane == s && chunk < nchunks) chunk_cnt[((long)blockIdx.y * RG_MAXK + s) * nchunks + chunk] = __popcll(b);
+    }
+    state = ((state & (total >> 16)) | (~state & total)) & 0xffffu;
+  }
+}
+
+// workgroup = group, wave s = its slot s: exclusive scan of the slot's chunk counts; the total is the lane's raw count
+__global__ __launch_bounds__(64 * RG_MAXK) void k_sweep_offsets(const SweepGroup* __restrict__ groups,
+                                                                const int* __restrict__ chunk_cnt, int nchunks,
+                                                                int* __restrict__ chunk_off,
+                                                                int* __restrict__ n_raw) {
+  const int lane = threadIdx.x & 63, s = threadIdx.x >> 6;
+  const int* cnt = chunk_cnt + ((long)blockIdx.x * RG_MAXK + s) * nchunks;
+  int* out = chunk_off + ((long)blockIdx.x * RG_MAXK + s) * nchunks;
+  int carry = 0;
+  for (int base = 0; base < nchunks; base += 64) {
+    const int c = base + lane;
+    const int v = c < nchunks ? cnt[c] : 0;
+    const int inc = rg_wave_scan_int(v, lane);
+    if (c < nchunks) out[c] = carry + inc - v;
+    carry += __shfl(inc, 63, 64);
+  }
+  const int id = groups[blockIdx.x].lane[s];
+  if (lane == 0 && id >= 0) n_raw[id] = carry;
+}
+
+// raw rows of lane l: raw + 2 raw_off[l], raw_off[l + 1] - raw_off[l] of them (the counting phase's counts)
+__global__ __launch_bounds__(RG_THREADS) void k_sweep_emit(const uint32_t* __restrict__ events, int T,
+                                                           const SweepGroup* __restrict__ groups, double start,
+                                                           double duration, double step,
+                                                           const int* __restrict__ chunk_off, int nchunks,
+                                                           const int* __restrict__ raw_off,
+                                                           double* __restrict__ raw) {
+  const int lane = threadIdx.x & 63;
+  const long i = (long)blockIdx.x * RG_THREADS + threadIdx.x;
+  const int chunk = (int)(i >> 6);
+  const uint32_t ev = i < T ? events[(long)blockIdx.y * T + i] : 0u;
+  if (__ballot(ev != 0u) == 0ull) return;
+  const SweepGroup& g = groups[blockIdx.y];
+  const double t = sw_time(i, start, duration, step);
+  const unsigned long long upto = ~0ull >> (63 - lane);   // lanes 0..lane
+#pragma unroll
+  for (int s = 0; s < RG_MAXK; ++s) {
+    const unsigned long long b = __ballot((ev >> s) & 1u);
+    if ((ev >> s) & 0x10001u) {
+      const int id = g.lane[s];
+      const int n = chunk_off[((long)blockIdx.y * RG_MAXK + s) * nchunks + chunk] + __popcll(b & upto) - 1;
+      if (id >= 0 && n >= 0 && n < raw_off[id + 1] - raw_off[id]) {
+        double* r = raw + ((long)raw_off[id] + n) * 2;
+        if ((ev >> s) & 1u) r[0] = t;
+        if ((ev >> (16 + s)) & 1u) r[1] = t;
+      }
+    }
+  }
+}
+
+// one workgroup per slot of the batch's groups: raw -> clean drops the regions the reference's Annotation refuses on
+// insertion (duration <= 1e-6).  `clean` has the layout of `raw` and is only read afterwards.
+__global__ __launch_bounds__(RG_THREADS) void k_sweep_clean(const SweepGroup* __restrict__ groups,
+                                                            const int* __restrict__ n_raw,
+                                                            const int* __restrict__ raw_off,
+                                                            const double* __restrict__ raw_all,
+                                                            double* __restrict__ clean_all,
+                                                            int* __restrict__ n_clean) {
+  __shared__ int red[4];
+  const int id = groups[blockIdx.x / RG_MAXK].lane[blockIdx.x % RG_MAXK], tid = threadIdx.x;
+  if (id < 0) return;                                   // (the whole workgroup)
+  const double* raw = raw_all + (long)raw_off[id] * 2;
+  double* clean = clean_all + (long)raw_off[id] * 2;
+  const int n0 = min(n_raw[id], raw_off[id + 1] - raw_off[id]);
+  int total, n1 = 0;
+  for (int base = 0; base < n0; base += RG_THREADS) {
+    const int i = base + tid;
+    double s = 0.0, e = 0.0;
+    if (i < n0) { s = raw[2 * i]; e = raw[2 * i + 1]; }
+    const int keep = i < n0 && (e - s) > RG_PRECISION;
+    const int pos = n1 + rg_block_scan_int(keep, red, total) - 1;
+    if (keep) { clean[2 * pos] = s; clean[2 * pos + 1] = e; }
+    n1 += total;
+  }
+  if (tid == 0) n_clean[id] = n1;
+}
+
+struct SweepJob {
+  double min_on, min_off;
+  int32_t lane, scratch_off;    // the job's merged rows: scratch + 2 scratch_off, room for the lane's raw count
+};
+
+// one workgroup per job: clean (read only) -> the job's scratch merges neighbours whose gap has
+// Segment.duration < min_duration_off; then the survivors of the min_duration_on removal are counted
+__global__ __launch_bounds__(RG_THREADS) void k_sweep_merge(const SweepJob* __restrict__ jobs,
+                                                            const int* __restrict__ n_clean,
+                                                            const int* __restrict__ raw_off,
+                                                            const double* __restrict__ clean_all,
+                                                            double* __restrict__ scratch_all,
+                                                            int* __restrict__ n_merged, int* __restrict__ counts) {
+  __shared__ int red[4];
+  const SweepJob job = jobs[blockIdx.x];
+  const int tid = threadIdx.x;
+  const double* in = clean_all + (long)raw_off[job.lane] * 2;
+  double* out = scratch_all + (long)job.scratch_off * 2;
+  const double min_on = job.min_on, min_off = job.min_off;
+  const int n1 = min(n_clean[job.lane], raw_off[job.lane + 1] - raw_off[job.lane]);
+  int total, n2 = 0;
+  for (int base = 0; base < n1; base += RG_THREADS) {
+    const int i = base + tid;
+    int head = 0, tail = 0;
+    double s = 0.0, e = 0.0;
+    if (i < n1) {
+      s = in[2 * i]; e = in[2 * i + 1];
+      head = i == 0 || !(min_off > 0.0 && rg_duration(in[2 * i - 1], s) < min_off);
+      tail = i == n1 - 1 || !(min_off > 0.0 && rg_duration(e, in[2 * i + 2]) < min_off);
+    }
+    const int run = n2 + rg_block_scan_int(head, red, total) - 1;
+    if (head) out[2 * run] = s;
+    if (tail) out[2 * run + 1] = e;
+    n2 += total;
+  }
+  __syncthreads();                                      // the merged rows are read by other threads below
+  int n3 = 0;
+  for (int base = 0; base < n2; base += RG_THREADS) {
+    const int i = base + tid;
+    const int keep = i < n2 && !(min_on > 0.0 && rg_duration(out[2 * i], out[2 * i + 1]) < min_on);
+    rg_block_scan_int(keep, red, total);
+    n3 += total;
+  }
+  if (tid == 0) { n_merged[blockIdx.x] = n2; counts[blockIdx.x] = n3; }
+}
+
+__global__ __launch_bounds__(64) void k_sweep_job_offsets(const int* __restrict__ counts, int M,
+                                                          int* __restrict__ job_off) {
+  const int lane = threadIdx.x;
+  int carry = 0;
+  for (int base = 0; base < M; base += 64) {
+    const int j = base + lane;
+    const int v = j < M ? counts[j] : 0;
+    const int inc = rg_wave_scan_int(v, lane);
+    if (j < M) job_off[j] = carry + inc - v;
+    carry += __shfl(inc, 63, 64);
+  }
+  if (lane == 0) job_off[M] = carry;
+}
+
+// one workgroup per job: scratch -> the job's rows of the packed output drops regions with duration < min_duration_on
+// and records every survivor's index among the merged regions (its track name)
+__global__ __launch_bounds__(RG_THREADS) void k_sweep_remove(const SweepJob* __restrict__ jobs,
+                                                             const double* __restrict__ scratch_all,
+                                                             const int* __restrict__ n_merged,
+                                                             const int* __restrict__ job_off, int rows,
+                                                             double* __restrict__ regions,
+                                                             int* __restrict__ tracks) {
+  __shared__ int red[4];
+  const SweepJob job = jobs[blockIdx.x];
+  const int tid = threadIdx.x;
+  const double* in = scratch_all + (long)job.scratch_off * 2;
+  const double min_on = job.min_on, min_off = job.min_off;
+  const int n2 = n_merged[blockIdx.x], o = job_off[blockIdx.x];
+  int total, n3 = 0;
+  for (int base = 0; base < n2; base += RG_THREADS) {
+    const int i = base + tid;
+    double s = 0.0, e = 0.0;
+    if (i < n2) { s = in[2 * i]; e = in[2 * i + 1]; }
+    const int keep = i < n2 && !(min_on > 0.0 && rg_duration(s, e) < min_on);
+    const long pos = (long)o + n3 + rg_block_scan_int(keep, red, total) - 1;
+    if (keep && pos < rows) {
+      regions[2 * pos] = s;
+      regions[2 * pos + 1] = e;
+      if (tracks) tracks[pos] = min_off > 0.0 ? i : 0;   // support() renames tracks; without it all are the first name
+    }
+    n3 += total;
+  }
+}
+
+// ------------------------------------------------------------------------------------------------ host side
+static size_t sw_up(size_t b) { return (b + 255) & ~(size_t)255; }
+
+// what one group of a launch batch needs: tile maps, entry states, event words, chunk counts and offsets
+static size_t sweep_group_bytes(int T) {
+  const size_t ntiles = cdiv(T, RG_TILE), nchunks = cdiv(T, RG_CHUNK);
+  return 2 * sw_up(4 * ntiles) + sw_up(4 * (size_t)T) + 2 * sw_up(4 * RG_MAXK * nchunks);
+}
+
+// what does not depend on the batch: group table, per-lane tables, the three row buffers, per-job tables
+static size_t sweep_fixed_bytes(int groups, int L, int M, long raw_rows, long job_rows) {
+  return 256 + sw_up(sizeof(SweepGroup) * (size_t)groups) + 3 * sw_up(4 * ((size_t)L + 1)) +
+         2 * sw_up(16 * (size_t)raw_rows) + sw_up(sizeof(SweepJob) * (size_t)M) + 2 * sw_up(4 * ((size_t)M + 1)) +
+         sw_up(16 * (size_t)job_rows);
+}
+
+struct SweepBatch {
+  uint32_t *tile_map, *state_in, *events;
+  int *chunk_cnt, *chunk_off;
+};
+
+static SweepBatch sweep_batch(char* p, int T, int groups) {
+  const size_t ntiles = cdiv(T, RG_TILE), nchunks = cdiv(T, RG_CHUNK);
+  SweepBatch b;
+  b.tile_map = (uint32_t*)p;  p += groups * sw_up(4 * ntiles);
+  b.state_in = (uint32_t*)p;  p += groups * sw_up(4 * ntiles);
+  b.events = (uint32_t*)p;    p += groups * sw_up(4 * (size_t)T);
+  b.chunk_cnt = (int*)p;      p += groups * sw_up(4 * RG_MAXK * nchunks);
+  b.chunk_off = (int*)p;
+  return b;
+}
+
+// lanes of one class, in lane order, sixteen to a group; classes in ascending order.  false: a class out of range
+static bool sweep_plan(int K, int L, const int32_t* lane_class, const float* onset, const float* offset,
+                       std::vector<SweepGroup>* groups) {
+  std::vector<std::vector<int>> by_class(K > 0 ? K : 0);
+  for (int l = 0; l < L; ++l) {
+    if (lane_class[l] < 0 || lane_class[l] >= K) return false;
+    by_class[lane_class[l]].push_back(l);
+  }
+  for (int k = 0; k < K; ++k)
+    for (size_t at = 0; at < by_class[k].size(); at += RG_MAXK) {
+      SweepGroup g;
+      g.cls = k;
+      for (int s = 0; s < RG_MAXK; ++s) {
+        const bool used = at + s < by_class[k].size();
+        const int l = used ? by_class[k][at + s] : -1;
+        g.lane[s] = l;
+        g.onset[s] = used ? onset[l] : __builtin_inff();
+        g.offset[s] = used ? offset[l] : -__builtin_inff();
+      }
+      groups->push_back(g);
+    }
+  return true;
+}
+
+static int sweep_check_lanes(const char* who, int T, int K, int L, const int32_t* lane_class, const float* onset,
+                             const float* offset) {
+  PA_REQUIRE(K > 0 && K <= RG_MAXK, "%s: K = %d classes, 1..%d supported", who, K, RG_MAXK);
+  PA_REQUIRE(T >= 0 && L >= 0, "%s: negative T or lane count", who);
+  PA_REQUIRE(L == 0 || (lane_class && onset && offset), "%s: null lane array", who);
+  for (int l = 0; l < L; ++l) {
+    PA_REQUIRE(lane_class[l] >= 0 && lane_class[l] < K, "%s: lane %d names class %d, 0..%d exist", who, l,
+               lane_class[l], K - 1);
+    PA_REQUIRE(onset[l] == onset[l] && offset[l] == offset[l], "%s: a threshold of lane %d is NaN", who, l);
+  }
+  return 0;
+}
+
+// the launches of one batch of `n` groups starting at group `g0`; `raw` NULL: counting only
+static void sweep_launch_batch(hipStream_t s, const float* scores, int T, int K, const SweepGroup* d_groups, int g0,
+                               int n, const SweepBatch& b, int* d_n_raw, double start, double duration, double step,
+                               const int* d_raw_off, double* raw, double* clean, int* d_n_clean) {
+  const int ntiles = cdiv(T, RG_TILE), nchunks = cdiv(T, RG_CHUNK);
+  const SweepGroup* g = d_groups + g0;
+  hipLaunchKernelGGL(k_sweep_reduce, dim3(ntiles, n), dim3(RG_THREADS), 0, s, scores, T, K, g, ntiles, b.tile_map);
+  hipLaunchKernelGGL(k_sweep_scan, dim3(n), dim3(64), 0, s, b.tile_map, ntiles, b.state_in);
+  hipLaunchKernelGGL(k_sweep_apply, dim3(ntiles, n), dim3(RG_THREADS), 0, s, scores, T, K, g, ntiles, b.state_in,
+                     raw ? b.events : nullptr, b.chunk_cnt, nchunks);
+  hipLaunchKernelGGL(k_sweep_offsets, dim3(n), dim3(64 * RG_MAXK), 0, s, g, b.chunk_cnt, nchunks, b.chunk_off,
+                     d_n_raw);
+  if (!raw) return;
+  hipLaunchKernelGGL(k_sweep_emit, dim3(cdiv(T, RG_THREADS), n), dim3(RG_THREADS), 0, s, b.events, T, g, start,
+                     duration, step, b.chunk_off, nchunks, d_raw_off, raw);
+  hipLaunchKernelGGL(k_sweep_clean, dim3(n * RG_MAXK), dim3(RG_THREADS), 0, s, g, d_n_raw, d_raw_off, raw, clean,
+                     d_n_clean);
+}
+
+}  // namespace pa
+
+extern "C" {
+
+int pa_regions_sweep_groups(int K, int L, const int32_t* lane_class) {
+  if (K <= 0 || K > pa::RG_MAXK || L < 0 || (L > 0 && !lane_class)) return -1;
+  int per_class[pa::RG_MAXK] = {0};
+  for (int l = 0; l < L; ++l) {
+    if (lane_class[l] < 0 || lane_class[l] >= K) return -1;
+    ++per_class[lane_class[l]];
+  }
+  int groups = 0;
+  for (int k = 0; k < K; ++k) groups += pa::cdiv(per_class[k], pa::RG_MAXK);
+  return groups;
+}
+
+size_t pa_regions_sweep_workspace_bytes(int T, int groups, int groups_per_launch, int L, int M, long raw_rows,
+                                        long job_rows) {
+  if (T < 2 || groups < 0 || groups_per_launch < 0 || L < 0 || M < 0 || raw_rows < 0 || job_rows < 0) return 0;
+  return pa::sweep_fixed_bytes(groups, L, M, raw_rows, job_rows) +
+         (size_t)groups_per_launch * pa::sweep_group_bytes(T);
+}
+
+int pa_regions_sweep_count(const float* scores, int T, int K, int L, const int32_t* lane_class, const float* onset,
+                           const float* offset, int32_t* n_raw, int32_t* launches, void* workspace,
+                           size_t workspace_bytes, void* stream) {
+  const char* who = "pa_regions_sweep_count";
+  if (launches) *launches = 0;
+  if (int rc = pa::sweep_check_lanes(who, T, K, L, lane_class, onset, offset)) return rc;
+  PA_REQUIRE(L == 0 || n_raw, "%s: null count array", who);
+  for (int l = 0; l < L; ++l) n_raw[l] = 0;
+  if (T < 2 || L == 0) return 0;      // the reference has no defined result for fewer than two frames
+  PA_REQUIRE(scores, "%s: null scores", who);
+  std::vector<pa::SweepGroup> groups;
+  pa::sweep_plan(K, L, lane_class, onset, offset, &groups);
+  const int G = (int)groups.size();
+  const size_t fixed = pa::sweep_fixed_bytes(G, L, 0, 0, 0), each = pa::sweep_group_bytes(T);
+  PA_REQUIRE(workspace && workspace_bytes >= fixed + each, "%s: workspace of %zu bytes, at least %zu needed", who,
+             workspace_bytes, fixed + each);
+  const int per = (int)std::min<size_t>(std::min(G, 65535), (workspace_bytes - fixed) / each);   // (grid.y)
+  hipStream_t s = (hipStream_t)stream;
+  char* p = (char*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
+  pa::SweepGroup* d_groups = (pa::SweepGroup*)p;  p += pa::sw_up(sizeof(pa::SweepGroup) * (size_t)G);
+  int* d_n_raw = (int*)p;                         p += 3 * pa::sw_up(4 * ((size_t)L + 1));
+  const pa::SweepBatch b = pa::sweep_batch(p, T, per);
+  if (hipMemcpyAsync(d_groups, groups.data(), sizeof(pa::SweepGroup) * (size_t)G, hipMemcpyHostToDevice, s) !=
+      hipSuccess) {
+    pa::set_error("%s: uploading the lane tables failed", who);
+    return 1;
+  }
+  {
+    pa::ProfScope prof("k_regions_sweep_count", stream, 4.0 * T * G * 16, 12.0 * T * G);
+    for (int g0 = 0; g0 < G; g0 += per) {
+      pa::sweep_launch_batch(s, scores, T, K, d_groups, g0, std::min(per, G - g0), b, d_n_raw, 0.0, 0.0, 0.0, nullptr,
+                             nullptr, nullptr, nullptr);
+      PA_CHECK_LAUNCH(who);
+      if (launches) ++*launches;
+    }
+  }
+  // the one read-back the row buffers are sized from (it also keeps `groups` alive until the upload has happened)
+  if (hipMemcpyAsync(n_raw, d_n_raw, sizeof(int32_t) * (size_t)L, hipMemcpyDeviceToHost, s) != hipSuccess ||
+      hipStreamSynchronize(s) != hipSuccess) {
+    pa::set_error("%s: reading the region counts back failed: %s", who, hipGetErrorString(hipGetLastError()));
+    return 1;
+  }
+  return 0;
+}
+
+int pa_regions_sweep_emit(const float* scores, int T, int K, int L, const int32_t* lane_class, const float* onset,
+                          const float* offset, const int32_t* n_raw, int M, const int32_t* job_lane,
+                          const double* min_duration_on, const double* min_duration_off, double start, double duration,
+                          double step, long rows, double* regions, int32_t* tracks, int32_t* job_off,
+                          int32_t* launches, void* workspace, size_t workspace_bytes, void* stream) {
+  const char* who = "pa_regions_sweep_emit";
+  if (launches) *launches = 0;
+  if (int rc = pa::sweep_check_lanes(who, T, K, L, lane_class, onset, offset)) return rc;
+  PA_REQUIRE(M >= 0 && rows >= 0, "%s: negative job or row count", who);
+  PA_REQUIRE(M == 0 || (job_lane && min_duration_on && min_duration_off), "%s: null job array", who);
+  PA_REQUIRE(job_off, "%s: null offset table", who);
+  PA_REQUIRE(start == start && duration == duration && step == step, "%s: the frame grid has a NaN", who);
+  for (int j = 0; j < M; ++j) {
+    PA_REQUIRE(job_lane[j] >= 0 && job_lane[j] < L, "%s: job %d names lane %d, 0..%d exist", who, j, job_lane[j],
+               L - 1);
+    PA_REQUIRE(min_duration_on[j] == min_duration_on[j] && min_duration_off[j] == min_duration_off[j],
+               "%s: a duration of job %d is NaN", who, j);
+  }
+  hipStream_t s = (hipStream_t)stream;
+  if (T < 2 || L == 0 || M == 0) {
+    if (hipMemsetAsync(job_off, 0, sizeof(int32_t) * ((size_t)M + 1), s) != hipSuccess) {
+      pa::set_error("%s: hipMemsetAsync failed", who);
+      return 1;
+    }
+    return 0;
+  }
+  PA_REQUIRE(scores && n_raw, "%s: null scores / raw counts", who);
+  std::vector<int32_t> raw_off((size_t)L + 1, 0);
+  long raw_rows = 0, job_rows = 0;
+  for (int l = 0; l < L; ++l) {
+    PA_REQUIRE(n_raw[l] >= 0 && n_raw[l] <= T / 2, "%s: lane %d is given %d raw regions, 0..%d possible", who, l,
+               n_raw[l], T / 2);
+    raw_rows += n_raw[l];
+    PA_REQUIRE(raw_rows <= 0x7fffffffL, "%s: more than 2^31 - 1 raw regions: sweep fewer lanes per call", who);
+    raw_off[l + 1] = (int32_t)raw_rows;
+  }
+  std::vector<pa::SweepJob> jobs((size_t)M);
+  for (int j = 0; j < M; ++j) {
+    jobs[j] = pa::SweepJob{min_duration_on[j], min_duration_off[j], job_lane[j], (int32_t)job_rows};
+    job_rows += n_raw[job_lane[j]];
+    PA_REQUIRE(job_rows <= 0x7fffffffL, "%s: more than 2^31 - 1 job rows: sweep fewer jobs per call", who);
+  }
+  PA_REQUIRE(rows >= job_rows && (regions || job_rows == 0), "%s: room for %ld rows, %ld needed", who, rows, job_rows);
+  std::vector<pa::SweepGroup> groups;
+  pa::sweep_plan(K, L, lane_class, onset, offset, &groups);
+  const int G = (int)groups.size();
+  const size_t fixed = pa::sweep_fixed_bytes(G, L, M, raw_rows, job_rows), each = pa::sweep_group_bytes(T);
+  PA_REQUIRE(workspace && workspace_bytes >= fixed + each, "%s: workspace of %zu bytes, at least %zu needed", who,
+             workspace_bytes, fixed + each);
+  const int per = (int)std::min<size_t>(std::min(G, 65535), (workspace_bytes - fixed) / each);   // (grid.y)
+  char* p = (char*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
+  pa::SweepGroup* d_groups = (pa::SweepGroup*)p;  p += pa::sw_up(sizeof(pa::SweepGroup) * (size_t)G);
+  int* d_n_raw = (int*)p;                         p += pa::sw_up(4 * ((size_t)L + 1));
+  int* d_raw_off = (int*)p;                       p += pa::sw_up(4 * ((size_t)L + 1));
+  int* d_n_clean = (int*)p;                       p += pa::sw_up(4 * ((size_t)L + 1));
+  double* raw = (double*)p;                       p += pa::sw_up(16 * (size_t)raw_rows);
+  double* clean = (double*)p;                     p += pa::sw_up(16 * (size_t)raw_rows);
+  pa::SweepJob* d_jobs = (pa::SweepJob*)p;        p += pa::sw_up(sizeof(pa::SweepJob) * (size_t)M);
+  int* d_n_merged = (int*)p;                      p += pa::sw_up(4 * ((size_t)M + 1));
+  int* d_counts = (int*)p;                        p += pa::sw_up(4 * ((size_t)M + 1));
+  double* scratch = (double*)p;                   p += pa::sw_up(16 * (size_t)job_rows);
+  const pa::SweepBatch b = pa::sweep_batch(p, T, per);
+  if (hipMemcpyAsync(d_groups, groups.data(), sizeof(pa::SweepGroup) * (size_t)G, hipMemcpyHostToDevice, s) !=
+          hipSuccess ||
+      hipMemcpyAsync(d_raw_off, raw_off.data(), 4 * ((size_t)L + 1), hipMemcpyHostToDevice, s) != hipSuccess ||
+      hipMemcpyAsync(d_jobs, jobs.data(), sizeof(pa::SweepJob) * (size_t)M, hipMemcpyHostToDevice, s) != hipSuccess) {
+    pa::set_error("%s: uploading the lane and job tables failed", who);
+    return 1;
+  }
+  {
+    pa::ProfScope prof("k_regions_sweep_emit", stream, 4.0 * T * G * 16, 16.0 * T * G + 48.0 * job_rows);
+    for (int g0 = 0; g0 < G; g0 += per) {
+      pa::sweep_launch_batch(s, scores, T, K, d_groups, g0, std::min(per, G - g0), b, d_n_raw, start, duration, step,
+                             d_raw_off, raw, clean, d_n_clean);
+      PA_CHECK_LAUNCH(who);
+      if (launches) ++*launches;
+    }
+    hipLaunchKernelGGL(pa::k_sweep_merge, dim3(M), dim3(pa::RG_THREADS), 0, s, d_jobs, d_n_clean, d_raw_off, clean,
+                       scratch, d_n_merged, d_counts);
+    hipLaunchKernelGGL(pa::k_sweep_job_offsets, dim3(1), dim3(64), 0, s, d_counts, M, job_off);
+    hipLaunchKernelGGL(pa::k_sweep_remove, dim3(M), dim3(pa::RG_THREADS), 0, s, d_jobs, scratch, d_n_merged, job_off,
+                       (int)std::min<long>(rows, 0x7fffffffL), regions, tracks);
+    PA_CHECK_LAUNCH(who);
+  }
+  // the host tables above were handed to asynchronous copies: they must outlive them
+  if (hipStreamSynchronize(s) != hipSuccess) {
+    pa::set_error("%s: the stream failed: %s", who, hipGetErrorString(hipGetLastError()));
+    return 1;
+  }
+  return 0;
+}
+
+}  // extern "C"

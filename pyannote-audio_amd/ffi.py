@@ -249,6 +249,14 @@ _OPTIONAL: list[tuple] = [
     ("pa_binarize_regions_workspace_bytes", [C.c_int, C.c_int, C.c_int], C.c_size_t),
     ("pa_binarize_regions", [c_fp, C.c_int, C.c_int, c_fp, c_fp, c_fp, c_fp, C.c_double, C.c_double, C.c_double,
                              C.c_int, c_fp, c_fp, c_fp, c_fp, C.c_size_t, c_fp], C.c_int),
+    ("pa_regions_sweep_groups", [C.c_int, C.c_int, c_fp], C.c_int),
+    ("pa_regions_sweep_workspace_bytes", [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_long, C.c_long],
+     C.c_size_t),
+    ("pa_regions_sweep_count", [c_fp, C.c_int, C.c_int, C.c_int, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, C.c_size_t,
+                                c_fp], C.c_int),
+    ("pa_regions_sweep_emit", [c_fp, C.c_int, C.c_int, C.c_int, c_fp, c_fp, c_fp, c_fp, C.c_int, c_fp, c_fp, c_fp,
+                               C.c_double, C.c_double, C.c_double, C.c_long, c_fp, c_fp, c_fp, c_fp, c_fp, C.c_size_t,
+                               c_fp], C.c_int),
     ("pa_resample_poly", [c_fp, C.c_long, c_fp, C.c_int, C.c_int, C.c_int, C.c_int, c_fp, C.c_long, c_fp],
      C.c_int),
     ("pa_plda_transform", [c_fp, C.c_int, C.c_int, C.c_int, C.c_int, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp],

@@ -150,6 +150,228 @@ def binarize_regions(scores: torch.Tensor, frames: SlidingWindow, onset, offset,
     return out, [packed_tracks[bounds[k]:bounds[k + 1]] for k in range(K)]
 
 
+#: default budget of `binarize_regions_sweep`'s device workspace (event words, chunk tables and row buffers)
+SWEEP_WORKSPACE_BYTES = 1 << 30
+_SEGMENT_PRECISION = 1e-6
+
+
+def _sweep_tables(K, lane_class, onset, offset, job_lane, min_duration_on, min_duration_off):
+    """the host arrays of a sweep, checked as the kernel's entry points check them"""
+    lane_class = np.ascontiguousarray(lane_class, dtype=np.int32).reshape(-1)
+    L = len(lane_class)
+    on = np.ascontiguousarray(np.broadcast_to(np.asarray(onset, dtype=np.float32), (L,)))
+    off = np.ascontiguousarray(np.broadcast_to(np.asarray(offset, dtype=np.float32), (L,)))
+    job_lane = np.ascontiguousarray(job_lane, dtype=np.int32).reshape(-1)
+    M = len(job_lane)
+    d_on = np.ascontiguousarray(np.broadcast_to(np.asarray(min_duration_on, dtype=np.float64), (M,)))
+    d_off = np.ascontiguousarray(np.broadcast_to(np.asarray(min_duration_off, dtype=np.float64), (M,)))
+    if not 1 <= K <= 16:
+        raise ValueError(f"binarize_regions_sweep: {K} classes, 1..16 supported")
+    if L and (lane_class.min() < 0 or lane_class.max() >= K):
+        raise ValueError(f"binarize_regions_sweep: a lane names a class outside 0..{K - 1}")
+    if M and (job_lane.min() < 0 or job_lane.max() >= L):
+        raise ValueError(f"binarize_regions_sweep: a job names a lane outside 0..{L - 1}")
+    if np.isnan(on).any() or np.isnan(off).any() or np.isnan(d_on).any() or np.isnan(d_off).any():
+        raise ValueError("binarize_regions_sweep: a threshold or a duration is NaN")
+    return lane_class, on, off, job_lane, d_on, d_off
+
+
+def _lane_regions_host(y: np.ndarray, frames: SlidingWindow, onset: np.float32, offset: np.float32) -> np.ndarray:
+    """one lane on the host: the regions of column `y` before merging, empty ones dropped -> (n, 2) float64.
+    Every frame is one of four maps of the state (keep, set, clear, swap): the state is the value of the last set /
+    clear frame, flipped once per swap since."""
+    T = len(y)
+    if T < 2:
+        return np.zeros((0, 2))
+    with np.errstate(invalid="ignore"):
+        above, below = y > onset, y < offset                 # float32 comparisons; NaN: both false
+    turn_on, turn_off = above & ~below, below & ~above
+    swap = above & below
+    turn_on[0], turn_off[0], swap[0] = above[0], not above[0], False      # frame 0 sets the state
+    idx = np.arange(T)
+    last = np.maximum.accumulate(np.where(turn_on | turn_off, idx, 0))
+    flips = np.cumsum(swap)
+    active = turn_on[last] ^ (((flips - flips[last]) & 1) == 1)
+    before = np.concatenate([[False], active[:-1]])
+    opens = np.flatnonzero(active & ~before)
+    closes = np.flatnonzero(~active & before)
+    if active[-1]:
+        closes = np.append(closes, T - 1)
+
+    def middle(i):
+        s = float(frames.start) + i.astype(np.float64) * float(frames.step)
+        return 0.5 * (s + (s + float(frames.duration)))
+
+    rows = np.stack([middle(opens), middle(closes)], axis=1)
+    return rows[(rows[:, 1] - rows[:, 0]) > _SEGMENT_PRECISION]
+
+
+def _job_regions_host(rows: np.ndarray, min_duration_on: float, min_duration_off: float):
+    """`Annotation.support(min_duration_off)` and the min_duration_on removal on a lane's rows -> rows, positions"""
+    positions = np.zeros(len(rows), dtype=np.int32)
+    if min_duration_off > 0.0 and len(rows):
+        gap = rows[1:, 0] - rows[:-1, 1]
+        gap = np.where(gap > _SEGMENT_PRECISION, gap, 0.0)
+        head = np.concatenate([[True], ~(gap < min_duration_off)])
+        tail = np.concatenate([head[1:], [True]])
+        rows = np.stack([rows[head, 0], rows[tail, 1]], axis=1)
+        positions = np.arange(len(rows), dtype=np.int32)
+    if min_duration_on > 0.0 and len(rows):
+        length = rows[:, 1] - rows[:, 0]
+        keep = ~(np.where(length > _SEGMENT_PRECISION, length, 0.0) < min_duration_on)
+        rows, positions = rows[keep], positions[keep]
+    return rows, positions
+
+
+def _sweep_host(scores: np.ndarray, frames, lane_class, on, off, job_lane, d_on, d_off):
+    lanes = {}
+    rows, tracks = [], []
+    for lane, a, b in zip(job_lane.tolist(), d_on.tolist(), d_off.tolist()):
+        if lane not in lanes:                # the hysteresis of a lane runs once, however many jobs read it
+            lanes[lane] = _lane_regions_host(scores[:, lane_class[lane]], frames, on[lane], off[lane])
+        r, t = _job_regions_host(lanes[lane], a, b)
+        rows.append(r)
+        tracks.append(t)
+    offsets = np.concatenate([[0], np.cumsum([len(r) for r in rows])]).astype(np.int64)
+    packed = np.concatenate(rows) if rows else np.zeros((0, 2))
+    packed_tracks = np.concatenate(tracks) if tracks else np.zeros(0, dtype=np.int32)
+    return np.ascontiguousarray(packed, dtype=np.float64).reshape(-1, 2), packed_tracks.astype(np.int32), offsets
+
+
+def _sweep_workspace(lib, x, groups, L, M, raw_rows, job_rows, budget):
+    """the fixed part and as many groups' event words and chunk tables as the budget holds (at least one group's)"""
+    T = x.shape[0]
+    fixed = int(lib.pa_regions_sweep_workspace_bytes(T, groups, 0, L, M, raw_rows, job_rows))
+    each = int(lib.pa_regions_sweep_workspace_bytes(T, groups, 1, L, M, raw_rows, job_rows)) - fixed
+    nbytes = fixed + max(1, min(groups, budget // max(each, 1))) * each
+    return torch.empty(nbytes, dtype=torch.uint8, device=x.device), nbytes
+
+
+def _sweep_count(x, lane_class, on, off, budget, stats) -> np.ndarray:
+    """the counting phase: regions of every lane before any clean-up (one read-back)"""
+    lib = ffi.load()
+    T, K = x.shape
+    L = len(lane_class)
+    n_raw = np.zeros(L, dtype=np.int32)
+    if T < 2 or L == 0:
+        return n_raw
+    groups = int(lib.pa_regions_sweep_groups(K, L, lane_class.ctypes.data))
+    launches = np.zeros(1, dtype=np.int32)
+    ws, nbytes = _sweep_workspace(lib, x, groups, L, 0, 0, 0, budget)
+    ffi.check(lib.pa_regions_sweep_count(ffi.ptr(x), T, K, L, lane_class.ctypes.data, on.ctypes.data,
+                                         off.ctypes.data, n_raw.ctypes.data, launches.ctypes.data, ffi.ptr(ws),
+                                         nbytes, ffi.stream()), "pa_regions_sweep_count")
+    stats["count_launches"] += int(launches[0])
+    return n_raw
+
+
+def _sweep_emit(x, frames, lane_class, on, off, n_raw, job_lane, d_on, d_off, want_tracks, budget, stats):
+    """the emitting phase for some lanes and their jobs -> device rows, tracks, host job counts"""
+    lib = ffi.load()
+    T, K = x.shape
+    dev = x.device
+    L, M = len(lane_class), len(job_lane)
+    n_raw = np.ascontiguousarray(n_raw, dtype=np.int32)
+    raw_rows = int(n_raw.sum(dtype=np.int64))
+    rows = int(n_raw[job_lane].sum(dtype=np.int64))
+    regions = torch.empty((rows, 2), dtype=torch.float64, device=dev)
+    tracks = torch.empty(rows, dtype=torch.int32, device=dev) if want_tracks else None
+    job_off = torch.empty(M + 1, dtype=torch.int32, device=dev)
+    launches = np.zeros(1, dtype=np.int32)
+    ws, nbytes = None, 0
+    if T >= 2 and L and M:
+        groups = int(lib.pa_regions_sweep_groups(K, L, lane_class.ctypes.data))
+        ws, nbytes = _sweep_workspace(lib, x, groups, L, M, raw_rows, rows, budget)
+    ffi.check(lib.pa_regions_sweep_emit(
+        ffi.ptr(x) if x.numel() else None, T, K, L, lane_class.ctypes.data, on.ctypes.data, off.ctypes.data,
+        n_raw.ctypes.data, M, job_lane.ctypes.data, d_on.ctypes.data, d_off.ctypes.data, float(frames.start),
+        float(frames.duration), float(frames.step), rows, ffi.ptr(regions) if rows else None,
+        ffi.ptr(tracks) if rows and want_tracks else None, ffi.ptr(job_off), launches.ctypes.data, ffi.ptr(ws), nbytes,
+        ffi.stream()), "pa_regions_sweep_emit")
+    stats["emit_launches"] += int(launches[0])
+    stats["calls"] += 1
+    offsets = job_off.cpu().numpy().astype(np.int64)
+    total = int(offsets[-1])
+    return regions[:total], (tracks[:total] if want_tracks else None), np.diff(offsets)
+
+
+def binarize_regions_sweep(scores, frames: SlidingWindow, lane_class, onset, offset, job_lane, min_duration_on=0.0,
+                           min_duration_off=0.0, return_tracks: bool = False, to_host: bool = True,
+                           workspace_bytes: int = SWEEP_WORKSPACE_BYTES, stats: Optional[dict] = None):
+    """The region lists of many detectors on one aggregated (T, K) float32 score array (`pa_regions_sweep_count` /
+    `pa_regions_sweep_emit`, csrc/regions_sweep.hip).  A lane is (class, onset, offset) -- float32 thresholds, scalars
+    are shared --, a job is (lane, min_duration_on, min_duration_off); job j's rows are bit for bit what
+    `binarize_regions` returns for column `lane_class[job_lane[j]]` with the job's four parameters.
+
+    `to_host=True`: a list of M (n_j, 2) float64 arrays (and, with `return_tracks`, M int32 arrays of track
+    positions).  `to_host=False`: (rows (N, 2) float64, tracks (N,) int32 or None, offsets (M + 1,) int64 numpy):
+    the packed rows stay on the scores' device, job j owns rows offsets[j]:offsets[j + 1].
+
+    `workspace_bytes` bounds the device scratch: lane groups are split over several launch sequences, and lanes over
+    several calls, when the event words (4 T bytes per group of 16 lanes) or the row buffers exceed it; results do
+    not depend on the split.  `stats`, when given, receives the number of launch sequences and calls.
+
+    Scores on the CPU (tensor or array) go through a numpy form of the same rule."""
+    on_gpu = isinstance(scores, torch.Tensor) and scores.is_cuda
+    if isinstance(scores, torch.Tensor):
+        if scores.dim() != 2 or scores.dtype != torch.float32:
+            raise ValueError("binarize_regions_sweep expects a (frames, classes) float32 array")
+        x = scores.contiguous() if on_gpu else scores.numpy()
+    else:
+        x = np.asarray(scores)
+        if x.ndim != 2 or x.dtype != np.float32:
+            raise ValueError("binarize_regions_sweep expects a (frames, classes) float32 array")
+    T, K = x.shape
+    lane_class, on, off, job_lane, d_on, d_off = _sweep_tables(K, lane_class, onset, offset, job_lane,
+                                                               min_duration_on, min_duration_off)
+    L, M = len(lane_class), len(job_lane)
+    stats = stats if stats is not None else {}
+    stats.update({"count_launches": 0, "emit_launches": 0, "calls": 0})
+    if not on_gpu:
+        rows, tracks, offsets = _sweep_host(x, frames, lane_class, on, off, job_lane, d_on, d_off)
+        if not to_host:
+            return torch.from_numpy(rows), (torch.from_numpy(tracks) if return_tracks else None), offsets
+    else:
+        with torch.cuda.device(x.device):
+            budget = int(workspace_bytes)
+            n_raw = _sweep_count(x, lane_class, on, off, budget, stats)
+            # lanes are taken in order, as many per call as keep the row buffers (raw and cleaned rows of the lane,
+            # merged rows and output rows of each of its jobs: 16 bytes a row) under the budget
+            per_lane = 16 * n_raw.astype(np.int64) * (2 + 2 * np.bincount(job_lane, minlength=L)[:L])
+            parts, lo = [], 0
+            while lo < L or not parts:
+                hi, used = lo, 0
+                while hi < L and (hi == lo or used + per_lane[hi] <= budget):
+                    used += per_lane[hi]
+                    hi += 1
+                picked = np.flatnonzero((job_lane >= lo) & (job_lane < hi))
+                r, t, n = _sweep_emit(x, frames, lane_class[lo:hi], on[lo:hi], off[lo:hi], n_raw[lo:hi],
+                                      np.ascontiguousarray(job_lane[picked] - lo), d_on[picked], d_off[picked],
+                                      return_tracks, budget, stats)
+                parts.append((picked, r, t, n))
+                lo = max(hi, lo + 1)
+            counts = np.zeros(M, dtype=np.int64)
+            for picked, _, _, n in parts:
+                counts[picked] = n
+            offsets = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+            if len(parts) == 1 and np.array_equal(parts[0][0], np.arange(M)):
+                rows, tracks = parts[0][1], parts[0][2]
+            else:       # back into job order: where every row of the calls' outputs goes
+                where = np.concatenate([np.concatenate([np.arange(offsets[j], offsets[j + 1]) for j in picked] or
+                                                       [np.zeros(0, dtype=np.int64)]) for picked, _, _, _ in parts])
+                order = torch.from_numpy(np.argsort(where, kind="stable")).to(x.device)
+                rows = torch.cat([r for _, r, _, _ in parts])[order]
+                tracks = torch.cat([t for _, _, t, _ in parts])[order] if return_tracks else None
+        if not to_host:
+            return rows, tracks, offsets
+        rows = rows.cpu().numpy()
+        tracks = tracks.cpu().numpy() if return_tracks else None
+    out = [rows[offsets[j]:offsets[j + 1]] for j in range(M)]
+    if not return_tracks:
+        return out
+    return out, [tracks[offsets[j]:offsets[j + 1]] for j in range(M)]
+
+
 @ffi.on_device(lambda scores, *a, **k: scores.device)
 def binarize(scores: torch.Tensor, onset: float = 0.5, offset: float | None = None,
              initial_state: bool | None = None) -> torch.Tensor:

@@ -24,6 +24,26 @@ from .pipeline import ParamDict, Pipeline, Uniform
 from .speaker_verification import PipelineModel, get_model
 
 
+def regions_to_annotation(regions, positions, classes, uri) -> Annotation:
+    """per-class region lists (n_k, 2) and track positions -> the Annotation `Binarize` gives class by class"""
+    # track names as Binarize / support leave them: each class is binarized on its own, so its tracks restart
+    # from the first generated name; `support` (min_duration_off > 0) names the merged regions in time order
+    # before the short ones are deleted, otherwise every region keeps the class's single track name
+    num_names = 1 + max((int(p.max()) for p in positions if len(p)), default=0)
+    names = np.array(list(islice(string_generator(), num_names)), dtype=object)
+    tracks = np.concatenate([names[p] for p in positions]).tolist()
+    labels = np.repeat(np.array(classes, dtype=object), [len(r) for r in regions]).tolist()
+    times = np.concatenate(regions)
+    if hasattr(Annotation, "from_columns"):
+        return Annotation.from_columns(times[:, 0], times[:, 1], tracks, labels, uri=uri)
+    # the real pyannote.core.Annotation (re-exported by core.py when it is importable) has no columnar constructor
+    from .core import Segment
+    detection = Annotation(uri=uri)
+    for (start, end), track, label in zip(times.tolist(), tracks, labels):
+        detection[Segment(start, end), track] = label
+    return detection
+
+
 class MultiLabelSegmentation(Pipeline):
     """Hyper-parameters: `thresholds[label]` = onset, offset [, min_duration_on, min_duration_off]; the two
     durations are top-level and shared between labels when `share_min_duration`."""
@@ -121,22 +141,7 @@ class MultiLabelSegmentation(Pipeline):
         regions, positions = frame_ops.binarize_regions(
             scores, frames, self._onset, self._offset, self._min_duration_on, self._min_duration_off,
             return_tracks=True)
-        # track names as Binarize / support leave them: each class is binarized on its own, so its tracks restart
-        # from the first generated name; `support` (min_duration_off > 0) names the merged regions in time order
-        # before the short ones are deleted, otherwise every region keeps the class's single track name
-        num_names = 1 + max((int(p.max()) for p in positions if len(p)), default=0)
-        names = np.array(list(islice(string_generator(), num_names)), dtype=object)
-        tracks = np.concatenate([names[p] for p in positions]).tolist()
-        labels = np.repeat(np.array(self._classes, dtype=object), [len(r) for r in regions]).tolist()
-        times = np.concatenate(regions)
-        if hasattr(Annotation, "from_columns"):
-            return Annotation.from_columns(times[:, 0], times[:, 1], tracks, labels, uri=uri)
-        # the real pyannote.core.Annotation (re-exported by core.py when it is importable) has no columnar constructor
-        from .core import Segment
-        detection = Annotation(uri=uri)
-        for (start, end), track, label in zip(times.tolist(), tracks, labels):
-            detection[Segment(start, end), track] = label
-        return detection
+        return regions_to_annotation(regions, positions, self._classes, uri)
 
     def get_metric(self):
         raise NotImplementedError(

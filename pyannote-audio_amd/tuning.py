@@ -1,4 +1,5 @@
-"""Tuning the clustering of a `SpeakerDiarization` pipeline on a corpus: the search the reference's `optimize` command
+"""Tuning on a corpus.  `DetectionTuner` (second half of this file) tunes the thresholds of the detection pipelines;
+`ClusteringTuner` the clustering of a `SpeakerDiarization` pipeline on a corpus: the search the reference's `optimize` command
 runs (src/pyannote/audio/__main__.py:116-283 -- the pipeline applied to every development file again for every
 candidate `clustering.threshold` / `min_cluster_size`), organised so that a candidate only pays for what depends on it.
 
@@ -246,6 +247,429 @@ class ClusteringTuner:
             return components
         computed = metric(file["annotation"], hypothesis, uem=file.get("annotated"), detailed=True)
         return computed if isinstance(computed, dict) else None
+
+
+# ------------------------------------------------------------------------------------ detection thresholds
+@dataclass
+class _Detection:
+    """one file of a detection corpus: its aggregated scores (uploaded once when the pipeline sits on a GPU) and the
+    rows the metric's integrals are taken from"""
+    file: dict
+    scores: object            # (T, K) float32: device tensor, or numpy on the host
+    frames: object
+    ref_labels: list
+    ref_seg: np.ndarray
+    ref_lab: np.ndarray
+    uem_seg: np.ndarray
+    device_rows: dict = field(default_factory=dict)     # the reference and uem rows on the counting device
+
+
+def _ranges(starts: np.ndarray, lengths: np.ndarray) -> np.ndarray:
+    """concatenated arange(starts[i], starts[i] + lengths[i])"""
+    total = int(lengths.sum())
+    if total == 0:
+        return np.zeros(0, dtype=np.int64)
+    first = np.cumsum(lengths) - lengths
+    return np.repeat(starts - first, lengths) + np.arange(total, dtype=np.int64)
+
+
+class DetectionTuner:
+    """`DetectionTuner(pipeline).prepare(files).sweep(onsets, offsets, min_duration_ons, min_duration_offs)` for a
+    `VoiceActivityDetection` or `MultiLabelSegmentation` pipeline -> {"entries": [{"params", "loss"} per candidate],
+    "best": the first optimum in the pipeline's direction, "shared": how many detectors the candidates name and how
+    many hysteresis lanes and duration jobs they were computed from, ...} (`write_config` takes it).
+
+    The whole hyper-parameter set of these pipelines is what the reference's `optimize` searches, so a candidate
+    costs no network and no Annotation: per file, ONE region sweep gives the region lists of all candidates
+    (`frames.binarize_regions_sweep`: distinct (class, onset, offset) triples are lanes, distinct (lane, durations)
+    pairs are jobs, a candidate is one job per class) and ONE counts call gives the metric's integrals of every
+    (file, candidate) (`pa_annot_corpus_counts` with the hypothesis rows where the sweep left them; the host sweep
+    without a device or beyond its limits).  The loss of a candidate is `abs(metric)` after `metric.add_counts` of
+    every file, equal (`==`) to `pipeline.instantiate(params)`, `pipeline(file)` and
+    `metric(file["annotation"], hypothesis, uem=file["annotated"])` per file with the same metric.
+
+    `metric`: a factory of fresh metrics.  Default: `pipeline.get_metric` for VoiceActivityDetection;
+    `annotation_metrics.IdentificationErrorRate` (`MacroAverageFMeasure` with `fscore`) on the pipeline's device for
+    MultiLabelSegmentation, whose `get_metric` needs pyannote.metrics.  A metric without `add_counts` gets
+    Annotations built from the region lists.  `keep_hypotheses`: also keep every candidate's Annotations in
+    `self.hypotheses[candidate][file]`.  The pipeline is left instantiated with the last candidate."""
+
+    #: bound on the workspace of one counts call (44 bytes per cut slot) and on the sweep's
+    workspace_bytes: int = 1 << 30
+
+    def __init__(self, pipeline, metric: Optional[Callable] = None, keep_hypotheses: bool = False):
+        from . import annotation_metrics as am
+        from .multilabel import MultiLabelSegmentation
+        from .voice_activity_detection import VoiceActivityDetection
+        self.pipeline = pipeline
+        self.multilabel = isinstance(pipeline, MultiLabelSegmentation)
+        if not self.multilabel and not isinstance(pipeline, VoiceActivityDetection):
+            raise TypeError("DetectionTuner tunes VoiceActivityDetection and MultiLabelSegmentation pipelines, got "
+                            f"{type(pipeline).__name__}")
+        self.classes = list(pipeline.classes())
+        self.powerset = bool(pipeline._segmentation.model.specifications.powerset)
+        if metric is not None:
+            self.metric = metric
+        elif not self.multilabel:
+            self.metric = pipeline.get_metric
+        elif pipeline.fscore:
+            self.metric = lambda: am.MacroAverageFMeasure(classes=self.classes, device=self._device())
+        else:
+            self.metric = lambda: am.IdentificationErrorRate(device=self._device())
+        self.keep_hypotheses = keep_hypotheses
+        self.prepared: list = []
+        self.hypotheses: list = []
+
+    def _device(self):
+        device = getattr(self.pipeline._segmentation, "device", None)
+        return device if device is not None and device.type == "cuda" else None
+
+    # ------------------------------------------------------------------------------------------ preparation
+    def prepare(self, files: Iterable) -> "DetectionTuner":
+        """every file's aggregated scores, from its training cache or computed (and cached) once, uploaded once when
+        the pipeline sits on a GPU; `pipeline.training` is restored whatever happens"""
+        pipeline = self.pipeline
+        previous = pipeline.training
+        pipeline.training = True
+        try:
+            self.prepared = [self._prepare_one(file) for file in files]
+        finally:
+            pipeline.training = previous
+        return self
+
+    def _prepare_one(self, file) -> _Detection:
+        import torch
+        from . import annotation_metrics as am
+        from collections.abc import MutableMapping
+        pipeline = self.pipeline
+        origin, file = file, pipeline.prepare_one(file)
+        if file.get("annotated") is None:
+            raise ValueError(f"file {file.get('uri')!r} has no 'annotated': the evaluated region would be approximated "
+                             "by the extent of a hypothesis that changes with the candidate")
+        key = pipeline.CACHED_SEGMENTATION
+        if key not in file:
+            if self.multilabel:
+                scores, frames = pipeline._aggregate(file, pipeline.setup_hook(file, None))
+                from .core import SlidingWindowFeature
+                file[key] = SlidingWindowFeature(scores.cpu().numpy(), frames)
+            else:
+                file[key] = pipeline._segmentation(file)
+        cached = file[key]
+        if isinstance(origin, MutableMapping) and key not in origin:     # (`prepare_one` works on a copy)
+            origin[key] = cached
+        data = np.ascontiguousarray(cached.data, dtype=np.float32)
+        if data.ndim != 2 or data.shape[1] != len(self.classes):
+            raise ValueError(f"cached scores of shape {data.shape}, (frames, {len(self.classes)}) expected")
+        device = self._device()
+        scores = torch.from_numpy(data).to(device) if device is not None else data
+        ref_labels, ref_seg, ref_lab = am._rows(file["annotation"])
+        uem_seg = am._uem_rows(file["annotated"])
+        am._check("reference", ref_seg)
+        am._check("uem", uem_seg)
+        return _Detection(file=file, scores=scores, frames=cached.sliding_window, ref_labels=ref_labels,
+                          ref_seg=ref_seg, ref_lab=ref_lab, uem_seg=uem_seg)
+
+    # ------------------------------------------------------------------------------------------- candidates
+    def candidates(self, onsets=None, offsets=None, min_duration_ons=(0.0,), min_duration_offs=(0.0,)) -> tuple:
+        """(parameter dicts of the grid, onsets outermost, then offsets, min_duration_on, min_duration_off; how many
+        grid points were left out because `offset > onset`, which VoiceActivityDetection does not reproduce)"""
+        if self.powerset and not self.multilabel:
+            if onsets is not None or offsets is not None:
+                raise ValueError("the onset and offset of a powerset model are fixed: only the durations are tuned")
+            pairs = [(None, None)]
+        else:
+            if onsets is None:
+                raise ValueError("DetectionTuner.sweep: no onsets")
+            pairs = [(float(a), float(a) if offsets is None else float(b))
+                     for a in onsets for b in ([None] if offsets is None else offsets)]
+        out, skipped = [], 0
+        for onset, offset in pairs:
+            if not self.multilabel and onset is not None and np.float32(offset or onset) > np.float32(onset):
+                skipped += len(min_duration_ons) * len(min_duration_offs)
+                continue
+            for d_on in min_duration_ons:
+                for d_off in min_duration_offs:
+                    d_on, d_off = float(d_on), float(d_off)
+                    if not self.multilabel:
+                        params = {"min_duration_on": d_on, "min_duration_off": d_off}
+                        if onset is not None:
+                            params.update(onset=onset, offset=offset)
+                    elif self.pipeline.share_min_duration:
+                        params = {"thresholds": {c: {"onset": onset, "offset": offset} for c in self.classes},
+                                  "min_duration_on": d_on, "min_duration_off": d_off}
+                    else:
+                        params = {"thresholds": {c: {"onset": onset, "offset": offset, "min_duration_on": d_on,
+                                                     "min_duration_off": d_off} for c in self.classes}}
+                    out.append(params)
+        return out, skipped
+
+    def sweep(self, onsets=None, offsets=None, min_duration_ons=(0.0,), min_duration_offs=(0.0,)) -> dict:
+        """the grid in that nesting order; `offsets=None`: offset = onset; the same values for every class"""
+        candidates, skipped = self.candidates(onsets, offsets, min_duration_ons, min_duration_offs)
+        result = self.evaluate(candidates)
+        result["skipped_offset_above_onset"] = skipped
+        return result
+
+    def _detectors(self, params) -> list:
+        """instantiates the candidate and reads back what the pipeline will binarize with: per class
+        (onset, offset, min_duration_on, min_duration_off), thresholds rounded to float32 (the comparison's type)"""
+        pipeline = self.pipeline
+        if self.multilabel:
+            pipeline.instantiate(params)
+            rows = zip(pipeline._onset, pipeline._offset, pipeline._min_duration_on, pipeline._min_duration_off)
+        else:
+            if self.powerset and ("onset" in params or "offset" in params):
+                raise ValueError("the onset and offset of a powerset model are fixed")
+            pipeline.instantiate(params)
+            binarize = pipeline._binarize
+            rows = [(binarize.onset, binarize.offset, binarize.min_duration_on, binarize.min_duration_off)]
+        out = []
+        for onset, offset, d_on, d_off in rows:
+            values = (float(np.float32(onset)), float(np.float32(offset)), float(d_on), float(d_off))
+            if any(np.isnan(values)):
+                raise ValueError(f"a candidate has a NaN parameter: {params}")
+            if not self.multilabel and values[1] > values[0]:
+                raise ValueError(
+                    f"offset {offset} > onset {onset}: VoiceActivityDetection's Binarize takes a frame between the two "
+                    "as active, where the reference swaps the state; a value tuned there would not reproduce")
+            out.append(values)
+        return out
+
+    # ------------------------------------------------------------------------------------------- evaluation
+    def evaluate(self, candidates: list) -> dict:
+        """any list of parameter dicts (as `pipeline.instantiate` takes them), in order"""
+        if not self.prepared:
+            raise RuntimeError("DetectionTuner: call prepare(files) first")
+        from . import annotation_metrics as am
+        candidates = list(candidates)
+        K = len(self.classes)
+        lanes, jobs, picks = {}, {}, []
+        for params in candidates:
+            pick = []
+            for k, (onset, offset, d_on, d_off) in enumerate(self._detectors(params)):
+                lane = lanes.setdefault((k, onset, offset), len(lanes))
+                pick.append(jobs.setdefault((lane, d_on, d_off), len(jobs)))
+            picks.append(tuple(pick))
+        picks_array = np.array(picks, dtype=np.int64).reshape(len(candidates), K)
+        lane_class = np.array([key[0] for key in lanes], dtype=np.int32)
+        onset = np.array([key[1] for key in lanes], dtype=np.float32)
+        offset = np.array([key[2] for key in lanes], dtype=np.float32)
+        job_lane = np.array([key[0] for key in jobs], dtype=np.int32)
+        d_on = np.array([key[1] for key in jobs], dtype=np.float64)
+        d_off = np.array([key[2] for key in jobs], dtype=np.float64)
+        job_class = lane_class[job_lane] if len(jobs) else np.zeros(0, dtype=np.int32)
+
+        probe = self.metric()
+        by_counts = hasattr(probe, "add_counts") and hasattr(probe, "collar") and hasattr(probe, "skip_overlap")
+        self._counts_device = am._device(getattr(probe, "device", None)) if by_counts else None
+        self._variant = (float(probe.collar), bool(probe.skip_overlap)) if by_counts else None
+        # distinct job tuples: two candidates with the same detectors share their counts
+        distinct = {}
+        entry_of = [distinct.setdefault(pick, len(distinct)) for pick in picks]
+        entry_jobs = np.array(list(distinct), dtype=np.int64).reshape(len(distinct), K)
+
+        metrics = [probe] + [self.metric() for _ in candidates[1:]]
+        self.hypotheses = [[] for _ in candidates] if self.keep_hypotheses else []
+        self.collisions = 0
+        for item in self.prepared:
+            self._evaluate_file(item, (lane_class, onset, offset, job_lane, d_on, d_off), job_class, entry_jobs,
+                                entry_of, metrics, by_counts)
+        entries = [{"params": params, "loss": abs(metric)} for params, metric in zip(candidates, metrics)]
+        direction = self.pipeline.get_direction()
+        return {"entries": entries, "best": best_entry(entries, direction),
+                "shared": {"candidates": len(candidates), "detectors": len(candidates) * K, "lanes": len(lanes),
+                           "jobs": len(jobs), "counted": len(distinct), "collisions": self.collisions}}
+
+    def _evaluate_file(self, item: _Detection, tables, job_class, entry_jobs, entry_of, metrics, by_counts):
+        """one sweep and one counts call for all candidates, then every candidate's metric takes the file"""
+        from . import annotation_metrics as am
+        from . import frames as frame_ops
+        K = len(self.classes)
+        want_tracks = K > 1 or self.keep_hypotheses or not by_counts
+        rows, tracks, offsets = frame_ops.binarize_regions_sweep(
+            item.scores, item.frames, *tables, return_tracks=want_tracks, to_host=False,
+            workspace_bytes=self.workspace_bytes)
+        counts = np.diff(offsets)
+        flagged = self._collisions(rows, tracks, counts, job_class, entry_jobs) if K > 1 else set()
+        self.collisions += sum(1 for e in entry_of if e in flagged)
+        flat = {}
+        host = None
+        if by_counts:
+            todo = [e for e in range(len(entry_jobs)) if e not in flagged]
+            flat = self._counts(item, rows, offsets, counts, entry_jobs, todo)
+        need_annotations = self.keep_hypotheses or not by_counts or flagged
+        if need_annotations:
+            host = (rows.cpu().numpy(), tracks.cpu().numpy())
+        uri = getattr(item.file["annotation"], "uri", None)
+        built = {}
+        for c, (e, metric) in enumerate(zip(entry_of, metrics)):
+            hypothesis = None
+            if self.keep_hypotheses or e not in flat:
+                if e not in built:
+                    built[e] = self._annotation(item, host, offsets, entry_jobs[e])
+                hypothesis = built[e]
+            if e in flat:
+                hyp_labels, values = flat[e]
+                metric.add_counts(am.counts_dict(item.ref_labels, hyp_labels, values), uri=uri)
+            else:
+                metric(item.file["annotation"], hypothesis, uem=item.file["annotated"])
+            if self.keep_hypotheses:
+                self.hypotheses[c].append(hypothesis)
+
+    def _labels(self, k: int):
+        return self.classes[k] if self.multilabel else "SPEECH"
+
+    def _annotation(self, item, host, offsets, picked):
+        """the Annotation the pipeline returns for one candidate, from the sweep's rows"""
+        from .core import Annotation
+        from .multilabel import regions_to_annotation
+        rows, tracks = host
+        regions = [rows[offsets[j]:offsets[j + 1]] for j in picked]
+        positions = [tracks[offsets[j]:offsets[j + 1]] for j in picked]
+        if not sum(len(r) for r in regions):
+            return Annotation(uri=item.file["uri"])
+        return regions_to_annotation(regions, positions, [self._labels(k) for k in range(len(picked))],
+                                     item.file["uri"])
+
+    def _collisions(self, rows, tracks, counts, job_class, entry_jobs) -> set:
+        """entries in which two classes hold a row with equal start, end and track position: the pipeline's
+        Annotation is keyed by (segment, track name), so the later class overwrites the earlier one's row there.
+        Those candidates are scored on the Annotation itself."""
+        import torch
+        if rows.shape[0] == 0:
+            return set()
+        dev = rows.device
+        job_of_row = torch.repeat_interleave(torch.arange(len(counts), device=dev),
+                                             torch.from_numpy(counts).to(dev))
+        cls = torch.from_numpy(job_class.astype(np.int64)).to(dev)[job_of_row]
+        keys = torch.cat([rows.contiguous().view(torch.int64), tracks.to(torch.int64)[:, None]], dim=1)
+        # a key held by two classes: distinct (key, class) pairs first, then keys that are left more than once
+        pairs = torch.unique(torch.cat([keys, cls[:, None]], dim=1), dim=0)
+        shared, held = torch.unique(pairs[:, :3], dim=0, return_counts=True)
+        shared = shared[held > 1]
+        if shared.shape[0] == 0:
+            return set()
+        both, inverse = torch.unique(torch.cat([shared, keys]), dim=0, return_inverse=True)
+        is_shared = torch.zeros(both.shape[0], dtype=torch.bool, device=dev)
+        is_shared[inverse[:shared.shape[0]]] = True
+        hit = is_shared[inverse[shared.shape[0]:]]
+        suspects = {}
+        for job, key in zip(job_of_row[hit].cpu().tolist(), inverse[shared.shape[0]:][hit].cpu().tolist()):
+            suspects.setdefault(job, set()).add(key)
+        flagged = set()
+        for e, picked in enumerate(entry_jobs.tolist()):
+            seen = [suspects[j] for j in picked if j in suspects]
+            if len(seen) > 1 and any(a & b for i, a in enumerate(seen) for b in seen[i + 1:]):
+                flagged.add(e)
+        return flagged
+
+    def _counts(self, item: _Detection, rows, offsets, counts, entry_jobs, todo) -> dict:
+        """entry -> (hypothesis labels in `labels()` order, the Kr Kh + Kr + Kh + 7 values of `pa_annot_counts`)"""
+        from . import annotation_metrics as am
+        collar, skip_overlap = self._variant
+        names = [self._labels(k) for k in range(entry_jobs.shape[1])]
+        order = sorted(range(len(names)), key=lambda k: str(names[k]))         # `Annotation.labels()`
+        plans = {}
+        for e in todo:
+            runs = [int(entry_jobs[e, k]) for k in order if counts[entry_jobs[e, k]] > 0]
+            labels = [names[k] for k in order if counts[entry_jobs[e, k]] > 0]
+            plans[e] = (labels, np.array(runs, dtype=np.int64))
+        out = {}
+        device = self._counts_device
+        Nr, Nu, Kr = len(item.ref_seg), len(item.uem_seg), len(item.ref_labels)
+        on_device = [e for e in todo if device is not None and Kr <= am.MAX_LABELS
+                     and 2 * (Nr + Nu + int(counts[plans[e][1]].sum())) + 4 * Nr <= (1 << 22)]
+        if on_device:
+            out.update(self._device_counts(item, rows, offsets, counts, plans, on_device, device, collar,
+                                           skip_overlap))
+        rest = [e for e in todo if e not in out]
+        if rest:
+            host_rows = rows.cpu().numpy()
+            for e in rest:
+                labels, runs = plans[e]
+                seg = np.concatenate([host_rows[offsets[j]:offsets[j + 1]] for j in runs] or [np.zeros((0, 2))])
+                lab = np.repeat(np.arange(len(runs), dtype=np.int32), counts[runs]) if len(runs) \
+                    else np.zeros(0, dtype=np.int32)
+                out[e] = (labels, am._host_counts(item.ref_seg, item.ref_lab, Kr, seg, lab, len(labels), item.uem_seg,
+                                                  collar, skip_overlap))
+        return out
+
+    def _device_counts(self, item, rows, offsets, counts, plans, entries, device, collar, skip_overlap) -> dict:
+        """`pa_annot_corpus_counts` with one corpus entry per (file, candidate): the reference and uem rows repeated
+        on the device, the hypothesis rows where the sweep left them (a job's rows are sorted: runs are plain
+        ranges), only the offset tables built here.  One download per call; calls are chunked at the entry point's
+        limits and at `workspace_bytes`."""
+        import ctypes
+        import torch
+        from . import annotation_metrics as am
+        from . import ffi
+        lib = ffi.load()
+        Nr, Nu, Kr = len(item.ref_seg), len(item.uem_seg), len(item.ref_labels)
+        if device not in item.device_rows:
+            item.device_rows[device] = (torch.from_numpy(np.ascontiguousarray(item.ref_seg)).to(device),
+                                        torch.from_numpy(item.ref_lab.astype(np.int32)).to(device),
+                                        torch.from_numpy(np.ascontiguousarray(item.uem_seg)).to(device))
+        ref_seg, ref_lab, uem_seg = item.device_rows[device]
+        hyp = rows.to(device).contiguous()
+        out = {}
+        Nh = {e: int(counts[plans[e][1]].sum()) for e in entries}
+        slots = {e: 2 * (Nr + Nh[e] + Nu) + 4 * Nr for e in entries}
+        at = 0
+        while at < len(entries):
+            chunk, used = [], 0
+            while at < len(entries) and len(chunk) < 65535 and \
+                    (not chunk or 44 * (used + slots[entries[at]]) + 36 * sum(Nh[e] for e in chunk) <=
+                     self.workspace_bytes):
+                chunk.append(entries[at])
+                used += slots[entries[at]]
+                at += 1
+            F = len(chunk)
+            Kh = [len(plans[e][0]) for e in chunk]
+            runs = np.concatenate([plans[e][1] for e in chunk]) if sum(Kh) else np.zeros(0, dtype=np.int64)
+            host = {"ref_off": np.arange(F + 1, dtype=np.int64) * Nr, "uem_off": np.arange(F + 1, dtype=np.int64) * Nu,
+                    "hyp_off": np.concatenate([[0], np.cumsum([Nh[e] for e in chunk])]),
+                    "cut_off": np.concatenate([[0], np.cumsum([slots[e] for e in chunk])]),
+                    "out_off": np.concatenate([[0], np.cumsum([Kr * k + Kr + k + len(am._SCALARS) for k in Kh])]),
+                    "Kr": np.full(F, Kr), "Kh": np.array(Kh), "run_first": np.concatenate([[0], np.cumsum(Kh)]),
+                    "run_off": np.concatenate([[0], np.cumsum(counts[runs])]),
+                    "run_rows": _ranges(offsets[runs], counts[runs])}
+            if max(int(v.max()) if len(v) else 0 for v in host.values()) > 0x7fffffff:
+                raise ValueError("more rows in one counts call than 32-bit tables index: lower workspace_bytes")
+            host = {name: np.ascontiguousarray(v, dtype=np.int32) for name, v in host.items()}
+            sizes = [len(a) + (len(a) & 1) for a in host.values()]
+            starts = np.concatenate([[0], np.cumsum(sizes)])
+            packed = np.zeros(int(starts[-1]), dtype=np.int32)
+            for a, s in zip(host.values(), starts):
+                packed[s:s + len(a)] = a
+            words = torch.from_numpy(packed).to(device)
+            struct = ffi.AnnotCorpus()
+            struct.F, struct.R = F, int(host["run_first"][-1])
+            # (every entry reads the same reference and uem rows: repeated, so that the offset tables stay offsets)
+            refs, labs, uems = ref_seg.repeat(F, 1), ref_lab.repeat(F), uem_seg.repeat(F, 1)
+            struct.ref_seg = refs.data_ptr() if Nr else None
+            struct.ref_label = labs.data_ptr() if Nr else None
+            struct.uem_seg = uems.data_ptr() if Nu else None
+            struct.hyp_seg = hyp.data_ptr() if hyp.numel() else None
+            struct.hyp_label = None                       # (the kernels label a row by its run)
+            for name, a, s in zip(host, host.values(), starts):
+                setattr(struct, name, words.data_ptr() + 4 * int(s) if len(a) else None)
+            for name in ("ref_off", "hyp_off", "uem_off", "Kr", "Kh"):
+                setattr(struct, "h_" + name, host[name].ctypes.data)
+            with torch.cuda.device(device):
+                ws_bytes = int(lib.pa_annot_corpus_workspace_bytes(ctypes.byref(struct)))
+                if ws_bytes == 0:
+                    raise ValueError("pa_annot_corpus_counts refuses the candidates' tables")
+                ws = torch.empty(ws_bytes, dtype=torch.uint8, device=device)
+                nout = int(host["out_off"][-1])
+                buffer = torch.empty(nout + (F + 1) // 2, dtype=torch.float64, device=device)
+                merged = buffer[nout:].view(torch.int32)
+                ffi.check(lib.pa_annot_corpus_counts(ctypes.byref(struct), 0.0, collar, int(skip_overlap),
+                                                     ffi.ptr(buffer), ffi.ptr(merged), ffi.ptr(ws), ws_bytes,
+                                                     ffi.stream()), "pa_annot_corpus_counts")
+                values = buffer.cpu().numpy()
+            for i, e in enumerate(chunk):
+                out[e] = (plans[e][0], values[host["out_off"][i]:host["out_off"][i + 1]])
+        return out
 
 
 def write_config(config_yml, result: dict, name: str) -> Path:

@@ -28,6 +28,8 @@ class VoiceActivityDetection(Pipeline):
     """Hyper-parameters: onset / offset (fixed to 0.5 for powerset models, whose outputs are already
     hard decisions), min_duration_on, min_duration_off."""
 
+    CACHED_SEGMENTATION = "cache/segmentation/inference"
+
     def __init__(self, segmentation: PipelineModel = None, fscore: bool = False, token=None, cache_dir=None,
                  **inference_kwargs):
         super().__init__()
@@ -76,7 +78,14 @@ class VoiceActivityDetection(Pipeline):
         """-> speech regions, every track labelled "SPEECH" (:161-203)"""
         hook = self.setup_hook(file, hook=hook)
         progress = (lambda **kw: hook("segmentation", None, **kw))
-        speech_scores: SlidingWindowFeature = self._segmentation(file, hook=progress)
+        # in training mode the aggregated scores are kept in the file and reused (:188-195): tuning the thresholds
+        # runs the network once per file, not once per candidate
+        if self.training and self.CACHED_SEGMENTATION in file:
+            speech_scores: SlidingWindowFeature = file[self.CACHED_SEGMENTATION]
+        else:
+            speech_scores = self._segmentation(file, hook=progress)
+            if self.training:
+                file[self.CACHED_SEGMENTATION] = speech_scores
         hook("segmentation", speech_scores)
         if not hasattr(self, "_binarize"):
             self.initialize()
