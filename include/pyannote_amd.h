@@ -245,6 +245,15 @@ int pa_resnet_stem(const float* fbank, int B, int T, int F, const float* w9, con
                    float* out, void* stream);
 int pa_conv3x3(const float* X, int B, int H, int W, int cin, const float* Wg, const float* shift,
                const float* R, float* Y, int cout, int stride, int relu, void* stream);
+/* The entry of a stride-2 BasicBlock in one launch: Y = [relu](conv3x3_s2(X) + shift), bit-identical to
+ * pa_conv3x3(..., stride 2, ...), and the 1x1 stride-2 shortcut Ysc = conv1x1_s2(X) + shift_sc (pa_gemm_tn_s2's result
+ * up to the summation order), whose pixel (2y, 2x) is the 3x3 convolution's centre tap.  Wg: [9][cout][cin], Wsc: the
+ * plain [cout][cin] image.  Refused (return 3, nothing written) unless cin % 16 == 0, cout % 64 == 0, the map has at
+ * least 16 output rows and Y and Ysc do not overlap; pa_conv3x3_s2_sc_supported tells the first three in advance. */
+int pa_conv3x3_s2_sc_supported(int H, int cin, int cout);
+int pa_conv3x3_s2_sc(const float* X, int B, int H, int W, int cin, const float* Wg, const float* shift,
+                     const float* Wsc, const float* shift_sc, float* Y, float* Ysc, int cout, int relu,
+                     void* stream);
 /* the same stride-1 convolution through Winograd F(2x2,3x3).  U is NOT a plain [16][cout][cin] array: it is
  * G g G^T packed as one contiguous 32-KB slab per (32-cout slice, 16-cin stage),
  * [cout/32][cin/16][row = 32 xi + (cout % 32)][slot][4] with xi = 4a + b and channel quad q of the stage at

@@ -34,6 +34,35 @@
 // (0.70 -> 0.79), 20x250 128->256 3.24 -> 2.84 (0.74 -> 0.85); bench.py 752.4 / 753.0 -> 744.9 / 742.6 ms per file.
 // Outputs bit-identical to the parent kernel's: run side by side on every stride-2 launch of the benchmark's pipeline
 // (3 591 chunks per launch, its real activations) 0 of 8.0 G outputs per file differ.
+//
+// SC = 1 (k_conv3x3_s2<4, 1, false, 1> behind pa_conv3x3_s2_sc, emb_resnet.hip): the entry of a stride-2 BasicBlock in
+// one launch.  The block's 1x1 stride-2 shortcut reads pixel (2 y, 2 x) of the same map -- the centre tap (tap 4) of this
+// convolution, which is in LDS in A-fragment layout in every stage -- so it is a TENTH tap with weights and
+// accumulators of its own instead of a k_gemm_tn launch that reads the map again:
+//   * the weight slab has a tenth 4-KB tap (entries 9 * 64 + n, same swizzle, tap and N-tile still ds_read
+//     immediates), filled by each wave's LAST weight piece from the plain [COUT][CIN] shortcut image through a
+//     descriptor of its own: 20 pieces per wave and stage in the run's 27 issue slots, 2 x (38 + 40) KB + the mailbox of
+//     the 160 KB of LDS.  The <2, 2> geometry (Ho < 16: the layer-4 entry) would need 162 KB and keeps its GEMM.
+//   * the run has 16 more MFMAs at its end, on the A fragments of tap 4 (read again) and the B fragments of the new
+//     tap, into acc_sc; no DMA slot of their own.  The nine-tap chain into acc is unchanged: Y keeps its bits.  The
+//     shortcut's chain: 16-channel blocks ascending, 8 k-steps pairing channels q and 8 + q, from zero, shift_sc added
+//     in the epilogue -- not k_gemm_tn's pairing, so Ysc has other last bits than pa_gemm_tn_s2's (measured against the
+//     float64 truth: 0.022 / 0.042 of the contract where the GEMM has 0.021 / 0.052).
+//   * the epilogue stores acc_sc + shift_sc (no ReLU, no residual) to Ysc at Y's offsets: 64 whole-line stores per lane
+//     behind the next tile's staging, so the first-stage wait is vmcnt(63), the largest the encoding has.
+// ISA of that instantiation: 180 VGPRs (147 without the shortcut, 175 with a residual input), 0 AccVGPRs, no scratch, no
+// spilled VGPR; one copy of the run: 160 v_mfma_f32_32x32x2_f32, 60
+// ds_read_b128 (54 inside the run), 20 buffer_load_dwordx4 ... lds in the run + 20 in the prologue, 64 buffer_store_dword,
+// 313 instructions from the run's first MFMA to its last (284 without the shortcut).  The SC = 0 instantiations have the
+// instruction counts they had.
+// Measured, fused against pa_conv3x3(stride 2) + pa_gemm_tn_s2 alternating in one call, 512 chunks per launch, two
+// passes each (profiles/conv_s2_shortcut_ab.txt): 80x998 32->64 4.720 / 4.699 -> 3.925 / 3.926 ms per block entry
+// (convolution 3.42 -> 3.93, GEMM 1.29 -> 0), 40x499 64->128 3.567 / 3.576 -> 3.393 / 3.395 (3.01 -> 3.39, 0.56 -> 0):
+// both shapes keep the fused path.  Per file: k_conv3x3_s2<4, 1> 45.8 -> 51.8 ms, k_gemm_tn<0, 0> 16.7 -> 3.4 ms, 7.3 ms
+// less; bench.py 743.37 / 743.07 -> 734.93 / 737.35 ms per file.  With all 160 KB of LDS taken, a kernel of another
+// stream that needs more than 4 KB of LDS waits for the end of the launch (21.6 ms) instead of running beside it: the
+// pipelined back end of the previous file (rocprim's partition kernel behind torch.nonzero) takes about 270 instead of
+// 190 ms, still hidden behind the 730 ms front end of the next file.
 #include "common.h"
 #include "emb_conv_s2_geom.h"
 
@@ -60,7 +89,16 @@ __device__ __forceinline__ void cs2_barrier() {
 #define CS2_TAIL_WAIT_LIT 32
 static_assert(ConvS2Geom<4, 1>::TILE_STORES == CS2_TAIL_WAIT_LIT && ConvS2Geom<2, 2>::TILE_STORES == CS2_TAIL_WAIT_LIT,
               "the literal of the s_waitcnt string");
-static_assert(ConvS2Geom<4, 1>::NPW <= CS2_SLOTS && ConvS2Geom<2, 2>::NPW <= CS2_SLOTS, "a slot of the MFMA run per piece");
+// With the shortcut folded in (SC = 1) the epilogue issues 64 stores per lane behind the staging -- 32 of each output,
+// unmerged buffer_store_dword again -- and vmcnt encodes 63 at most: vmcnt(63) then waits for the staging AND the
+// oldest of those stores.  Right while at least 63 vector-memory instructions follow the staging.
+#define CS2_TAIL_WAIT_LIT_SC 63
+static_assert(CS2_TAIL_WAIT_LIT_SC <= 63 && ConvS2Geom<4, 1, 1>::TILE_STORES >= CS2_TAIL_WAIT_LIT_SC &&
+                  ConvS2Geom<4, 1, 1>::TILE_STORES == 2 * CS2_TAIL_WAIT_LIT,
+              "the literal of the s_waitcnt string, shortcut folded in: both outputs' stores");
+static_assert(ConvS2Geom<4, 1>::NPW <= CS2_SLOTS && ConvS2Geom<2, 2>::NPW <= CS2_SLOTS &&
+                  ConvS2Geom<4, 1, 1>::NPW <= CS2_SLOTS,
+              "a slot of the MFMA run per piece");
 
 // one LDS-DMA piece: M0 = dst + delta (an immediate, or a scalar for the clamped last patch piece); `voff` = the
 // lane's source offset, `soff` = the stage's channel offset in bytes.  s_add_u32 writes SCC: declared, the compiler
@@ -78,7 +116,7 @@ __device__ __forceinline__ void cs2_piece_s(unsigned dst, int delta, int voff, _
                : "memory", "scc");
 }
 struct Cs2Stage {          // wave-uniform
-  __amdgpu_buffer_rsrc_t xsrd, wsrd;
+  __amdgpu_buffer_rsrc_t xsrd, wsrd, scsrd;   // scsrd: the shortcut's [COUT][CIN] image (SC = 1 only)
   int soff;
   unsigned pdst, wdst;     // LDS byte address of the buffers being filled + 1024 * wave
   int last_delta;          // of the wave's last patch piece (conv_s2_patch_piece)
@@ -87,6 +125,7 @@ template <class G, int N>
 __device__ __forceinline__ void cs2_issue(const Cs2Stage& st, const int (&poff)[G::PPW], const int (&woff)[G::WPW]) {
   if constexpr (N < G::PPW - 1) cs2_piece<4096 * N>(st.pdst, poff[N], st.xsrd, st.soff);
   else if constexpr (N == G::PPW - 1) cs2_piece_s(st.pdst, st.last_delta, poff[N], st.xsrd, st.soff);
+  else if constexpr (G::SC && N == G::NPW - 1) cs2_piece<4096 * (N - G::PPW)>(st.wdst, woff[N - G::PPW], st.scsrd, st.soff);
   else if constexpr (N < G::NPW) cs2_piece<4096 * (N - G::PPW)>(st.wdst, woff[N - G::PPW], st.wsrd, st.soff);
 }
 // (the piece number is a constant after unrolling: the switch folds)
@@ -104,15 +143,19 @@ __device__ __forceinline__ void cs2_issue_n(const int n, const Cs2Stage& st, con
   }
 }
 
-template <int TH, int TWT, bool HAS_R>
+template <int TH, int TWT, bool HAS_R, int SC>
 __global__ __launch_bounds__(256, 2) void k_conv3x3_s2(const float* __restrict__ X, int H, int W, int CIN,
                                                        const float* __restrict__ Wg,
                                                        const float* __restrict__ shift,
                                                        const float* __restrict__ R, float* __restrict__ Y, int Ho,
                                                        int Wo, int COUT, int relu, int tiles_w, int tiles_hw,
                                                        int n_tiles, int total_tiles, int xranges,
-                                                       int* __restrict__ counters) {
-  using G = ConvS2Geom<TH, TWT>;
+                                                       int* __restrict__ counters, const float* __restrict__ Wsc,
+                                                       const float* __restrict__ shift_sc,
+                                                       float* __restrict__ Ysc) {
+  using G = ConvS2Geom<TH, TWT, SC>;
+  static_assert(!(SC && HAS_R), "a block entry has no residual input");
+  constexpr int NT = G::WTAPS;   // taps of the run: tap 9 (SC) is the shortcut, on the A fragments of tap 4
   constexpr int BN = CS2_BN;
   constexpr int OOB = CS2_OOB;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_s2[];
@@ -172,7 +215,8 @@ __global__ __launch_bounds__(256, 2) void k_conv3x3_s2(const float* __restrict__
   for (int k = 0; k < G::PPW; ++k) pl[k] = conv_s2_patch_lane<G>(conv_s2_patch_piece<G>(slw, k), lane, W, CIN);
   int woff[G::WPW];
 #pragma unroll
-  for (int k = 0; k < G::WPW; ++k) woff[k] = conv_s2_w_lane(4 * k + slw, lane, COUT, CIN);
+  for (int k = 0; k < G::WPW; ++k)
+    woff[k] = k < 9 ? conv_s2_w_lane(4 * k + slw, lane, COUT, CIN) : conv_s2_wsc_lane(4 * k + slw, lane, CIN);
   const int last_delta = 1024 * (conv_s2_patch_piece<G>(slw, G::PPW - 1) - slw);
   int poff[G::PPW];      // patch sources of the tile being staged
   auto tile_offsets = [&](const Tile& q) {
@@ -189,10 +233,16 @@ __global__ __launch_bounds__(256, 2) void k_conv3x3_s2(const float* __restrict__
     return __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(Wg + (long)q.n0 * CIN), 0,
                                              live ? (9 * COUT - q.n0) * CIN * 4 : 0, 0x00020000);
   };
-  auto stage_to = [&](int to_buf, __amdgpu_buffer_rsrc_t xs, __amdgpu_buffer_rsrc_t ws, int c0) {
+  auto sc_srd = [&](const Tile& q, bool live) {
+    return __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(SC ? Wsc + (long)q.n0 * CIN : Wg), 0,
+                                             SC && live ? (COUT - q.n0) * CIN * 4 : 0, 0x00020000);
+  };
+  auto stage_to = [&](int to_buf, __amdgpu_buffer_rsrc_t xs, __amdgpu_buffer_rsrc_t ws, __amdgpu_buffer_rsrc_t scs,
+                      int c0) {
     Cs2Stage st;
     st.xsrd = xs;
     st.wsrd = ws;
+    st.scsrd = scs;
     st.soff = c0 * 4;
     st.pdst = lds0 + to_buf * G::PATCH_BYTES + 1024 * slw;
     st.wdst = lds0 + G::W_BASE + to_buf * G::W_BYTES + 1024 * slw;
@@ -209,10 +259,10 @@ __global__ __launch_bounds__(256, 2) void k_conv3x3_s2(const float* __restrict__
     return;
   }
   Tile cur = decode(t0), nxt = cur;
-  __amdgpu_buffer_rsrc_t xcur = x_srd(cur, true), wcur = w_srd(cur, true);
+  __amdgpu_buffer_rsrc_t xcur = x_srd(cur, true), wcur = w_srd(cur, true), sccur = sc_srd(cur, true);
   tile_offsets(cur);
   {
-    const Cs2Stage st = stage_to(0, xcur, wcur, 0);
+    const Cs2Stage st = stage_to(0, xcur, wcur, sccur, 0);
 #pragma unroll
     for (int n = 0; n < G::NPW; ++n) cs2_issue_n<G>(n, st, poff, woff);
   }
@@ -225,22 +275,33 @@ __global__ __launch_bounds__(256, 2) void k_conv3x3_s2(const float* __restrict__
   bool first_tile = true;
 
   for (;;) {
-    f32x16 acc[2];
+    // acc_sc (SC = 1): the shortcut's accumulators.  Its chain: 16-channel blocks ascending, in a block 8 k-steps, step
+    // q = 4 h + c pairing channels q and 8 + q (the two lane halves of a 32x32x2 MFMA); from zero, shift_sc added in
+    // the epilogue.  The nine-tap chain into acc is what it was.
+    f32x16 acc[2], acc_sc[SC ? 2 : 1];
 #pragma unroll
     for (int j = 0; j < 2; ++j)
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[j][r] = 0.f;
+#pragma unroll
+    for (int j = 0; j < (SC ? 2 : 0); ++j)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc_sc[j][r] = 0.f;
     for (int s = 0; s < nst; ++s) {
       const bool last = s == nst - 1;
-      if (s == 0 && !first_tile) asm volatile("s_waitcnt vmcnt(" CS2_STR(CS2_TAIL_WAIT_LIT) ")" ::: "memory");
-      else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      if (s == 0 && !first_tile) {
+        if constexpr (SC) asm volatile("s_waitcnt vmcnt(" CS2_STR(CS2_TAIL_WAIT_LIT_SC) ")" ::: "memory");
+        else asm volatile("s_waitcnt vmcnt(" CS2_STR(CS2_TAIL_WAIT_LIT) ")" ::: "memory");
+      } else {
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      }
       if (last && tid == 0) mail[tpar] = resolve(tq, claim);
       cs2_barrier();
       // what this run stages -- the next 16 channels of this tile, or the first 16 of the next one -- is worked out
       // BEHIND the run's first fragment reads: their LDS latency hides the decoding of the next tile
       Cs2Stage st;
       auto setup = [&]() {
-        __amdgpu_buffer_rsrc_t xs = xcur, ws = wcur;
+        __amdgpu_buffer_rsrc_t xs = xcur, ws = wcur, scs = sccur;
         if (last) {
           tn = __builtin_amdgcn_readfirstlane(mail[tpar]);
           if (tn >= 0) {
@@ -249,8 +310,9 @@ __global__ __launch_bounds__(256, 2) void k_conv3x3_s2(const float* __restrict__
           }
           xs = x_srd(nxt, tn >= 0);
           ws = w_srd(nxt, tn >= 0);
+          scs = sc_srd(nxt, tn >= 0);
         }
-        st = stage_to(buf ^ 1, xs, ws, last ? 0 : (s + 1) * CS2_CB);
+        st = stage_to(buf ^ 1, xs, ws, scs, last ? 0 : (s + 1) * CS2_CB);
       };
 
       {
@@ -258,7 +320,7 @@ __global__ __launch_bounds__(256, 2) void k_conv3x3_s2(const float* __restrict__
         f32x4 fa[2][2], fb[2][2][2];   // [tap parity][h], [tap parity][j][h]
         auto rd = [&](const int tap, const int r, const int par) {
           const int h = r / 3, w = r % 3;
-          if (w == 0) fa[par][h] = cs2_lds_read128(aptr[tap][h]);
+          if (w == 0) fa[par][h] = cs2_lds_read128(aptr[tap < 9 ? tap : 4][h]);
           else fb[par][w - 1][h] = cs2_lds_read128(bptr[h] + tap * 4096 + (w - 1) * 2048);
         };
 #pragma unroll
@@ -267,15 +329,16 @@ __global__ __launch_bounds__(256, 2) void k_conv3x3_s2(const float* __restrict__
         setup();
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-        for (int tap = 0; tap < 9; ++tap) {
+        for (int tap = 0; tap < NT; ++tap) {
           const int par = tap & 1;
 #pragma unroll
           for (int m = 0; m < 16; ++m) {
             const int h = m >> 3, c = (m >> 1) & 3, j = m & 1;
             const float av = fa[par][h][c], bv = fb[par][j][h][c];
-            acc[j] = MFMA32(av, bv, acc[j]);
+            if (tap < 9) acc[j] = MFMA32(av, bv, acc[j]);
+            else acc_sc[SC ? j : 0] = MFMA32(av, bv, acc_sc[SC ? j : 0]);
             __builtin_amdgcn_sched_barrier(0);
-            if (tap + 1 < 9 && (m & 1) == 0 && m < 12) {
+            if (tap + 1 < NT && (m & 1) == 0 && m < 12) {
               rd(tap + 1, m >> 1, par ^ 1);
               __builtin_amdgcn_sched_barrier(0);
             }
@@ -341,6 +404,15 @@ __global__ __launch_bounds__(256, 2) void k_conv3x3_s2(const float* __restrict__
       // (both shift values in front of the first store: a load behind the stores of N-tile 0 is waited for with
       //  vmcnt(0), i.e. behind those stores)
       const float shv[2] = {shift[cur.n0 + li], shift[cur.n0 + 32 + li]};
+      // the shortcut's output (SC = 1): Ysc = acc_sc + shift_sc at the offsets of Y, no ReLU, no residual -- 32 more
+      // whole-line stores per lane, those of an N-tile behind Y's
+      const __amdgpu_buffer_rsrc_t yscsrd = __builtin_amdgcn_make_buffer_rsrc(
+          SC ? Ysc + (long)cur.b * Ho * Wo * COUT : Y, 0, SC ? Ho * Wo * COUT * 4 : 0, 0x00020000);
+      float shsc[2] = {0.f, 0.f};
+      if constexpr (SC) {
+        shsc[0] = shift_sc[cur.n0 + li];
+        shsc[1] = shift_sc[cur.n0 + 32 + li];
+      }
       goffs(0, off[0]);
       gres(off[0], rv[0]);
 #pragma unroll
@@ -356,12 +428,20 @@ __global__ __launch_bounds__(256, 2) void k_conv3x3_s2(const float* __restrict__
           if (relu) v = fmaxf(v, 0.f);
           __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned int, v), ysrd, off[j & 1][r], 0, 0);
         }
+        if constexpr (SC) {
+          const float ss = shsc[j];
+#pragma unroll
+          for (int r = 0; r < 16; ++r)
+            __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned int, acc_sc[j][r] + ss), yscsrd,
+                                                  off[j & 1][r], 0, 0);
+        }
       }
     }
     if (tn < 0) break;
     cur = nxt;
     xcur = x_srd(cur, true);
     wcur = w_srd(cur, true);
+    sccur = sc_srd(cur, true);
     tpar ^= 1;
   }
   if (tid == 0) tq_done(tq, gridDim.x);
@@ -369,10 +449,11 @@ __global__ __launch_bounds__(256, 2) void k_conv3x3_s2(const float* __restrict__
 
 int xcd_ranges_wanted(bool by_default);   // emb_winograd4.hip
 
-template <int TH, int TWT, bool HAS_R>
+template <int TH, int TWT, bool HAS_R, int SC = 0>
 static int launch_conv_s2_r(const float* X, int B, int H, int W, int CIN, const float* Wg, const float* shift,
-                            const float* R, float* Y, int COUT, int relu, hipStream_t st) {
-  using G = ConvS2Geom<TH, TWT>;
+                            const float* R, float* Y, int COUT, int relu, hipStream_t st, const float* Wsc = nullptr,
+                            const float* shift_sc = nullptr, float* Ysc = nullptr) {
+  using G = ConvS2Geom<TH, TWT, SC>;
   const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
   const int tiles_w = cdiv(Wo, G::TW), tiles_h = cdiv(Ho, TH);
   const size_t lds = (size_t)G::LDS_BYTES + 16;   // + the mailbox
@@ -382,7 +463,7 @@ static int launch_conv_s2_r(const float* X, int B, int H, int W, int CIN, const 
   (void)hipGetDevice(&dev);
   if (dev < 0 || dev >= MAXDEV) dev = 0;
   if (!resident_of[dev]) {
-    (void)hipFuncSetAttribute((const void*)k_conv3x3_s2<TH, TWT, HAS_R>, hipFuncAttributeMaxDynamicSharedMemorySize,
+    (void)hipFuncSetAttribute((const void*)k_conv3x3_s2<TH, TWT, HAS_R, SC>, hipFuncAttributeMaxDynamicSharedMemorySize,
                               (int)lds);
     int cus = 256;
     (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
@@ -397,8 +478,9 @@ static int launch_conv_s2_r(const float* X, int B, int H, int W, int CIN, const 
     set_error("pa_conv3x3: cannot allocate the tile counters");
     return 2;
   }
-  hipLaunchKernelGGL((k_conv3x3_s2<TH, TWT, HAS_R>), dim3(grid), dim3(256), lds, st, X, H, W, CIN, Wg, shift, R, Y, Ho,
-                     Wo, COUT, relu, tiles_w, tiles_hw, n_tiles, (int)total, xcd_ranges_wanted(true), counters);
+  hipLaunchKernelGGL((k_conv3x3_s2<TH, TWT, HAS_R, SC>), dim3(grid), dim3(256), lds, st, X, H, W, CIN, Wg, shift, R, Y,
+                     Ho, Wo, COUT, relu, tiles_w, tiles_hw, n_tiles, (int)total, xcd_ranges_wanted(true), counters, Wsc,
+                     shift_sc, Ysc);
   return 0;
 }
 
@@ -411,6 +493,14 @@ int launch_conv_s2(const float* X, int B, int H, int W, int CIN, const float* Wg
                         : launch_conv_s2_r<4, 1, false>(X, B, H, W, CIN, Wg, shift, R, Y, COUT, relu, st);
   return R != nullptr ? launch_conv_s2_r<2, 2, true>(X, B, H, W, CIN, Wg, shift, R, Y, COUT, relu, st)
                       : launch_conv_s2_r<2, 2, false>(X, B, H, W, CIN, Wg, shift, R, Y, COUT, relu, st);
+}
+
+// launcher of pa_conv3x3_s2_sc (emb_resnet.hip): the <4, 1> geometry with the 1x1 stride-2 shortcut as a tenth tap;
+// cin % 16 == 0, cout % 64 == 0, Ho >= 16 (the <2, 2> geometry has no LDS left for the tenth tap)
+int launch_conv_s2_sc(const float* X, int B, int H, int W, int CIN, const float* Wg, const float* shift,
+                      const float* Wsc, const float* shift_sc, float* Y, float* Ysc, int COUT, int relu,
+                      hipStream_t st) {
+  return launch_conv_s2_r<4, 1, false, 1>(X, B, H, W, CIN, Wg, shift, nullptr, Y, COUT, relu, st, Wsc, shift_sc, Ysc);
 }
 
 }  // namespace pa

@@ -18,7 +18,9 @@ constexpr int CS2_OOB = (int)0x80000000;   // a lane offset past every descripto
 // made of 64-byte ENTRIES (16 channels = four 16-byte quads):
 //   patch   (2 TH + 1) input rows x 2 column parities x (TW + 1) columns: entry e = (py * 2 + (px & 1)) * PWH + (px >> 1)
 //           (de-interleaved columns: the 32 lanes of an M-tile, two input columns apart, read consecutive entries);
-//   weights 9 taps x 64 output channels: entry e = tap * 64 + n.
+//   weights 9 taps x 64 output channels: entry e = tap * 64 + n.  With SC = 1 (the block entry's 1x1 stride-2
+//           shortcut folded in: its pixel (2 y, 2 x) is the 3x3 convolution's centre tap) a TENTH 4-KB tap follows,
+//           entries 9 * 64 + n, filled from the plain [COUT][CIN] shortcut image through a descriptor of its own.
 // Bank swizzle.  A fragment read is a ds_read_b128 of quad q = 2 (lane >> 5) + h of entry e0 + (lane & 31).  The
 // hardware serves it in four groups of 16 lanes -- {0-3, 12-15, 20-27}, {4-11, 16-19, 28-31} and the same + 32 --
 // on 64 banks (a 256-byte row = 4 entries).  Every group reads one quad of 16 entries that are distinct mod 16, so
@@ -26,26 +28,31 @@ constexpr int CS2_OOB = (int)0x80000000;   // a lane offset past every descripto
 // e0 is: no padding, no conflicts.
 // The images are WRITTEN by LDS-DMA: piece i (one buffer_load_dwordx4 ... lds of one wave) fills the 1 KB at
 // 1024 i, lane l its 16-byte slot 64 i + l -- the layout is therefore made by the lanes' SOURCE offsets.
-template <int TH_, int TWT_>
+template <int TH_, int TWT_, int SC_ = 0>
 struct ConvS2Geom {
-  static constexpr int TH = TH_, TWT = TWT_, TW = 32 * TWT_;
+  static constexpr int TH = TH_, TWT = TWT_, TW = 32 * TWT_, SC = SC_;
+  static constexpr int WTAPS = 9 + SC_;                    // 4-KB taps of the weight slab
   static constexpr int PH = 2 * TH + 1, PW = 2 * TW + 1;
   static constexpr int PWH = TW + 1;                       // entries per (row, column parity)
   static constexpr int PENT = PH * 2 * PWH;                // patch entries
   static constexpr int PPIECES = (PENT + 15) / 16;         // 1 KB pieces of the patch
-  static constexpr int WPIECES = 9 * CS2_BN / 16;          // ... of the weight slab: 36
+  static constexpr int WPIECES = WTAPS * CS2_BN / 16;      // ... of the weight slab: 36 (SC: 40)
   static constexpr int PPW = (PPIECES + 3) / 4;            // patch pieces per wave (wave w: pieces w, w + 4, ...)
-  static constexpr int WPW = WPIECES / 4;                  // weight pieces per wave: 9
+  static constexpr int WPW = WPIECES / 4;                  // weight pieces per wave: 9 (SC: 10, the last one the shortcut's)
   static constexpr int NPW = PPW + WPW;                    // pieces a wave issues per stage
   static constexpr int PATCH_BYTES = PPIECES * 1024;
   static constexpr int W_BYTES = WPIECES * 1024;
   // [patch 0][patch 1][weights 0][weights 1]: a lane's read pointers move by PATCH_BYTES / W_BYTES between the buffers
   static constexpr int W_BASE = 2 * PATCH_BYTES;
   static constexpr int LDS_BYTES = 2 * (PATCH_BYTES + W_BYTES);
-  static constexpr int TILE_STORES = 2 * 16;               // output stores per lane and tile (two N-tiles x 16 pixels)
+  // output stores per lane and tile (two N-tiles x 16 pixels; SC: of both outputs)
+  static constexpr int TILE_STORES = 2 * 16 * (1 + SC_);
+  static_assert(SC_ == 0 || SC_ == 1, "the shortcut is there or not");
   static_assert(TH * TWT == 4, "one M-tile per wave, four waves");
   static_assert(WPIECES % 4 == 0 && PPW * 4 >= PPIECES, "pieces split over four waves");
-  static_assert(8 * 4096 + 2048 < 65536, "ds_read immediates of a B fragment: tap and N-tile");
+  static_assert((WTAPS - 1) * 4096 + 2048 < 65536, "ds_read immediates of a B fragment: tap and N-tile");
+  // (<4, 1, 1>: 2 x (38 + 40) KB + the mailbox fit; <2, 2, 1> would need 2 x (41 + 40) KB = 162 KB and does not:
+  //  the layer-4 entry, Ho < 16, keeps its separate shortcut GEMM)
   static_assert(LDS_BYTES + 64 <= 160 * 1024, "two stages in LDS");
 };
 
@@ -95,11 +102,19 @@ __device__ __forceinline__ int conv_s2_w_lane(int piece, int lane, int COUT, int
   const int tap = e >> 6, n = e & 63;
   return ((tap * COUT + n) * CIN + 4 * q) * 4;
 }
+// ... of the shortcut's pieces (SC = 1: pieces 36 .. 39 = tap 9): byte offset in the slice Wsc[n0 + n][c0 + .] of the
+// image [COUT][CIN]
+__device__ __forceinline__ int conv_s2_wsc_lane(int piece, int lane, int CIN) {
+  const int sl = 64 * piece + lane;
+  const int e = sl >> 2, q = (sl & 3) ^ conv_s2_swz(e);
+  const int n = e & 63;
+  return (n * CIN + 4 * q) * 4;
+}
 
 // Fragment reads (byte address inside one buffer of the image): lane (li = lane & 31, kh = lane >> 5) of the wave
 // with M-tile mt reads, for tap = 3 dy + dx and half h, the channels 8 kh + 4 h .. + 3 of
 //   A: input pixel (2 yy + dy, 2 (32 xt + li) + dx) of the patch, yy = mt / TWT, xt = mt % TWT;
-//   B: output channel 32 j + li of the tap.
+//   B: output channel 32 j + li of the tap (tap 9, SC = 1: of the shortcut, whose A fragments are those of tap 4).
 template <class G>
 __device__ __forceinline__ int conv_s2_a_entry(int mt, int li, int tap) {
   const int dy = tap / 3, dx = tap % 3;

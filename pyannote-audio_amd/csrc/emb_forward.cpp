@@ -11,6 +11,12 @@ struct EmbPlan {
   size_t t2_off, gather_off;  // Bottleneck: sub-regions of act[3] (t1 at 0)
 };
 
+// PA_S2_FOLD=0 (environment) keeps the two launches at every block entry, for an A/B
+inline bool s2_fold_wanted() {
+  static const bool fold = getenv("PA_S2_FOLD") == nullptr || atoi(getenv("PA_S2_FOLD")) != 0;
+  return fold;
+}
+
 // Winograd F(4x4,3x3) (pa_conv3x3_wino4: units of 4 x 64 output pixels) or F(2x2,3x3) (pa_conv3x3_wino: 8 x 32,
 // 4 x 64 or 2 x 128 per workgroup) for an H x W map, both weight images being available.  Per USEFUL pixel F(4x4) is
 // 1.02x / 1.12x / 1.29x as fast on the 64 / 128 / 256-channel layers (B = 512 launches on MI355X,
@@ -256,13 +262,22 @@ static int emb_forward_impl(const pa_emb_weights* w, const float* wav, int64_t w
       const int Ho = p.Hs[l + 1], Wo = p.Ws[l + 1];
       if (w->blk_wsc[blk] != nullptr) {
         // out = relu(bn2(conv2(relu(bn1(conv1_s(x))))) + bn_sc(conv1x1_s(x)))   (resnet.py:140-145)
-        PA_RUN(pa_conv3x3(cur, B, H, W, cin, w->blk_w1[blk], w->blk_shift1[blk], nullptr, f1, cout, stride,
-                          1, stream));
-        PA_RUN(zero_tail(f1, l + 1, cout));
         const size_t q = (size_t)B * Ho * Wo * cin;
         float* R = f2 + pa::Bump::align(q);
+        // a stride-2 entry the fused kernel takes (layers 2 and 3 of ResNet34): the shortcut's pixel (2y, 2x) is the
+        // centre tap of the 3x3 convolution -- one launch writes f1 and R, the map is read once
+        const bool fold = stride == 2 && s2_fold_wanted() && pa_conv3x3_s2_sc_supported(H, cin, cout);
+        if (fold)
+          PA_RUN(pa_conv3x3_s2_sc(cur, B, H, W, cin, w->blk_w1[blk], w->blk_shift1[blk], w->blk_wsc[blk],
+                                  w->blk_shiftsc[blk], f1, R, cout, 1, stream));
+        else
+          PA_RUN(pa_conv3x3(cur, B, H, W, cin, w->blk_w1[blk], w->blk_shift1[blk], nullptr, f1, cout, stride,
+                            1, stream));
+        PA_RUN(zero_tail(f1, l + 1, cout));
         // (the 1x1 stride-2 shortcut reads its pixels in place: no gathered copy)
-        if (stride == 2)
+        if (fold) {
+          // (R is written already)
+        } else if (stride == 2)
           PA_RUN(pa_gemm_tn_s2(cur, B, H, W, cin, w->blk_wsc[blk], cin, w->blk_shiftsc[blk], R, cout, cout, stream));
         else
           PA_RUN(pa_gemm_tn(cur, cin, w->blk_wsc[blk], cin, w->blk_shiftsc[blk], R, cout, B * Ho * Wo, cout, cin, 0, 0,

@@ -400,6 +400,10 @@ int xcd_ranges_wanted(bool by_default);   // emb_winograd4.hip
 // stride 2 (emb_conv_s2.hip: k_conv3x3_s2)
 int launch_conv_s2(const float* X, int B, int H, int W, int CIN, const float* Wg, const float* shift, const float* R,
                    float* Y, int COUT, int relu, hipStream_t st);
+// ... with the block entry's 1x1 stride-2 shortcut folded in (k_conv3x3_s2<4, 1, false, 1>)
+int launch_conv_s2_sc(const float* X, int B, int H, int W, int CIN, const float* Wg, const float* shift,
+                      const float* Wsc, const float* shift_sc, float* Y, float* Ysc, int COUT, int relu,
+                      hipStream_t st);
 
 template <int TH, int TWT, int BN, bool HAS_R>
 static int launch_conv_r(const float* X, int B, int H, int W, int CIN, const float* Wg,
@@ -488,6 +492,35 @@ int pa_conv3x3(const float* X, int B, int H, int W, int cin, const float* Wg, co
     PA_REQUIRE(false, "pa_conv3x3: stride %d not supported", stride);
   }
   PA_CHECK_LAUNCH("pa_conv3x3");
+  return 0;
+}
+
+// can pa_conv3x3_s2_sc take an (H, cin) -> cout block entry?  (The caller keeps pa_conv3x3 + pa_gemm_tn_s2 otherwise.)
+int pa_conv3x3_s2_sc_supported(int H, int cin, int cout) {
+  return H >= 1 && cin >= pa::CB && cin % pa::CB == 0 && cout >= 64 && cout % 64 == 0 && (H - 1) / 2 + 1 >= 16;
+}
+
+// The entry of a stride-2 BasicBlock (resnet.py:109-118, 140-145) in one launch: the 1x1 stride-2 shortcut reads pixel
+// (2 y, 2 x) -- the centre tap of the 3x3 / stride 2 / pad 1 convolution, which the kernel has in LDS for every stage.
+//   Y = [relu]( conv3x3_s2(X) + shift ),   Ysc = conv1x1_s2(X) + shift_sc
+// Y has the bits of pa_conv3x3(X, ..., stride 2); Ysc is its own chain of MFMAs (emb_conv_s2.hip).
+int pa_conv3x3_s2_sc(const float* X, int B, int H, int W, int cin, const float* Wg, const float* shift,
+                     const float* Wsc, const float* shift_sc, float* Y, float* Ysc, int cout, int relu,
+                     void* stream) {
+  if (B <= 0) return 0;
+  PA_REQUIRE(cin >= pa::CB && cin % pa::CB == 0, "pa_conv3x3_s2_sc: cin %% 16 == 0 required");
+  PA_REQUIRE(cout >= 64 && cout % 64 == 0, "pa_conv3x3_s2_sc: cout %% 64 == 0 required");
+  const int Ho = (H - 1) / 2 + 1, Wo_ = (W - 1) / 2 + 1;
+  PA_REQUIRE(H >= 1 && W >= 1 && Ho >= 16, "pa_conv3x3_s2_sc: at least 16 output rows required (got %d)", Ho);
+  const size_t n_out = (size_t)B * Ho * Wo_ * cout;
+  PA_REQUIRE(Y != nullptr && Ysc != nullptr && (Y + n_out <= Ysc || Ysc + n_out <= Y),
+             "pa_conv3x3_s2_sc: Y and Ysc overlap");
+  // both convolutions' work, the input once, both outputs, both weight images
+  pa::ProfScope prof("k_conv3x3", stream, 2.0 * (9 + 1) * cin * cout * (double)B * Ho * Wo_,
+                     4.0 * ((double)B * H * W * cin + 2.0 * (double)B * Ho * Wo_ * cout + 10.0 * cin * cout));
+  if (pa::launch_conv_s2_sc(X, B, H, W, cin, Wg, shift, Wsc, shift_sc, Y, Ysc, cout, relu, (hipStream_t)stream) != 0)
+    return 2;
+  PA_CHECK_LAUNCH("pa_conv3x3_s2_sc");
   return 0;
 }
 

@@ -216,6 +216,9 @@ _OPTIONAL: list[tuple] = [
     ("pa_resnet_stem", [c_fp, C.c_int, C.c_int, C.c_int, c_fp, c_fp, c_fp, c_fp], C.c_int),
     ("pa_conv3x3", [c_fp, C.c_int, C.c_int, C.c_int, C.c_int, c_fp, c_fp, c_fp, c_fp, C.c_int, C.c_int,
                     C.c_int, c_fp], C.c_int),
+    ("pa_conv3x3_s2_sc_supported", [C.c_int, C.c_int, C.c_int], C.c_int),
+    ("pa_conv3x3_s2_sc", [c_fp, C.c_int, C.c_int, C.c_int, C.c_int, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, C.c_int,
+                          C.c_int, c_fp], C.c_int),
     ("pa_conv3x3_wino", [c_fp, C.c_int, C.c_int, C.c_int, C.c_int, c_fp, c_fp, c_fp, c_fp, C.c_int, C.c_int,
                          c_fp], C.c_int),
     ("pa_conv3x3_wino4", [c_fp, C.c_int, C.c_int, C.c_int, C.c_int, c_fp, c_fp, c_fp, c_fp, C.c_int, C.c_int,

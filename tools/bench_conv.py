@@ -1,5 +1,7 @@
 """Per-shape timing of pa_conv3x3 on the ResNet34 layer shapes (development aid; HIP events through
-the library profiler).  usage: [WINO=1|4] [ONLY_S1=1|ONLY_S2=1] [PA_LIB=variant.so] python tools/bench_conv.py [B] [reps]"""
+the library profiler).  usage: [WINO=1|4] [ONLY_S1=1|ONLY_S2=1] [PA_LIB=variant.so] python tools/bench_conv.py [B] [reps]
+SC=1: the block entries pa_conv3x3_s2_sc takes (80x998 32->64, 40x499 64->128) instead -- the fused call against
+pa_conv3x3(stride 2) + pa_gemm_tn_s2 on the same operands, alternating, two passes each."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -20,6 +22,45 @@ if os.environ.get("ONLY_S2") == "1":   # the three block-entry convolutions (csr
     shapes = [sh for sh in shapes if sh[4] == 2]
 if os.environ.get("ONLY_CIN"):         # one input width only (e.g. ONLY_CIN=32: layer 1)
     shapes = [sh for sh in shapes if sh[2] == int(os.environ["ONLY_CIN"])]
+
+
+def block_entries():
+    """unfused / fused / unfused / fused per shape; ms per block entry (both launches of the unfused form summed)"""
+    for (H, W, ci, co, s, _) in shapes:
+        if s != 2 or not lib.pa_conv3x3_s2_sc_supported(H, ci, co):
+            continue
+        Ho, Wo = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+        X = torch.randn(B, H, W, ci, device=dev)
+        Wg = torch.randn(9, co, ci, device=dev) * 0.05
+        Wsc = torch.randn(co, ci, device=dev) * 0.1
+        sh, shsc = torch.randn(co, device=dev), torch.randn(co, device=dev)
+        Y, Ysc = torch.empty(B, Ho, Wo, co, device=dev), torch.empty(B, Ho, Wo, co, device=dev)
+
+        def unfused():
+            ffi.check(lib.pa_conv3x3(ffi.ptr(X), B, H, W, ci, ffi.ptr(Wg), ffi.ptr(sh), None, ffi.ptr(Y), co, 2, 1,
+                                     ffi.stream()), "conv")
+            ffi.check(lib.pa_gemm_tn_s2(ffi.ptr(X), B, H, W, ci, ffi.ptr(Wsc), ci, ffi.ptr(shsc), ffi.ptr(Ysc), co, co,
+                                        ffi.stream()), "gemm_s2")
+
+        def fused():
+            ffi.check(lib.pa_conv3x3_s2_sc(ffi.ptr(X), B, H, W, ci, ffi.ptr(Wg), ffi.ptr(sh), ffi.ptr(Wsc),
+                                           ffi.ptr(shsc), ffi.ptr(Y), ffi.ptr(Ysc), co, 1, ffi.stream()), "conv_sc")
+        for name, run in (("unfused", unfused), ("fused", fused)) * 2:
+            for _ in range(int(os.environ.get('WARM', '10'))): run()
+            torch.cuda.synchronize()
+            ffi.prof_enable(True)
+            for _ in range(reps): run()
+            torch.cuda.synchronize()
+            rep = ffi.prof_report()
+            ffi.prof_enable(False)
+            parts = {k: rep[k]["ms"] / reps for k in ("k_conv3x3", "k_gemm_tn") if k in rep}
+            print(f"entry {H}x{W} {ci}->{co} {name:8s}: {sum(parts.values()):.3f} ms  "
+                  + "  ".join(f"{k} {v:.3f}" for k, v in parts.items()), flush=True)
+
+
+if os.environ.get("SC") == "1":
+    block_entries()
+    sys.exit(0)
 for (H, W, ci, co, s, res) in shapes:
     Ho, Wo = (H - 1) // s + 1, (W - 1) // s + 1
     X = torch.randn(B, H, W, ci, device=dev)
