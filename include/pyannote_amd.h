@@ -92,6 +92,22 @@ int pa_seg_forward(const pa_seg_weights* w, const float* wav, int64_t wav_len, i
                    int num_chunks, int num_samples, float* logp, uint8_t* multilabel, void* workspace,
                    size_t workspace_bytes, void* stream);
 
+/* The chunks of SEVERAL waveforms in one launch group (short files: the LSTM recurrence takes the same time for 21
+ * chunks as for 2 048).  wavs / wav_lens / chunks_per_file: HOST arrays of num_files entries; wavs[f] is a device
+ * pointer (read as zeros from wav_lens[f] on, never concatenated with its neighbours).  File f contributes
+ * chunks_per_file[f] chunks at chunk_stride, as pa_seg_forward would take them; logp / multilabel cover the
+ * concatenation of all files' chunks in file order, and every chunk's rows are bit for bit those of pa_seg_forward
+ * on its file alone: the waveform statistics and the sinc layer (whose span is re-centred by the file's first chunk)
+ * run per file, everything behind them once over all chunks.  A file of 0 chunks contributes nothing; 0 chunks in
+ * all: returns 0, nothing is launched.  Returns 3 (pa_last_error) for a negative chunk count, more than 65 535
+ * chunks, chunks too short for a frame, or a workspace below pa_seg_files_workspace_bytes (0 = invalid arguments):
+ * the common buffers for all chunks + the span scratch of the longest file, reused file after file. */
+size_t pa_seg_files_workspace_bytes(const pa_seg_weights* w, int num_files, const int* chunks_per_file,
+                                    int num_samples, int64_t chunk_stride);
+int pa_seg_forward_files(const pa_seg_weights* w, const float* const* wavs, const int64_t* wav_lens,
+                         const int* chunks_per_file, int num_files, int64_t chunk_stride, int num_samples,
+                         float* logp, uint8_t* multilabel, void* workspace, size_t workspace_bytes, void* stream);
+
 /* building blocks of pa_seg_forward (exported for unit parity tests) */
 int pa_row_stats(const float* x, long row_stride, long total_len, int rows, int len, float eps,
                  float* mean, float* rstd, void* stream);
@@ -576,6 +592,13 @@ int pa_linkage_chain_f64(const double* D, int n, int method, double* raw, void* 
  * seg: (C, F, S) uint8 {0,1};  start_frame: (C) int32 = closest_frame(chunk.start + frame.duration/2)
  * (core/inference.py:596), computed by the caller in float64 exactly as the reference does.
  * ---------------------------------------------------------------------------------------- */
+/* Dense chunk buffer from several device-resident waveforms (csrc/gather.hip): out (num_chunks, num_samples) fp32,
+ * out[c][i] = file_ptr[chunk_file[c]][chunk_start[c] + i], 0 where chunk_start[c] + i >= file_len[chunk_file[c]].
+ * All four tables are DEVICE arrays: per file its base pointer and length in samples, per chunk its file index and
+ * first sample (>= 0).  What a launch group of the embedding network reads when its chunks come from several
+ * files; 16-byte accesses where base + start and the output row are 16-byte aligned. */
+int pa_gather_chunks(const float* const* file_ptr, const int64_t* file_len, const int32_t* chunk_file,
+                     const int64_t* chunk_start, int num_chunks, int num_samples, float* out, void* stream);
 /* active[c][s] = sum_f seg;  clean[c][s] = sum_f seg * [sum_s' seg == 1]   (both (C,S) int32) */
 int pa_seg_chunk_stats(const uint8_t* seg, int C, int F, int S, int32_t* active, int32_t* clean,
                        void* stream);

@@ -50,8 +50,8 @@ void sincnet_plan_span(int sinc_stride, int B, int N, int64_t chunk_stride, Bump
   }
 }
 
-int sincnet_run(const SincNetView& w, const SincNetPlan& p, const float* wav, int64_t wav_len, int64_t chunk_stride,
-                int B, int N, float* ws, float* x0, void* stream) {
+int sincnet_sinc_stage(const SincNetView& w, const SincNetPlan& p, const float* wav, int64_t wav_len,
+                       int64_t chunk_stride, int B, int N, float* ws, void* stream) {
   PA_RUN(pa_row_stats(wav, chunk_stride, wav_len, B, N, 1e-5f, ws + p.wav_mean, ws + p.wav_rstd, stream));
   if (p.span_pos > 0) {
     // (chunk 0's statistics decide the constant the span is re-centred by: no further pass over the audio)
@@ -64,6 +64,10 @@ int sincnet_run(const SincNetView& w, const SincNetPlan& p, const float* wav, in
     PA_RUN(pa_sinc_fir_pool(wav, wav_len, chunk_stride, B, N, w.sinc_stride, ws + p.wav_mean, ws + p.wav_rstd,
                             w.wav_gamma, w.wav_beta, w.sinc_filt, ws + p.s1, stream));
   }
+  return 0;
+}
+
+int sincnet_after_sinc(const SincNetView& w, const SincNetPlan& p, int B, float* ws, float* x0, void* stream) {
   PA_RUN(pa_row_stats(ws + p.s1, p.P1, (long)B * 80 * p.P1, B * 80, p.P1, 1e-5f, ws + p.st1m, ws + p.st1r, stream));
   PA_RUN(pa_conv5_pool(ws + p.s1, B, 80, p.P1, ws + p.st1m, ws + p.st1r, w.norm0, w.norm0 + 80, w.conv1_w, w.conv1_b,
                        ws + p.s2, stream));
@@ -72,6 +76,12 @@ int sincnet_run(const SincNetView& w, const SincNetPlan& p, const float* wav, in
                        ws + p.s3, stream));
   PA_RUN(pa_row_stats(ws + p.s3, p.T, (long)B * 60 * p.T, B * 60, p.T, 1e-5f, ws + p.st3m, ws + p.st3r, stream));
   return pa_norm_transpose(ws + p.s3, B, p.T, ws + p.st3m, ws + p.st3r, w.norm2, w.norm2 + 60, x0, stream);
+}
+
+int sincnet_run(const SincNetView& w, const SincNetPlan& p, const float* wav, int64_t wav_len, int64_t chunk_stride,
+                int B, int N, float* ws, float* x0, void* stream) {
+  PA_RUN(sincnet_sinc_stage(w, p, wav, wav_len, chunk_stride, B, N, ws, stream));
+  return sincnet_after_sinc(w, p, B, ws, x0, stream);
 }
 
 bool lstm_head_check(const LstmHeadView& w, const char* who) {

@@ -59,6 +59,14 @@ PA_INTERNAL bool sincnet_plan(int sinc_stride, int B, int N, Bump* ws, SincNetPl
 // the shared sinc layer, where the chunks overlap by a multiple of the sinc stride (see forward_common.cpp): the raw
 // filter outputs of the whole span + the tap sums.  The segmentation model's only.
 PA_INTERNAL void sincnet_plan_span(int sinc_stride, int B, int N, int64_t chunk_stride, Bump* ws, SincNetPlan* p);
+// The two halves of sincnet_run, for a caller that joins the chunks of several waveforms (pa_seg_forward_files):
+// the waveform statistics + the sinc layer of the B chunks of ONE waveform -> p.wav_mean, p.wav_rstd, p.s1 (the
+// only stage whose values depend on which chunks share a launch: the span is re-centred by chunk 0) ...
+PA_INTERNAL int sincnet_sinc_stage(const SincNetView& w, const SincNetPlan& p, const float* wav, int64_t wav_len,
+                                   int64_t chunk_stride, int B, int N, float* ws, void* stream);
+// ... and everything behind p.s1, chunk by chunk, for all B chunks of the plan
+PA_INTERNAL int sincnet_after_sinc(const SincNetView& w, const SincNetPlan& p, int B, float* ws, float* x0,
+                                   void* stream);
 // x0: rows [(tile, t, b16)][64] of ceil(B / 16) tiles
 PA_INTERNAL int sincnet_run(const SincNetView& w, const SincNetPlan& p, const float* wav, int64_t wav_len,
                             int64_t chunk_stride, int B, int N, float* ws, float* x0, void* stream);

@@ -237,6 +237,10 @@ _OPTIONAL: list[tuple] = [
     ("pa_nonfinite_flag_f64", [c_fp, C.c_long, c_fp, c_fp], C.c_int),
     ("pa_linkage_chain_workspace_bytes", [C.c_int], C.c_size_t),
     ("pa_linkage_chain_f64", [c_fp, C.c_int, C.c_int, c_fp, c_fp, C.c_size_t, c_fp], C.c_int),
+    ("pa_seg_files_workspace_bytes", [C.POINTER(SegWeights), C.c_int, c_fp, C.c_int, C.c_int64], C.c_size_t),
+    ("pa_seg_forward_files", [C.POINTER(SegWeights), c_fp, c_fp, c_fp, C.c_int, C.c_int64, C.c_int, c_fp, c_fp, c_fp,
+                              C.c_size_t, c_fp], C.c_int),
+    ("pa_gather_chunks", [c_fp, c_fp, c_fp, c_fp, C.c_int, C.c_int, c_fp, c_fp], C.c_int),
     ("pa_seg_chunk_stats", [c_fp, C.c_int, C.c_int, C.c_int, c_fp, c_fp, c_fp], C.c_int),
     ("pa_embedding_masks", [c_fp, C.c_int, C.c_int, C.c_int, c_fp, C.c_int, C.c_int, c_fp, c_fp], C.c_int),
     ("pa_speaker_count", [c_fp, C.c_int, C.c_int, C.c_int, c_fp, C.c_int, c_fp, c_fp, c_fp], C.c_int),

@@ -73,6 +73,42 @@ def speaker_count(seg: torch.Tensor, chunks: SlidingWindow, frames: SlidingWindo
     return SlidingWindowFeature(count.cpu().numpy().reshape(T, 1), out_frames)
 
 
+def gather_chunks(wavs, chunk_file, chunk_start, num_samples: int) -> torch.Tensor:
+    """Chunks of several device-resident waveforms -> one dense (num_chunks, num_samples) float32 device tensor
+    (`pa_gather_chunks`): row c = wavs[chunk_file[c]][chunk_start[c] : chunk_start[c] + num_samples], zeros past that
+    waveform's end.  wavs: 1-D float32 tensors on one device; chunk_file / chunk_start: host integer sequences.
+    What a launch group of the embedding network reads when its chunks come from several files."""
+    chunk_file = np.ascontiguousarray(chunk_file, dtype=np.int32).reshape(-1)
+    chunk_start = np.ascontiguousarray(chunk_start, dtype=np.int64).reshape(-1)
+    if chunk_file.size != chunk_start.size:
+        raise ValueError("gather_chunks: one file index and one start per chunk")
+    if not len(wavs) or num_samples < 0:
+        raise ValueError("gather_chunks: no waveform, or a negative chunk length")
+    dev = wavs[0].device
+    for wav in wavs:
+        if wav.dim() != 1 or wav.dtype != torch.float32 or wav.device != dev:
+            raise ValueError("gather_chunks: waveforms must be 1-D float32 tensors on one device")
+    if chunk_file.size and (chunk_file.min() < 0 or chunk_file.max() >= len(wavs) or chunk_start.min() < 0):
+        raise ValueError("gather_chunks: a chunk names a waveform that is not there, or starts before its first sample")
+    with torch.cuda.device(dev):
+        out = torch.empty((chunk_file.size, num_samples), dtype=torch.float32, device=dev)
+        if not out.numel():
+            return out
+        wavs = [w.contiguous() for w in wavs]
+        # ONE upload: [base pointers | lengths | starts | file indices] (8-byte entries first)
+        table = np.concatenate([np.array([w.data_ptr() for w in wavs], dtype=np.int64),
+                                np.array([w.numel() for w in wavs], dtype=np.int64), chunk_start]).view(np.uint8)
+        table = torch.from_numpy(np.concatenate([table, chunk_file.view(np.uint8)])).to(dev)
+        base = table.data_ptr()
+        n, c = 8 * len(wavs), 8 * chunk_file.size
+        ffi.check(ffi.load().pa_gather_chunks(ffi.c_fp(base), ffi.c_fp(base + n), ffi.c_fp(base + 2 * n + c),
+                                              ffi.c_fp(base + 2 * n), chunk_file.size, num_samples, ffi.ptr(out),
+                                              ffi.stream()), "pa_gather_chunks")
+        # (`table` and the waveforms are used by a launch that is queued on the current stream: torch's allocator
+        #  hands their memory out again to work on that same stream only, i.e. behind the launch)
+    return out
+
+
 def aggregate_device(scores, chunks: SlidingWindow, frames: SlidingWindow, device: torch.device,
                      warm_up: Tuple[float, float] = (0.0, 0.0), epsilon: float = 1e-12, hamming: bool = False,
                      missing: float = np.nan, skip_average: bool = False) -> Tuple[torch.Tensor, SlidingWindow]:

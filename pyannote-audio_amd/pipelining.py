@@ -204,6 +204,55 @@ def run_ahead(make_iter: Callable[[], Iterator[Any]], depth: int = 1, context: C
             worker.join(timeout=0.05)
 
 
+class PackGrouper:
+    """Joins items that arrive one by one into groups by a size budget, in order: an item joins the open group while
+    the group's total stays within `budget`, otherwise it closes that group and opens the next; an item larger than
+    the budget is therefore a group of its own.  (apply_batch(pack=...): the chunks of several short files share one
+    launch group, and a file's chunk count is known only once the file is loaded -- hence the incremental form.)
+
+        add(size) -> the positions of the group that this item closed, or None
+        flush()   -> the positions of the open group (empty when there is none)"""
+
+    def __init__(self, budget: int):
+        if int(budget) < 1:
+            raise ValueError(f"a group budget must be at least 1 (got {budget})")
+        self.budget = int(budget)
+        self._open: list = []
+        self._total = 0
+        self._next = 0
+
+    def add(self, size: int):
+        size = int(size)
+        if size < 0:
+            raise ValueError("an item's size cannot be negative")
+        closed = None
+        if self._open and self._total + size > self.budget:
+            closed, self._open, self._total = self._open, [], 0
+        self._open.append(self._next)
+        self._total += size
+        self._next += 1
+        return closed
+
+    def flush(self) -> list:
+        closed, self._open, self._total = self._open, [], 0
+        return closed
+
+
+def pack_groups(sizes: Iterable[int], budget: int) -> list:
+    """`PackGrouper` over sizes that are all known: [[positions of group 0], [of group 1], ...], every position once
+    and in order."""
+    grouper = PackGrouper(budget)
+    groups = []
+    for size in sizes:
+        closed = grouper.add(size)
+        if closed is not None:
+            groups.append(closed)
+    last = grouper.flush()
+    if last:
+        groups.append(last)
+    return groups
+
+
 class ReadAhead:
     """`load(items[i + 1])` runs in ONE worker thread while the caller works on item i: `take(i)` hands out
     `load(items[i])` (started by `take(i - 1)`, or now) and starts the next one.  At most one result is held ahead of

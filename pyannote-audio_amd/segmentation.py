@@ -2,6 +2,8 @@
 `pa_seg_forward`.  Mirrors models/segmentation/PyanNet.py:211-240 + core/inference.py:182-215."""
 from __future__ import annotations
 
+import ctypes as C
+
 import torch
 
 from . import ffi
@@ -74,6 +76,63 @@ class SegmentationEngine:
             c0 += nb
         return logp, ml
 
+    #: whether `forward_files` exists for this engine (PyanNet: yes; SSeRiouSSEngine keeps the per-file path)
+    PACKS_FILES = True
+
+    @ffi.on_device(lambda self, *a, **k: self.pack.device)
+    def forward_files(self, wavs, chunk_stride: int, chunks_per_file, num_samples: int,
+                      want_logp: bool = True, want_multilabel: bool = True):
+        """The chunks of several waveforms in shared launch groups (`pa_seg_forward_files`).  wavs: 1-D fp32 device
+        tensors; file f contributes chunks_per_file[f] chunks, chunk c = wavs[f][c*stride : c*stride + num_samples]
+        (zero padded past the end).  Returns what `forward_strided` returns, over the concatenation of all files'
+        chunks in file order; every file's rows equal, bit for bit, those of `forward_strided` on that file alone.
+
+        A launch group holds at most `max_chunks` chunks: files are joined in order while they fit, and a file with
+        more chunks than that is cut at the chunk boundaries `forward_strided` cuts it at."""
+        lib = ffi.load()
+        w = self.pack.struct
+        if not self.PACKS_FILES or not self.pack.powerset:
+            raise NotImplementedError("forward_files packs the powerset PyanNet model only")
+        counts = [int(c) for c in chunks_per_file]
+        if len(counts) != len(wavs):
+            raise ValueError("forward_files: one chunk count per waveform")
+        if any(c < 0 for c in counts):
+            raise ValueError("forward_files: a negative chunk count")
+        F = self.frames_of(num_samples)
+        if F <= 0:
+            raise ValueError(f"chunks of {num_samples} samples are too short for this model")
+        dev = self.pack.device
+        total = sum(counts)
+        logp = torch.empty((total, F, w.num_classes), dtype=torch.float32, device=dev) if want_logp else None
+        ml = torch.empty((total, F, w.num_speakers), dtype=torch.uint8, device=dev) if want_multilabel else None
+        # pieces of at most max_chunks chunks: (waveform from the piece's first chunk on, chunks)
+        pieces = []
+        for wav, count in zip(wavs, counts):
+            assert wav.dim() == 1 and wav.dtype == torch.float32 and wav.is_cuda
+            for c0 in range(0, count, self.max_chunks):
+                off = c0 * chunk_stride
+                pieces.append((wav[off:] if off < wav.numel() else wav[:0], min(self.max_chunks, count - c0)))
+        first, done = 0, 0
+        while first < len(pieces):
+            last, nb = first, 0
+            while last < len(pieces) and (last == first or nb + pieces[last][1] <= self.max_chunks):
+                nb += pieces[last][1]
+                last += 1
+            group = pieces[first:last]
+            n = len(group)
+            ptrs = (C.c_void_p * n)(*[p.data_ptr() if p.numel() else None for p, _ in group])
+            lens = (C.c_int64 * n)(*[p.numel() for p, _ in group])
+            cnts = (C.c_int * n)(*[c for _, c in group])
+            need = lib.pa_seg_files_workspace_bytes(w, n, cnts, num_samples, chunk_stride)
+            ws = self._workspace(need)
+            rc = lib.pa_seg_forward_files(
+                w, ptrs, lens, cnts, n, chunk_stride, num_samples,
+                ffi.ptr(logp[done:done + nb]) if logp is not None else None,
+                ffi.ptr(ml[done:done + nb]) if ml is not None else None, ffi.ptr(ws), ws.numel(), ffi.stream())
+            ffi.check(rc, "segmentation forward (packed files)")
+            first, done = last, done + nb
+        return logp, ml
+
     # -- model-specific entry points (PyanNet here; SSeRiouSSEngine overrides them)
     def frames_of(self, num_samples: int) -> int:
         return num_frames(num_samples, int(self.pack.struct.sinc_stride) or 10)
@@ -98,6 +157,8 @@ class SSeRiouSSEngine(SegmentationEngine):
     """SSeRiouSS (models/segmentation/SSeRiouSS.py:289-328) over `pa_sser_forward`: wav2vec 2.0 / WavLM encoder
     -> layer mix -> bi-LSTM stack -> head, on strided chunks of a device-resident waveform.  The feature
     extractor's first stages are large (65 MB per 10 s chunk at 512 channels): 16 chunks per launch group."""
+
+    PACKS_FILES = False
 
     def __init__(self, pack, max_chunks: int = 16):
         super().__init__(pack, max_chunks=max_chunks)

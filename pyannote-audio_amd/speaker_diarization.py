@@ -41,7 +41,7 @@ from .diarization import optimal_mapping, set_num_speakers, to_annotation
 from .inference import Inference
 from .model import Model
 from .pipeline import ParamDict, Pipeline, Uniform
-from .pipelining import ReadAhead, pipelined, pipelined_owned, run_ahead
+from .pipelining import PackGrouper, ReadAhead, pipelined, pipelined_owned, run_ahead
 from .speaker_verification import PipelineModel, PretrainedSpeakerEmbedding, get_model
 
 
@@ -149,6 +149,7 @@ class SpeakerDiarization(Pipeline):
         self._expects_num_speakers = self.clustering.expects_num_clusters
         self.timings: dict = {}
         self.batch_timeline: list = []       # apply_batch: host-clock stage boundaries per file
+        self.last_pack_groups: list = []     # apply_batch(pack=...): the URIs of every group of the last call
 
     def _clustering_kwargs(self, name: str, metric: str) -> dict:
         kwargs = {"metric": metric}
@@ -394,6 +395,114 @@ class SpeakerDiarization(Pipeline):
         hook("embeddings", front.embeddings)
         return front
 
+    # ------------------------------------------------------------------- front ends of a packed group
+    def _pack_budget(self, pack, hook, joint_clustering: bool) -> Optional[int]:
+        """chunks per group of `apply_batch(pack=...)`, or None where the call takes the per-file path: `pack` off,
+        and every case whose front end is more than the two networks on one file's chunks ("Packed front
+        ends")"""
+        if pack is False or pack is None:
+            return None
+        engine = getattr(self._segmentation.model, "engine", None)
+        budget = getattr(engine, "max_chunks", 0) if pack is True else int(pack)
+        if budget < 1:
+            raise ValueError(f"pack must be True, False or a positive number of chunks (got {pack!r})")
+        if hook is not None or joint_clustering or self.training or parallel.current_shard().world_size > 1:
+            return None
+        if not getattr(engine, "PACKS_FILES", False) or not self._segmentation.model.specifications.powerset:
+            return None
+        if self._embedding is None:
+            return None
+        # (the gathered buffer holds zeros past a file's end: only for front ends that read them as such anyway)
+        if not getattr(self._embedding.model_.engine, "READS_PAST_END_AS_ZERO", False):
+            return None
+        return budget
+
+    def _num_chunks(self, num_samples: int) -> int:
+        """chunks of the sliding window over a file of `num_samples` samples, the zero-padded last one included"""
+        window = self._segmentation.model.audio.get_num_samples(self._segmentation.duration)
+        step = round(self._segmentation.step * self._audio.sample_rate)
+        n_full, has_last = Inference.num_chunks(num_samples, window, step)
+        return n_full + has_last
+
+    def _front_ends_packed(self, files: List[dict], waveforms: List[torch.Tensor],
+                           after_segmentation: Optional[Callable] = None) -> List[_FrontEnd]:
+        """`_front_end` of several files whose chunks share the launch groups of both networks: ONE segmentation
+        forward (`forward_files`), one download of the hard segmentations, one `chunk_stats` / `embedding_masks`, one
+        gather of the chunks somebody speaks in (+ one silent representative, see `_embed_speech_chunks`), one
+        embedding forward, one download -- then one `_FrontEnd` per file from slices along the chunk axis.  Only the
+        speaker count is per file (it depends on the file's own frame count).  Every file's arrays are those of
+        `_front_end` on that file, bit for bit (tests/test_packed_front_end_gpu.py)."""
+        marks = [("start", time.perf_counter()), ("load", time.perf_counter())]
+        sr = self._audio.sample_rate
+        seg_model = self._segmentation.model
+        device = seg_model.device
+        window = seg_model.audio.get_num_samples(self._segmentation.duration)
+        step = round(self._segmentation.step * sr)
+        counts = [self._num_chunks(w.shape[1]) for w in waveforms]
+        bounds = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+        total = int(bounds[-1])
+        chunks = self._chunk_grid()
+        wavs = [w.to(device, torch.float32).contiguous().view(-1) for w in waveforms]
+
+        _, dev_seg = seg_model.engine.forward_files(wavs, step, counts, window, want_logp=False,
+                                                    want_multilabel=True)
+        enqueued = {"segmentation": time.perf_counter()}
+        seg_host = dev_seg.cpu().numpy().astype(np.float32)
+        marks.append(("segmentation", time.perf_counter()))
+        if after_segmentation is not None:
+            after_segmentation()
+
+        counted = [frame_ops.speaker_count(dev_seg[a:b], chunks, self._frames)
+                   for a, b in zip(bounds[:-1], bounds[1:])]
+        marks.append(("speaker_counting", time.perf_counter()))
+        fronts = [_FrontEnd(file=f, chunks=chunks, segmentations=SlidingWindowFeature(seg_host[a:b], chunks),
+                            dev_seg=dev_seg[a:b], count=count, marks=list(marks), enqueued=dict(enqueued),
+                            silent=bool(np.nanmax(count.data) == 0.0))
+                  for f, count, a, b in zip(files, counted, bounds[:-1], bounds[1:])]
+        if all(fr.silent for fr in fronts):
+            return fronts                          # nobody speaks anywhere: no embeddings
+
+        # the embedding stage of `_embed` / `_embed_speech_chunks`, over the group's chunk axis
+        C, F, S = dev_seg.shape
+        emb_sr = self._embedding.sample_rate
+        emb_window = self._audio.get_num_samples(chunks.duration, emb_sr)
+        emb_step = round(chunks.step * emb_sr)
+        exclude_overlap = self.embedding_exclude_overlap
+        active, clean = frame_ops.chunk_stats(dev_seg)
+        masks = frame_ops.embedding_masks(dev_seg, clean, exclude_overlap,
+                                          self._min_num_frames(F, chunks.duration, exclude_overlap))
+        engine = self._embedding.model_.engine
+        emb_dev = engine.pack.device
+        speech = masks.flatten(1).any(dim=1).cpu().numpy()              # (C,)  (host wait, as `_embed_speech_chunks`)
+        kept, silent = np.flatnonzero(speech), np.flatnonzero(~speech)
+        if not self.skip_inactive_chunks:
+            kept, silent = np.arange(total), silent[:0]
+        sel = np.concatenate([kept, silent[:1]])
+        chunk_file = np.searchsorted(bounds, sel, side="right") - 1
+        chunk_start = (sel - bounds[chunk_file]) * emb_step
+        emb_wavs = [w.to(emb_dev, torch.float32).contiguous().view(-1) for w in waveforms]
+        dense = frame_ops.gather_chunks(emb_wavs, chunk_file, chunk_start, emb_window)
+        sel_dev = torch.from_numpy(sel).to(emb_dev)
+        out = engine.forward_strided(dense.view(-1), emb_window, int(sel.size), emb_window,
+                                     masks.to(emb_dev)[sel_dev].contiguous())
+        dev_emb = torch.empty((total,) + tuple(out.shape[1:]), dtype=out.dtype, device=out.device)
+        if silent.size:
+            dev_emb[torch.from_numpy(silent).to(emb_dev)] = out[-1]
+        dev_emb[torch.from_numpy(kept).to(emb_dev)] = out[:kept.size]
+        self.last_embedded_chunks = (total, int(sel.size))
+        queued = time.perf_counter()
+        emb_host = dev_emb.cpu().numpy()
+        active, clean = active.cpu().numpy(), clean.cpu().numpy()
+        done = time.perf_counter()
+        for front, a, b in zip(fronts, bounds[:-1], bounds[1:]):
+            if front.silent:
+                continue                           # (`_front_end` returns before the embedding stage)
+            front.enqueued["embeddings"] = queued
+            front.embeddings, front.dev_emb = emb_host[a:b].copy(), dev_emb[a:b]
+            front.active, front.clean = active[a:b].copy(), clean[a:b].copy()
+            front.marks.append(("embeddings", done))
+        return fronts
+
     # --------------------------------------------------------------------------- training cache
     def prepare_one(self, file: AudioFile, preload: bool = False) -> Mapping:
         prepared = super().prepare_one(file, preload=preload)
@@ -546,7 +655,7 @@ class SpeakerDiarization(Pipeline):
 
     def apply_batch(self, files: Iterable[AudioFile], num_speakers: Optional[int] = None,
                     min_speakers: Optional[int] = None, max_speakers: Optional[int] = None,
-                    hook: Optional[Callable] = None, joint_clustering: bool = False,
+                    hook: Optional[Callable] = None, joint_clustering: bool = False, pack=False,
                     **kwargs) -> Iterator[Tuple[AudioFile, Any]]:
         """Several files (core/pipeline.py:489-508 calls this for list inputs) -> (file, output) pairs
         in input order.
@@ -555,8 +664,16 @@ class SpeakerDiarization(Pipeline):
         end of file i run on a second stream while the front end of file i+1 runs on the first.
         `joint_clustering=True`: ONE clustering over the embeddings of all files (of all ranks when
         torch.distributed is initialised and `parallel.set_shard` was not used to split single files):
-        speakers get the same label in every file (BASELINE.json configs[4])."""
+        speakers get the same label in every file (BASELINE.json configs[4]).
+        `pack`: short files share launch groups -- the front ends of consecutive files run as ONE front end
+        (`_front_ends_packed`) while their chunks together stay within a budget (True: the segmentation engine's
+        `max_chunks`; an int: that many chunks); clustering and the back end stay per file.  Results are those of the
+        per-file path, bit for bit.  `last_pack_groups` lists the URIs of every group; it stays empty where the call
+        takes the per-file path after all (a hook, joint clustering, training, a chunk shard, a model that is not
+        the powerset PyanNet, no embedding model)."""
         files = [Audio.validate_file(f) for f in files]
+        self.last_pack_groups = []
+        pack_budget = self._pack_budget(pack, hook, joint_clustering)
         batch_level = {"num_speakers": num_speakers, "min_speakers": min_speakers,
                        "max_speakers": max_speakers, **kwargs}
         batch_level = {k: v for k, v in batch_level.items() if v is not None}
@@ -635,6 +752,47 @@ class SpeakerDiarization(Pipeline):
         def stream():
             for (_, file, _), out in pipelined(items, front_of, tail_of, self.TAIL_GATE_TIMEOUT):
                 yield file, out
+
+        # pack: the items of the pipeline are GROUPS of files.  A file's chunk count is known once it is loaded, so
+        # the groups form while the files arrive (the file that closes a group waits, loaded, for the next one).
+        def groups():
+            grouper, loaded = PackGrouper(pack_budget), []
+            for i, file, bounds in items:
+                waveform = self._load(file, ahead.take(i))
+                closed = grouper.add(self._num_chunks(waveform.shape[1]))
+                if closed is not None:
+                    yield loaded
+                    loaded = []
+                loaded.append((file, bounds, waveform))
+            if grouper.flush():
+                yield loaded
+
+        def front_of_group(group, release: Callable):
+            self.last_pack_groups.append([file["uri"] for file, _, _ in group])
+            line = {"front_start": time.perf_counter() - t_batch}
+            fronts = self._front_ends_packed([file for file, _, _ in group], [w for _, _, w in group],
+                                             after_segmentation=release)
+            states = []
+            for front, (file, bounds, _) in zip(fronts, group):
+                own = dict(line)
+                own.update({name: stamp - t_batch for name, stamp in front.marks[1:]})
+                own.update({name + "_queued": stamp - t_batch for name, stamp in front.enqueued.items()})
+                own["submit"] = time.perf_counter() - t_batch
+                self.batch_timeline.append(own)
+                states.append((front, self.setup_hook(file, hook=None), own, bounds))
+            return states
+
+        def tail_of_group(states, alone: bool):
+            # (`alone` is True for the last group: no front end runs beside any of its files' tails)
+            return [tail_of(state, alone) for state in states]
+
+        def packed_stream():
+            for group, outs in pipelined(groups(), front_of_group, tail_of_group, self.TAIL_GATE_TIMEOUT):
+                for (file, _, _), out in zip(group, outs):
+                    yield file, out
+
+        if pack_budget is not None:
+            stream = packed_stream
 
         try:
             if hook is None and len(items) > 2 and os.environ.get("PA_BATCH_RUN_AHEAD", "1") != "0":
