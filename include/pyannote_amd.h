@@ -717,6 +717,41 @@ size_t pa_vbx_workspace_bytes(int n, int s, int d);
 int pa_vbx_iteration(const double* fea, const double* Phi, int n, int s, int d, double Fa, double Fb,
                      int first, double* gamma, double* elbo_out, void* workspace, size_t workspace_bytes,
                      void* stream);
+/* bytes of `workspace` below, from the number of jobs, n, the largest S of the call and d (0: an argument is
+ * not positive) */
+size_t pa_vbx_batch_workspace_bytes(int jobs, int n, int smax, int d);
+/* Whole VB inferences for `jobs` jobs over the same features fea (n, d), d = 128: no read-back, no host
+ * synchronisation.  Job j starts from the (n, S_j) responsibilities at gamma0 + job_init[2 j] (an offset in
+ * doubles; gamma0 holds gamma0_len doubles and is only read, several jobs may name the same ones), with
+ * S_j = job_init[2 j + 1] <= smax, Fa = job_f[2 j] and Fb = job_f[2 j + 1]; both tables are device arrays.  rho and
+ * G are computed once and shared.  Every round is the three steps of pa_vbx_iteration launched once for all jobs;
+ * after the ELBO of round `it` a job's ELBO workgroup applies `it > 0 && elbo[it] - elbo[it - 1] < epsilon` in
+ * double and, if it holds, retires the job, whose workgroups return at entry from then on.  max_iterations rounds
+ * are enqueued.  gamma (jobs, n * smax): the final (n, S_j) responsibilities of job j, contiguous at the start of
+ * its slab; elbo (jobs, max_iterations): its history, valid up to iterations[j] (jobs; 0 for a job whose table
+ * entry is out of range, which is left alone).  Per job, bit for bit what max_iterations calls of
+ * pa_vbx_iteration followed by that test on the host give. */
+int pa_vbx_run_batch(const double* fea, const double* Phi, int n, int d, int jobs, const double* gamma0,
+                     long gamma0_len, const int64_t* job_init, const double* job_f, int smax,
+                     int max_iterations, double epsilon, double* gamma, double* elbo, int32_t* iterations,
+                     void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- constrained assignment of local speakers to clusters (pipelines/clustering.py:127-140) ---- */
+
+/* limits of pa_constrained_assign: local speakers per chunk (4) and clusters (64) */
+int pa_constrained_assign_max_speakers(void);
+int pa_constrained_assign_max_clusters(void);
+/* soft (chunks, speakers, clusters) fp64 and silent (chunks, speakers) uint8 on the device.  Per chunk: the
+ * injective map of the non-silent rows into the clusters with the largest sum (a partial map of `clusters` rows
+ * when there are fewer clusters than non-silent rows), found by exhaustive search over each row's best columns.
+ * hard (chunks, speakers) int8: the cluster of every row, -2 for a silent or unassigned row.  flagged (chunks)
+ * uint8: 1 where the optimum is not safely unique -- a non-silent row holds a non-finite value; another map comes
+ * within 1e-9 of the best total; or, with more clusters than non-silent rows A, the A-th and (A+1)-th best value of
+ * a row lie within 1e-9 (the search keeps A columns per row, and a map through a dropped column loses at least that
+ * gap, so a larger gap proves that no unseen map is a runner-up); the rows of such a chunk are all -2 and the caller solves it with the solver
+ * whose tie-breaking it wants to reproduce. */
+int pa_constrained_assign(const double* soft, const unsigned char* silent, int chunks, int speakers, int clusters,
+                          signed char* hard, unsigned char* flagged, void* stream);
 
 /* ---- frame-level diarization error rates (utils/metric.py:41-93,
  *      torchmetrics/functional/audio/diarization_error_rate.py:33-162) ---- */

@@ -5,7 +5,9 @@ max_clusters) -> (hard (C,S), soft (C,S,K), centroids (K,D))`, pipelines/cluster
 What runs where
   GPU (libpyannote_amd.so)   float64 pdist + the whole centroid-linkage merge (`distance.linkage_centroid`,
                              bit-identical to SciPy incl. ties), cosine cdist of every embedding to the
-                             centroids, the PLDA projection and the VB iterations of VBx
+                             centroids, the PLDA projection and the VB iterations of VBx (one file: `_vbx`; the
+                             candidates of a tuning sweep: `vbx_batch`), the constrained assignment of all chunks
+                             for such a sweep (`constrained_argmax_device`)
   host, SciPy / sklearn      `fcluster` on the (GPU-built) dendrogram, Hungarian assignment, KMeans --
                              the very library calls the reference makes, O(N) or tiny
   host, this file            everything between those calls, organised around array operations instead
@@ -31,7 +33,7 @@ from __future__ import annotations
 import time
 import warnings
 from enum import Enum
-from typing import Optional, Tuple
+from typing import Callable, Optional, Tuple
 
 import numpy as np
 import torch
@@ -213,6 +215,47 @@ class BaseClustering(Pipeline):
         for c, cost in enumerate(scores):
             speakers, clusters = linear_sum_assignment(cost, maximize=True)
             hard[c, speakers] = clusters
+        return hard
+
+    #: chunks of the last `constrained_argmax_device` call that went back to the host solver
+    last_flagged_chunks: int = 0
+
+    def constrained_argmax_device(self, soft_clusters: np.ndarray, silent: np.ndarray) -> np.ndarray:
+        """`np.where(silent, -2, self.constrained_argmax(soft_clusters))` with all chunks assigned in one launch
+        (`pa_constrained_assign`, csrc/assign.hip).  `silent` (C, S): local speakers that never speak; the caller has
+        pushed their rows below every other value (`soft[silent] = soft.min() - 1`), so they only ever take what the
+        others leave and the kernel searches over the other rows alone.  A chunk whose optimum is not safely unique
+        (an active row of NaN, which `nan_to_num` turns into a constant; a runner-up within 1e-9; a row whose last
+        kept and first dropped column lie within 1e-9, where the kernel's pruned search could miss such a runner-up;
+        silent rows that do not lie below every active value) is solved by
+        `constrained_argmax` on the rows the host path would have seen, as is every chunk beyond the kernel's
+        limits (4 local speakers, 64 clusters) or without a GPU."""
+        silent = np.asarray(silent, dtype=bool)
+        C, S, K = soft_clusters.shape
+        on_gpu = getattr(self.device, "type", None) == "cuda"
+        if not on_gpu or C == 0 or K == 0 or S > 4 or K > 64:
+            self.last_flagged_chunks = C
+            return np.where(silent, -2, self.constrained_argmax(soft_clusters)).astype(np.int8)
+        from . import ffi
+        device = self.device
+        with torch.cuda.device(device):
+            soft = torch.from_numpy(np.ascontiguousarray(soft_clusters, dtype=np.float64)).to(device)
+            mask = torch.from_numpy(np.ascontiguousarray(silent, dtype=np.uint8)).to(device)
+            out = torch.empty(C * (S + 1), dtype=torch.int8, device=device)     # hard (C, S), then flagged (C)
+            ffi.check(ffi.load().pa_constrained_assign(ffi.ptr(soft), ffi.ptr(mask), C, S, K, ffi.ptr(out[:C * S]),
+                                                       ffi.ptr(out[C * S:]), ffi.stream()), "pa_constrained_assign")
+            host = out.cpu().numpy()
+        hard = host[:C * S].reshape(C, S).copy()
+        # the kernel leaves the silent rows out, which is the host's answer only while they lie below every value of
+        # an active row.  They do not when a NaN embedding makes `soft.min()` NaN: the silent rows then become the
+        # smallest finite value, like the NaN row itself.  A chunk where they come within the margin goes to the host.
+        scores = np.nan_to_num(soft_clusters, nan=np.nanmin(soft_clusters))
+        mask = silent[:, :, None]
+        unsafe = np.where(mask, scores, -np.inf).max(axis=(1, 2)) > np.where(mask, np.inf, scores).min(axis=(1, 2)) - 1e-9
+        flagged = np.nonzero((host[C * S:] != 0) | unsafe)[0]
+        self.last_flagged_chunks = len(flagged)
+        if len(flagged):
+            hard[flagged] = np.where(silent[flagged], -2, self.constrained_argmax(scores[flagged]))
         return hard
 
     def _similarities(self, embeddings: np.ndarray, centroids: np.ndarray, device_embeddings=None) -> np.ndarray:
@@ -437,26 +480,35 @@ class VBxClustering(BaseClustering):
             self.plda.to(device)
         return self
 
-    def _ahc_labels(self, train: np.ndarray) -> np.ndarray:
+    def _unit_linkage(self, train: np.ndarray):
+        """the centroid linkage of the unit vectors (it depends on no hyper-parameter) and those vectors"""
         unit = train / np.linalg.norm(train, axis=1, keepdims=True)
         if not np.isfinite(unit).all():
             raise ValueError("The condensed distance matrix must contain only finite values.")
-        Z = distance.linkage_centroid(unit, self.device)
+        return distance.linkage_centroid(unit, self.device), unit
+
+    def _ahc_labels(self, train: np.ndarray) -> np.ndarray:
+        Z, unit = self._unit_linkage(train)
         labels = fcluster(Z, self.threshold, criterion="distance") - 1
         return np.unique(labels, return_inverse=True)[1], unit
+
+    def initial_responsibilities(self, labels: np.ndarray) -> np.ndarray:
+        """(N, S) float64: the smoothed one-hot AHC labels VB starts from (utils/vbx.py:143-147)"""
+        from scipy.special import softmax
+        n, s = len(labels), int(labels.max()) + 1
+        onehot = np.zeros((n, s))
+        onehot[np.arange(n), labels] = 1.0
+        return onehot if self.init_smoothing < 0 else softmax(onehot * self.init_smoothing, axis=1)
 
     def _vbx(self, fea, labels: np.ndarray):
         """responsibilities (N, S) and speaker priors (S,) after VB inference on the device"""
         import torch
-        from scipy.special import softmax
         from . import ffi
         lib = ffi.load()
         device = self.device
         n, d = fea.shape
-        s = int(labels.max()) + 1
-        onehot = np.zeros((n, s))
-        onehot[np.arange(n), labels] = 1.0
-        q0 = onehot if self.init_smoothing < 0 else softmax(onehot * self.init_smoothing, axis=1)
+        q0 = self.initial_responsibilities(labels)
+        s = q0.shape[1]
         gamma = torch.from_numpy(q0).to(device)
         phi = torch.from_numpy(np.ascontiguousarray(self.plda.phi, dtype=np.float64)).to(device)
         elbo = torch.zeros(self.max_iterations, dtype=torch.float64, device=device)
@@ -474,7 +526,109 @@ class VBxClustering(BaseClustering):
         q = gamma.cpu().numpy()
         pi = q.sum(axis=0)
         self.timings["vbx_iterations"] = len(history)
+        self.last_elbo_history = history
         return q, pi / pi.sum()
+
+    def vbx_batch(self, fea, inits: list, jobs: list, workspace_bytes: Optional[int] = None):
+        """Whole VB inferences for many (initialisation, Fa, Fb) jobs over the same features, without a read-back per
+        iteration (`pa_vbx_run_batch`, csrc/vbx.hip).  `fea` (N, 128) device tensor; `inits`: (N, S_i) float64 arrays
+        (`initial_responsibilities`), uploaded once; `jobs`: (index into `inits`, Fa, Fb).  Returns per job
+        (q (N, S), ELBO history): bit for bit what `_vbx` gives with those hyper-parameters.  `workspace_bytes`
+        bounds what one call allocates beyond the shared inputs -- the kernels' workspace plus the result buffer
+        (J N Smax doubles, the larger of the two); a batch over the budget is run in several calls
+        (`last_vbx_calls`), one download each."""
+        from . import ffi
+        lib = ffi.load()
+        device = self.device
+        n, d = fea.shape
+        if not jobs:
+            self.last_vbx_calls = 0
+            return []
+        sizes = [int(q0.shape[1]) for q0 in inits]
+        offsets = np.concatenate([[0], np.cumsum([n * s for s in sizes])]).astype(np.int64)
+        job_s = [sizes[i] for i, _, _ in jobs]
+        iters = self.max_iterations
+
+        def call_bytes(count, smax):      # the kernels' workspace and the buffer the results come back in
+            return int(lib.pa_vbx_batch_workspace_bytes(count, n, smax, d)) \
+                + 8 * (count * n * smax + count * iters + (count + 1) // 2)
+        calls = split_vbx_jobs(job_s, call_bytes, workspace_bytes)
+        out = [None] * len(jobs)
+        with torch.cuda.device(device):
+            gamma0 = torch.from_numpy(np.concatenate([np.ascontiguousarray(q0, dtype=np.float64).reshape(-1)
+                                                      for q0 in inits])).to(device)
+            phi = torch.from_numpy(np.ascontiguousarray(self.plda.phi, dtype=np.float64)).to(device)
+            for call in calls:
+                J, smax = len(call), max(job_s[j] for j in call)
+                table = np.array([[offsets[jobs[j][0]], job_s[j]] for j in call], dtype=np.int64)
+                factors = np.array([[float(jobs[j][1]), float(jobs[j][2])] for j in call], dtype=np.float64)
+                job_init, job_f = torch.from_numpy(table).to(device), torch.from_numpy(factors).to(device)
+                # one buffer, one download: gamma (J, n smax), the ELBO histories (J, iters), the iteration counts
+                buffer = torch.zeros(J * n * smax + J * iters + (J + 1) // 2, dtype=torch.float64, device=device)
+                gamma, elbo = buffer[:J * n * smax], buffer[J * n * smax:J * n * smax + J * iters]
+                counts = buffer[J * n * smax + J * iters:].view(torch.int32)
+                ws = torch.empty(lib.pa_vbx_batch_workspace_bytes(J, n, smax, d), dtype=torch.uint8, device=device)
+                ffi.check(lib.pa_vbx_run_batch(ffi.ptr(fea), ffi.ptr(phi), n, d, J, ffi.ptr(gamma0), gamma0.numel(),
+                                               ffi.ptr(job_init), ffi.ptr(job_f), smax, iters,
+                                               float(self.elbo_epsilon), ffi.ptr(gamma), ffi.ptr(elbo),
+                                               ffi.ptr(counts), ffi.ptr(ws), ws.numel(), ffi.stream()),
+                          "pa_vbx_run_batch")
+                host = buffer.cpu().numpy()
+                done = host[J * n * smax + J * iters:].view(np.int32)
+                for k, j in enumerate(call):
+                    if done[k] < 1:
+                        raise RuntimeError("pa_vbx_run_batch left a job untouched: its table entry is out of range")
+                    q = host[k * n * smax:k * n * smax + n * job_s[j]].reshape(n, job_s[j]).copy()
+                    history = host[J * n * smax + k * iters:J * n * smax + k * iters + done[k]].tolist()
+                    out[j] = (q, history)
+        self.last_vbx_calls = len(calls)
+        return out
+
+    def before_cut(self, embeddings: np.ndarray, segmentations: SlidingWindowFeature, num_clean_frames=None):
+        """what a file needs before the AHC cut, none of it a function of threshold, Fa or Fb: the training
+        embeddings, their unit vectors, the centroid linkage of those and the PLDA features (kept on the device).
+        None with fewer than two training embeddings."""
+        train, _, _ = self.filter_embeddings(embeddings, segmentations=segmentations,
+                                             num_clean_frames=num_clean_frames)
+        if train.shape[0] < 2:
+            return None
+        Z, unit = self._unit_linkage(train)
+        return train, unit, Z, self.plda.transform_device(train, self.device)
+
+    def after_vbx(self, embeddings: np.ndarray, segmentations: SlidingWindowFeature, train: np.ndarray,
+                  unit: np.ndarray, q: np.ndarray, num_clusters: Optional[int] = None, min_clusters=1,
+                  max_clusters=np.inf, active_frames=None, assign_on_device: bool = False):
+        """from the responsibilities `q` to (hard, soft, centroids): speakers whose prior collapsed are pruned, the
+        centroids are `W.T @ train` on the host, a violated bound falls back to KMeans, silent local speakers are
+        pushed out of the assignment.  `assign_on_device`: the constrained assignment through
+        `constrained_argmax_device`, whose silent rows are -2 (the pipeline masks them to -2 anyway)."""
+        pi = q.sum(axis=0)
+        priors = pi / pi.sum()
+        W = q[:, priors > self.prune_below]
+        centroids = W.T @ train / W.sum(axis=0, keepdims=True).T
+        constrained = self.constrained_assignment
+        found = centroids.shape[0]
+        self.timings["vbx_speakers"] = found
+        # a violated bound (or an explicit number that VBx did not find) falls back to KMeans on the
+        # unit vectors, without the assignment constraint (clustering.py:624-645)
+        if found < min_clusters:
+            num_clusters = min_clusters
+        elif found > max_clusters:
+            num_clusters = max_clusters
+        if num_clusters and num_clusters != found:
+            from sklearn.cluster import KMeans
+            constrained = False
+            km = KMeans(n_clusters=num_clusters, n_init=3, random_state=42, copy_x=False).fit_predict(unit)
+            centroids = segment_means(train, km, num_clusters)
+        soft = self._similarities(embeddings, centroids)
+        if constrained:
+            # silent local speakers must never win a cluster in the assignment (:658-660)
+            silent = (segmentations.data.sum(axis=1) == 0) if active_frames is None else (active_frames == 0)
+            soft[silent] = soft.min() - 1.0
+            hard = self.constrained_argmax_device(soft, silent) if assign_on_device else self.constrained_argmax(soft)
+        else:
+            hard = np.argmax(soft, axis=2)
+        return hard.reshape(embeddings.shape[:2]), soft, centroids
 
     def __call__(self, embeddings: np.ndarray, segmentations: Optional[SlidingWindowFeature] = None,
                  num_clusters: Optional[int] = None, min_clusters: Optional[int] = None,
@@ -494,35 +648,30 @@ class VBxClustering(BaseClustering):
         labels, unit = self._ahc_labels(train)
         t1 = time.perf_counter()
         fea = self.plda.transform_device(train, self.device)
-        q, priors = self._vbx(fea, labels)
+        q, _ = self._vbx(fea, labels)
         t2 = time.perf_counter()
-        W = q[:, priors > self.prune_below]
-        centroids = W.T @ train / W.sum(axis=0, keepdims=True).T
-        constrained = self.constrained_assignment
-        found = centroids.shape[0]
-        # a violated bound (or an explicit number that VBx did not find) falls back to KMeans on the
-        # unit vectors, without the assignment constraint (clustering.py:624-645)
-        if found < min_clusters:
-            num_clusters = min_clusters
-        elif found > max_clusters:
-            num_clusters = max_clusters
-        if num_clusters and num_clusters != found:
-            from sklearn.cluster import KMeans
-            constrained = False
-            km = KMeans(n_clusters=num_clusters, n_init=3, random_state=42, copy_x=False).fit_predict(unit)
-            centroids = segment_means(train, km, num_clusters)
-        soft = self._similarities(embeddings, centroids)
-        if constrained:
-            # silent local speakers must never win a cluster in the assignment (:658-660)
-            silent = (segmentations.data.sum(axis=1) == 0) if kwargs.get("active_frames") is None \
-                else (kwargs["active_frames"] == 0)
-            soft[silent] = soft.min() - 1.0
-            hard = self.constrained_argmax(soft)
-        else:
-            hard = np.argmax(soft, axis=2)
+        out = self.after_vbx(embeddings, segmentations, train, unit, q, num_clusters=num_clusters,
+                             min_clusters=min_clusters, max_clusters=max_clusters,
+                             active_frames=kwargs.get("active_frames"))
         self.timings.update(ahc=t1 - t0, vbx=t2 - t1, assign=time.perf_counter() - t2,
                             num_embeddings=train.shape[0])
-        return hard.reshape(embeddings.shape[:2]), soft, centroids
+        return out
+
+
+def split_vbx_jobs(job_sizes: list, bytes_of: Callable, budget: Optional[int] = None) -> list:
+    """the jobs of one `VBxClustering.vbx_batch`, in order, as consecutive runs of job indices: a run is as long as
+    `bytes_of(jobs in it, largest S in it)` stays within `budget` (None: one run); a single job over the budget
+    still gets a run of its own.  Runs are also cut at the 65 535 jobs one launch takes."""
+    runs, run, largest = [], [], 0
+    for j, s in enumerate(job_sizes):
+        if run and (len(run) >= 65535 or (budget is not None and bytes_of(len(run) + 1, max(s, largest)) > budget)):
+            runs.append(run)
+            run, largest = [], 0
+        run.append(j)
+        largest = max(largest, s)
+    if run:
+        runs.append(run)
+    return runs
 
 
 class OracleClustering(BaseClustering):

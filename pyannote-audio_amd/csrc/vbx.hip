@@ -11,6 +11,8 @@
 // hipcc-flags: -ffp-contract=off
 #include "common.h"
 
+#include <algorithm>
+
 namespace pa {
 
 constexpr int VB_T = 256;
@@ -96,20 +98,19 @@ __global__ __launch_bounds__(VB_T) void k_vbx_prepare(const double* __restrict__
 
 // M step for speaker s = blockIdx.x: Nk = sum_n gamma[n,s]; invL (17), alpha (16);
 // cterm[s] = 0.5 sum_d (invL + alpha^2) Phi;  eterm[s] = sum_d (log invL - invL - alpha^2 + 1)  (25)
-__global__ __launch_bounds__(VB_T) void k_vbx_mstep(const double* __restrict__ gamma,
-                                                   const double* __restrict__ rho, int N, int S, int D,
-                                                   const double* __restrict__ Phi, double FaFb,
-                                                   double* __restrict__ alpha, double* __restrict__ invL,
-                                                   double* __restrict__ Nk, double* __restrict__ cterm,
-                                                   double* __restrict__ eterm) {
-  __shared__ double red[VB_T / 64];
-  const int s = blockIdx.x;
+// (one body for the per-file kernel and the batched one below: the two must agree bit for bit)
+__device__ __forceinline__ void vbx_mstep_body(int s, const double* __restrict__ gamma,
+                                               const double* __restrict__ rho, int N, int S, int D,
+                                               const double* __restrict__ Phi, double FaFb,
+                                               double* __restrict__ alpha, double* __restrict__ invL,
+                                               double* __restrict__ Nk, double* __restrict__ cterm,
+                                               double* __restrict__ eterm, double* part_sm, double* red) {
   double part = 0.0;
   for (int n = threadIdx.x; n < N; n += VB_T) part += gamma[(long)n * S + s];
   const double nk = block_sum_d(part, red);
   // (gamma^T rho)[s, :]: the N rows are split over the VB_T / 128 thread groups, 4 independent partial
   // sums per thread; partials are combined in a fixed order (deterministic, not numpy's BLAS order)
-  extern __shared__ double part_sm[];  // [VB_T / 128][D]
+  // part_sm: [VB_T / 128][D]
   constexpr int DP = 128, NP = VB_T / DP;
   const int p = threadIdx.x / DP, dl = threadIdx.x % DP;
   const int n0 = (int)((long)N * p / NP), n1 = (int)((long)N * (p + 1) / NP);
@@ -147,21 +148,29 @@ __global__ __launch_bounds__(VB_T) void k_vbx_mstep(const double* __restrict__ g
   }
 }
 
+__global__ __launch_bounds__(VB_T) void k_vbx_mstep(const double* __restrict__ gamma,
+                                                   const double* __restrict__ rho, int N, int S, int D,
+                                                   const double* __restrict__ Phi, double FaFb,
+                                                   double* __restrict__ alpha, double* __restrict__ invL,
+                                                   double* __restrict__ Nk, double* __restrict__ cterm,
+                                                   double* __restrict__ eterm) {
+  __shared__ double red[VB_T / 64];
+  extern __shared__ double part_sm[];  // [VB_T / 128][D]
+  vbx_mstep_body(blockIdx.x, gamma, rho, N, S, D, Phi, FaFb, alpha, invL, Nk, cterm, eterm, part_sm, red);
+}
+
 // E step for frame n = blockIdx.x: log_p[s] = Fa (rho_n . alpha_s - cterm[s] + G[n]) (23);
 // lpi[s] = log(pi[s] + 1e-8) with pi = Nk / sum Nk (uniform in the first iteration);
 // log_p_x = logsumexp_s(log_p + lpi);  gamma[n,s] = exp(log_p + lpi - log_p_x)
-__global__ __launch_bounds__(VB_T) void k_vbx_estep(const double* __restrict__ rho,
-                                                   const double* __restrict__ alpha,
-                                                   const double* __restrict__ cterm,
-                                                   const double* __restrict__ G,
-                                                   const double* __restrict__ Nk, int uniform_pi, int N,
-                                                   int S, int D, double Fa, double* __restrict__ gamma,
-                                                   double* __restrict__ logpx) {
-  extern __shared__ double sm[];  // D (rho_n) + S (scores)
-  __shared__ double red[VB_T / 64];
-  double* r = sm;
+__device__ __forceinline__ void vbx_estep_body(long n, const double* __restrict__ rho,
+                                               const double* __restrict__ alpha,
+                                               const double* __restrict__ cterm,
+                                               const double* __restrict__ G,
+                                               const double* __restrict__ Nk, int uniform_pi, int S, int D,
+                                               double Fa, double* __restrict__ gamma,
+                                               double* __restrict__ logpx, double* sm, double* red) {
+  double* r = sm;  // D (rho_n) + S (scores)
   double* sc = sm + D;
-  const long n = blockIdx.x;
   for (int d = threadIdx.x; d < D; d += VB_T) r[d] = rho[n * D + d];
   double tot = 0.0;
   for (int s = threadIdx.x; s < S; s += VB_T) tot += Nk[s];
@@ -184,17 +193,131 @@ __global__ __launch_bounds__(VB_T) void k_vbx_estep(const double* __restrict__ r
   if (threadIdx.x == 0) logpx[n] = lse;
 }
 
-// ELBO (25) = sum_n log_p_x[n] + 0.5 Fb sum_s eterm[s]: one workgroup, fixed summation tree
-__global__ __launch_bounds__(VB_T) void k_vbx_elbo(const double* __restrict__ logpx, int N,
-                                                  const double* __restrict__ eterm, int S, double Fb,
-                                                  double* __restrict__ out) {
+__global__ __launch_bounds__(VB_T) void k_vbx_estep(const double* __restrict__ rho,
+                                                   const double* __restrict__ alpha,
+                                                   const double* __restrict__ cterm,
+                                                   const double* __restrict__ G,
+                                                   const double* __restrict__ Nk, int uniform_pi, int N,
+                                                   int S, int D, double Fa, double* __restrict__ gamma,
+                                                   double* __restrict__ logpx) {
+  extern __shared__ double sm[];  // D (rho_n) + S (scores)
   __shared__ double red[VB_T / 64];
+  vbx_estep_body(blockIdx.x, rho, alpha, cterm, G, Nk, uniform_pi, S, D, Fa, gamma, logpx, sm, red);
+}
+
+// ELBO (25) = sum_n log_p_x[n] + 0.5 Fb sum_s eterm[s]: one workgroup, fixed summation tree
+// (every thread returns the value)
+__device__ __forceinline__ double vbx_elbo_body(const double* __restrict__ logpx, int N,
+                                                const double* __restrict__ eterm, int S, double Fb,
+                                                double* red) {
   double a = 0.0, b = 0.0;
   for (int n = threadIdx.x; n < N; n += VB_T) a += logpx[n];
   for (int s = threadIdx.x; s < S; s += VB_T) b += eterm[s];
   a = block_sum_d(a, red);
   b = block_sum_d(b, red);
-  if (threadIdx.x == 0) out[0] = a + Fb * 0.5 * b;
+  return a + Fb * 0.5 * b;
+}
+
+__global__ __launch_bounds__(VB_T) void k_vbx_elbo(const double* __restrict__ logpx, int N,
+                                                  const double* __restrict__ eterm, int S, double Fb,
+                                                  double* __restrict__ out) {
+  __shared__ double red[VB_T / 64];
+  const double v = vbx_elbo_body(logpx, N, eterm, S, Fb, red);
+  if (threadIdx.x == 0) out[0] = v;
+}
+
+// ---- a batch of VB inferences over the same features (pa_vbx_run_batch) ----------------------------------
+// A job is (initial responsibilities, S_j, Fa_j, Fb_j); rho and G are shared.  Every round is the three steps
+// above with the job as blockIdx.y; a job's ELBO workgroup applies the convergence test and raises the job's
+// `done` flag, after which all of its workgroups return at entry.  Per-job buffers sit at a common stride
+// (sized for the largest S of the call); inside its slab a job uses its own S_j as the row length, so the
+// index arithmetic -- and with it every sum -- is the per-file kernels'.
+struct VbxJob {
+  long gamma0;  // offset of the job's initial responsibilities (N, S) in the gamma0 buffer, in doubles
+  int S;        // 0: the job table names responsibilities outside the buffer or more clusters than Smax
+  double Fa, Fb;
+};
+
+struct VbxBatch {
+  const int64_t* job_init;  // [J][2]: offset into gamma0, S
+  const double* job_f;      // [J][2]: Fa, Fb
+  long gamma0_len;
+  double* gamma;    // [J][N * Smax]
+  double* logpx;    // [J][N]
+  double* alpha;    // [J][Smax * D]
+  double* invL;     // [J][Smax * D]
+  double* Nk;       // [J][Smax] (also cterm, eterm)
+  double* cterm;
+  double* eterm;
+  double* elbo;     // [J][max_iterations]
+  int* iterations;  // [J]
+  int* done;        // [J]
+  int N, D, Smax, max_iterations;
+};
+
+// a job the kernels must not touch (its iteration count stays 0) comes back with S = 0
+__device__ __forceinline__ VbxJob vbx_job(const VbxBatch& b, int j) {
+  VbxJob job;
+  job.gamma0 = b.job_init[2 * j];
+  const int64_t S = b.job_init[2 * j + 1];
+  const bool ok = S >= 1 && S <= b.Smax && job.gamma0 >= 0 && job.gamma0 + (long)b.N * S <= b.gamma0_len;
+  job.S = ok ? (int)S : 0;
+  job.Fa = b.job_f[2 * j];
+  job.Fb = b.job_f[2 * j + 1];
+  return job;
+}
+
+__global__ __launch_bounds__(VB_T) void k_vbx_batch_begin(VbxBatch b, const double* __restrict__ gamma0) {
+  const int j = blockIdx.y;
+  const VbxJob job = vbx_job(b, j);
+  const long count = (long)b.N * job.S;
+  const double* src = gamma0 + job.gamma0;
+  double* dst = b.gamma + (long)j * b.N * b.Smax;
+  for (long i = (long)blockIdx.x * VB_T + threadIdx.x; i < count; i += (long)gridDim.x * VB_T) dst[i] = src[i];
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    b.done[j] = job.S == 0;
+    b.iterations[j] = 0;
+  }
+}
+
+__global__ __launch_bounds__(VB_T) void k_vbx_batch_mstep(VbxBatch b, const double* __restrict__ rho,
+                                                         const double* __restrict__ Phi) {
+  __shared__ double red[VB_T / 64];
+  extern __shared__ double part_sm[];
+  const int j = blockIdx.y;
+  if (b.done[j]) return;
+  const VbxJob job = vbx_job(b, j);
+  if ((int)blockIdx.x >= job.S) return;
+  const long sd = (long)j * b.Smax * b.D, ss = (long)j * b.Smax;
+  vbx_mstep_body(blockIdx.x, b.gamma + (long)j * b.N * b.Smax, rho, b.N, job.S, b.D, Phi, job.Fa / job.Fb,
+                 b.alpha + sd, b.invL + sd, b.Nk + ss, b.cterm + ss, b.eterm + ss, part_sm, red);
+}
+
+__global__ __launch_bounds__(VB_T) void k_vbx_batch_estep(VbxBatch b, const double* __restrict__ rho,
+                                                         const double* __restrict__ G, int first) {
+  __shared__ double red[VB_T / 64];
+  extern __shared__ double sm[];
+  const int j = blockIdx.y;
+  if (b.done[j]) return;
+  const VbxJob job = vbx_job(b, j);
+  const long sd = (long)j * b.Smax * b.D, ss = (long)j * b.Smax;
+  vbx_estep_body(blockIdx.x, rho, b.alpha + sd, b.cterm + ss, G, b.Nk + ss, first, job.S, b.D, job.Fa,
+                 b.gamma + (long)j * b.N * b.Smax, b.logpx + (long)j * b.N, sm, red);
+}
+
+// the test of the host loop (clustering.py: `it > 0 and elbo[it] - elbo[it - 1] < epsilon`), in double
+__global__ __launch_bounds__(VB_T) void k_vbx_batch_elbo(VbxBatch b, int it, double epsilon) {
+  __shared__ double red[VB_T / 64];
+  const int j = blockIdx.x;
+  if (b.done[j]) return;
+  const VbxJob job = vbx_job(b, j);
+  const double v = vbx_elbo_body(b.logpx + (long)j * b.N, b.N, b.eterm + (long)j * b.Smax, job.S, job.Fb, red);
+  if (threadIdx.x == 0) {
+    double* history = b.elbo + (long)j * b.max_iterations;
+    history[it] = v;
+    b.iterations[j] = it + 1;
+    if (it > 0 && v - history[it - 1] < epsilon) b.done[j] = 1;
+  }
 }
 
 }  // namespace pa
@@ -247,6 +370,77 @@ int pa_vbx_iteration(const double* fea, const double* Phi, int n, int s, int d, 
                      first, n, s, d, Fa, gamma, logpx);
   hipLaunchKernelGGL(pa::k_vbx_elbo, dim3(1), dim3(pa::VB_T), 0, st, logpx, n, eterm, s, Fb, elbo_out);
   PA_CHECK_LAUNCH("pa_vbx_iteration");
+  return 0;
+}
+
+static size_t vbx_align(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
+
+size_t pa_vbx_batch_workspace_bytes(int jobs, int n, int smax, int d) {
+  if (jobs <= 0 || n <= 0 || smax <= 0 || d <= 0) return 0;
+  const size_t J = (size_t)jobs;
+  // shared: rho (n d) + G (n); per job: logpx (n) + alpha, invL (smax d each) + Nk, cterm, eterm (smax each)
+  // + its `done` flag
+  return vbx_align(8 * ((size_t)n * d + n)) + vbx_align(8 * J * n) + 2 * vbx_align(8 * J * smax * d) +
+         3 * vbx_align(8 * J * smax) + vbx_align(J * sizeof(int));
+}
+
+// Whole VB inferences of `jobs` jobs over the same features `fea` (n, d), no read-back and no host
+// synchronisation: job j starts from the (n, S_j) responsibilities at gamma0 + job_init[2 j] (read-only; several
+// jobs may name the same ones), S_j = job_init[2 j + 1] <= smax, and runs with Fa = job_f[2 j], Fb = job_f[2 j + 1]
+// (both tables on the device).  `max_iterations` rounds are enqueued; a job whose ELBO gain falls below `epsilon`
+// stops taking part.  gamma (jobs, n * smax): job j's final (n, S_j) responsibilities, contiguous at the start
+// of its slab; elbo (jobs, max_iterations): the history, valid up to iterations[j] (int32, jobs; 0 for a job
+// whose table entry is out of range, which is left alone).  Per job, bit for bit what `max_iterations` calls
+// of pa_vbx_iteration with the host's test give.
+int pa_vbx_run_batch(const double* fea, const double* Phi, int n, int d, int jobs, const double* gamma0,
+                     long gamma0_len, const int64_t* job_init, const double* job_f, int smax,
+                     int max_iterations, double epsilon, double* gamma, double* elbo, int32_t* iterations,
+                     void* workspace, size_t workspace_bytes, void* stream) {
+  if (n <= 0 || jobs <= 0) return 0;
+  PA_REQUIRE(d == 128, "pa_vbx_run_batch: the PLDA space has 128 dimensions");
+  PA_REQUIRE(jobs <= 65535 && max_iterations >= 1, "pa_vbx_run_batch: bad job or iteration count");
+  PA_REQUIRE(smax >= 1 && (size_t)(d + smax) * 8 <= 64 * 1024,
+             "pa_vbx_run_batch: too many clusters for one workgroup");
+  PA_REQUIRE(workspace_bytes >= pa_vbx_batch_workspace_bytes(jobs, n, smax, d),
+             "pa_vbx_run_batch: workspace too small");
+  const size_t J = (size_t)jobs;
+  char* w = (char*)workspace;
+  auto take = [&](size_t bytes) {
+    char* p = w;
+    w += vbx_align(bytes);
+    return p;
+  };
+  double* rho = (double*)take(8 * ((size_t)n * d + n));
+  double* G = rho + (size_t)n * d;
+  pa::VbxBatch b;
+  b.logpx = (double*)take(8 * J * n);
+  b.alpha = (double*)take(8 * J * smax * d);
+  b.invL = (double*)take(8 * J * smax * d);
+  b.Nk = (double*)take(8 * J * smax);
+  b.cterm = (double*)take(8 * J * smax);
+  b.eterm = (double*)take(8 * J * smax);
+  b.done = (int*)take(J * sizeof(int));
+  b.job_init = job_init;
+  b.job_f = job_f;
+  b.gamma0_len = gamma0_len;
+  b.gamma = gamma;
+  b.elbo = elbo;
+  b.iterations = iterations;
+  b.N = n, b.D = d, b.Smax = smax, b.max_iterations = max_iterations;
+  hipStream_t st = (hipStream_t)stream;
+  pa::ProfScope prof("k_vbx_run_batch", stream, 4.0 * n * (double)smax * d * jobs * max_iterations,
+                     8.0 * jobs * max_iterations * (2.0 * n * smax + 2.0 * n * d));
+  hipLaunchKernelGGL(pa::k_vbx_prepare, dim3(n), dim3(pa::VB_T), 0, st, fea, n, d, Phi, rho, G);
+  const int copy_blocks = (int)std::min<size_t>(64, ((size_t)n * smax + pa::VB_T - 1) / pa::VB_T);
+  hipLaunchKernelGGL(pa::k_vbx_batch_begin, dim3(copy_blocks, jobs), dim3(pa::VB_T), 0, st, b, gamma0);
+  for (int it = 0; it < max_iterations; ++it) {
+    hipLaunchKernelGGL(pa::k_vbx_batch_mstep, dim3(smax, jobs), dim3(pa::VB_T), (size_t)(pa::VB_T / 128) * d * 8,
+                       st, b, rho, Phi);
+    hipLaunchKernelGGL(pa::k_vbx_batch_estep, dim3(n, jobs), dim3(pa::VB_T), (size_t)(d + smax) * 8, st, b, rho,
+                       G, (int)(it == 0));
+    hipLaunchKernelGGL(pa::k_vbx_batch_elbo, dim3(jobs), dim3(pa::VB_T), 0, st, b, it, epsilon);
+  }
+  PA_CHECK_LAUNCH("pa_vbx_run_batch");
   return 0;
 }
 

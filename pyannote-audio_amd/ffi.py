@@ -271,6 +271,12 @@ _OPTIONAL: list[tuple] = [
     ("pa_vbx_workspace_bytes", [C.c_int, C.c_int, C.c_int], C.c_size_t),
     ("pa_vbx_iteration", [c_fp, c_fp, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, c_fp, c_fp,
                           c_fp, C.c_size_t, c_fp], C.c_int),
+    ("pa_vbx_batch_workspace_bytes", [C.c_int, C.c_int, C.c_int, C.c_int], C.c_size_t),
+    ("pa_vbx_run_batch", [c_fp, c_fp, C.c_int, C.c_int, C.c_int, c_fp, C.c_long, c_fp, c_fp, C.c_int, C.c_int,
+                          C.c_double, c_fp, c_fp, c_fp, c_fp, C.c_size_t, c_fp], C.c_int),
+    ("pa_constrained_assign_max_speakers", [], C.c_int),
+    ("pa_constrained_assign_max_clusters", [], C.c_int),
+    ("pa_constrained_assign", [c_fp, c_fp, C.c_int, C.c_int, C.c_int, c_fp, c_fp, c_fp], C.c_int),
     ("pa_stats_pool", [c_fp, C.c_int, C.c_int, C.c_int, C.c_int, c_fp, C.c_int, C.c_int, c_fp, c_fp,
                        c_fp], C.c_int),
     ("pa_stats_pool_rows", [c_fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_fp, C.c_int, C.c_int, c_fp,

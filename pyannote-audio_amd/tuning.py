@@ -10,12 +10,18 @@ candidate `clustering.threshold` / `min_cluster_size`), organised so that a cand
                      and the metric -- and not even those when an earlier candidate gave this file the same
                      `hard_clusters` (two thresholds between the same pair of merge heights do): its results are copies
 
+With `VBxClustering` (threshold, Fa, Fb; `sweep_vbx`) the dendrogram of the unit vectors and the PLDA projection are
+the per-file part, and what the candidates of a file share further is worked out by `plan_vbx_jobs`: equal cuts are one
+initialisation, distinct (initialisation, Fa, Fb) triples one VB inference, all of them jobs of `pa_vbx_run_batch`
+(DESIGN.md section 26).
+
 There is no sampler, no journal and no `pyannote.database` here: the candidates are a grid in the order given, files
 are dicts as `evaluation.benchmark` takes them ("annotation", optionally "annotated" and "pipeline_kwargs")."""
 from __future__ import annotations
 
 import copy
 import time
+import warnings
 from dataclasses import dataclass, field, replace
 from datetime import datetime
 from pathlib import Path
@@ -24,7 +30,7 @@ from typing import Callable, Iterable, Optional
 import numpy as np
 
 from . import distance
-from .clustering import AgglomerativeClustering, Dendrogram
+from .clustering import AgglomerativeClustering, Dendrogram, VBxClustering
 from .evaluation import get_diarization
 
 
@@ -37,6 +43,7 @@ class _Prepared:
     bounds: tuple
     trees: dict = field(default_factory=dict)     # method -> None or (tree, train, chunk_idx, speaker_idx, bounds)
     evaluated: list = field(default_factory=list)  # [(train labels, hard_clusters, hypothesis, components, other params)]
+    vbx: object = False      # VBxClustering: False until asked, then None or (train, unit, tree, PLDA features on the device)
 
 
 def best_entry(entries: list, direction: str = "minimize") -> dict:
@@ -51,6 +58,25 @@ def best_entry(entries: list, direction: str = "minimize") -> dict:
     return best
 
 
+def plan_vbx_jobs(cut_rows: np.ndarray, picks: list) -> tuple:
+    """What one file's VBx candidates share.  `cut_rows` (T, n): the AHC labels at the T distinct thresholds;
+    `picks`: per candidate (row of `cut_rows`, Fa, Fb), in candidate order.  Returns
+      inits    the rows that get an initialisation: the first of every run of equal rows, in row order
+      jobs     the distinct (index into `inits`, Fa, Fb) triples, in order of first use: one VB inference each
+      job_of   per candidate, its index into `jobs`"""
+    seen, inits, init_of_row = {}, [], []
+    for t, row in enumerate(cut_rows):
+        key = np.ascontiguousarray(row).tobytes()
+        if key not in seen:
+            seen[key] = len(inits)
+            inits.append(t)
+        init_of_row.append(seen[key])
+    jobs, job_of = {}, []
+    for row, Fa, Fb in picks:
+        job_of.append(jobs.setdefault((init_of_row[row], float(Fa), float(Fb)), len(jobs)))
+    return inits, list(jobs), job_of
+
+
 class ClusteringTuner:
     """`ClusteringTuner(pipeline).prepare(files).sweep(thresholds, min_cluster_sizes)` -> {"entries": [{"params",
     "loss"} per candidate, thresholds outermost], "best": the first minimum, "shared_evaluations": how many (candidate,
@@ -59,7 +85,19 @@ class ClusteringTuner:
     `metric`: a factory of fresh metrics (default `pipeline.get_metric`); the loss of a candidate is `abs(metric)`
     after every file, i.e. what `pipeline.instantiate(params)`, `pipeline(file)` per file and
     `metric(file["annotation"], output, uem=file.get("annotated"))` give.  Every parameter but the two swept ones
-    stays as the pipeline is instantiated; the pipeline is left instantiated with the last candidate."""
+    stays as the pipeline is instantiated; the pipeline is left instantiated with the last candidate.
+
+    With `VBxClustering` (`sweep_vbx(thresholds, Fas, Fbs)`), per file: the linkage and the PLDA projection once, every
+    candidate threshold from one `Dendrogram.cuts` call, and the VB inferences of all candidates -- one per distinct
+    (cut, Fa, Fb) -- from `pa_vbx_run_batch` calls that no iteration reads back from (`VBxClustering.vbx_batch`);
+    per candidate the centroids (host), the assignment (`pa_constrained_assign`), the back end and the metric."""
+
+    #: bound on what one `pa_vbx_run_batch` call allocates (kernel workspace + result buffer); a file's jobs beyond it
+    #: take several calls
+    workspace_bytes: int = 1 << 30
+    #: False: a VBxClustering candidate goes through the pipeline's own call on the cached front end, like any other
+    #: clustering without a dendrogram to share (what tools/time_vbx_tuning.py measures the batched route against)
+    batch_vbx: bool = True
 
     def __init__(self, pipeline, metric: Optional[Callable] = None):
         self.pipeline = pipeline
@@ -71,6 +109,11 @@ class ClusteringTuner:
         self.train_clusters: list = []
         #: per candidate, per file: the speaker diarization that was scored
         self.hypotheses: list = []
+        #: per candidate, per file: VB iterations of the candidate's inference (None where none was run)
+        self.vbx_iterations: list = []
+        #: of the last `evaluate` with VBxClustering: candidates x files with an inference, VB inferences run,
+        #: initialisations built, `pa_vbx_run_batch` calls
+        self.vbx_shared: dict = {}
 
     # ------------------------------------------------------------------------------------------ preparation
     def prepare(self, files: Iterable) -> "ClusteringTuner":
@@ -121,6 +164,42 @@ class ClusteringTuner:
                 item.trees[method] = (tree, train, chunk_idx, speaker_idx, bounds)
         return item.trees[method]
 
+    def _vbx_front(self, item: _Prepared):
+        """`VBxClustering.before_cut`, once per file: None where the pipeline's own call decides (a silent file,
+        fewer than two training embeddings)"""
+        if item.vbx is False:
+            front, clustering = item.front, self.pipeline.clustering
+            item.vbx = None
+            if clustering.plda is not None and clustering.plda.lda_dimension != 128:
+                # `pa_vbx_run_batch` is built for the 128 PLDA dimensions of the published models
+                warnings.warn(f"ClusteringTuner: a PLDA of {clustering.plda.lda_dimension} dimensions is not batched; every "
+                              "VBx candidate goes through the pipeline's own call")
+            elif front is not None and not front.silent and clustering.plda is not None:
+                with distance.device_to_ourselves():
+                    before = clustering.before_cut(front.embeddings, front.segmentations, num_clean_frames=front.clean)
+                if before is not None:
+                    train, unit, Z, fea = before
+                    item.vbx = (train, unit, Dendrogram(Z), fea)
+        return item.vbx
+
+    def _vbx_file(self, item: _Prepared, thresholds: list, picks: list) -> Optional[dict]:
+        """every candidate's VB inference on one file: {"job_of": per candidate, "q": per job (responsibilities,
+        ELBO history), "finished": per job, filled by `_evaluate`}"""
+        plan = self._vbx_front(item)
+        if plan is None:
+            return None
+        clustering = self.pipeline.clustering
+        _, _, tree, fea = plan
+        rows = tree.cuts(thresholds, device=self.cut_device())
+        rows = np.stack([np.unique(row, return_inverse=True)[1] for row in rows])
+        inits, jobs, job_of = plan_vbx_jobs(rows, picks)
+        starts = [clustering.initial_responsibilities(rows[t]) for t in inits]
+        results = clustering.vbx_batch(fea, starts, jobs, workspace_bytes=self.workspace_bytes)
+        for name, more in (("candidates", len(picks)), ("jobs", len(jobs)), ("initialisations", len(inits)),
+                           ("calls", clustering.last_vbx_calls)):
+            self.vbx_shared[name] = self.vbx_shared.get(name, 0) + more
+        return {"job_of": job_of, "q": results, "finished": {}}
+
     #: "device" cuts every dendrogram with `pa_dendrogram_cuts` on the pipeline's GPU, "host" runs the same plan
     #: through numpy (profiles/clustering_tuning_timing.txt has both at one audio-hour)
     cut_on: str = "device"
@@ -151,34 +230,66 @@ class ClusteringTuner:
             raise ValueError("ClusteringTuner.sweep: a threshold is NaN")
         return self.evaluate(self.candidates(thresholds, min_cluster_sizes))
 
+    def sweep_vbx(self, thresholds, Fas, Fbs) -> dict:
+        """the grid `thresholds` x `Fas` x `Fbs` of a `VBxClustering` pipeline: thresholds outermost, then Fa, then Fb"""
+        if not isinstance(getattr(self.pipeline, "clustering", None), VBxClustering):
+            raise TypeError("ClusteringTuner.sweep_vbx: the pipeline's clustering is not VBxClustering")
+        grid = [(float(t), float(a), float(b)) for t in thresholds for a in Fas for b in Fbs]
+        if any(np.isnan(point).any() for point in grid):
+            raise ValueError("ClusteringTuner.sweep_vbx: a threshold, Fa or Fb is NaN")
+        base = self.pipeline.parameters(instantiated=True)
+        candidates = []
+        for threshold, Fa, Fb in grid:
+            params = copy.deepcopy(base)
+            params["clustering"].update(threshold=threshold, Fa=Fa, Fb=Fb)
+            candidates.append(params)
+        return self.evaluate(candidates)
+
     def evaluate(self, candidates: list) -> dict:
         """any list of parameter dicts, in order.  With `AgglomerativeClustering` every file's dendrogram (one per
-        linkage method among the candidates) is cut ONCE, at the thresholds of all candidates."""
+        linkage method among the candidates) is cut ONCE, at the thresholds of all candidates; with `VBxClustering`
+        the VB inferences of all candidates on a file are the jobs of batched launches (`_vbx_file`)."""
         if not self.prepared:
             raise RuntimeError("ClusteringTuner: call prepare(files) first")
         pipeline = self.pipeline
         agglomerative = isinstance(getattr(pipeline, "clustering", None), AgglomerativeClustering)
+        vbx = self.batch_vbx and isinstance(getattr(pipeline, "clustering", None), VBxClustering)
         self.shared_evaluations = self.evaluations = 0
-        self.train_clusters, self.hypotheses = [], []
+        self.train_clusters, self.hypotheses, self.vbx_iterations = [], [], []
+        self.vbx_shared = {}
         for item in self.prepared:
             item.evaluated = []
-        thresholds, cuts = [], {}
-        if agglomerative:
+        thresholds, cuts, inferences = [], {}, {}
+        if agglomerative or vbx:
             thresholds = list(dict.fromkeys(float(params["clustering"]["threshold"]) for params in candidates))
+        if vbx and any(np.isnan(thresholds)):
+            raise ValueError("ClusteringTuner.evaluate: a threshold is NaN")
         row_of = {t: k for k, t in enumerate(thresholds)}
+        picks = [(row_of[float(p["clustering"]["threshold"])], float(p["clustering"]["Fa"]), float(p["clustering"]["Fb"]))
+                 for p in candidates] if vbx else []
         previous = pipeline.training
         pipeline.training = True      # (the generic path goes through the pipeline's call: cached front ends there too)
         entries = []
         try:
-            for params in candidates:
+            for c, params in enumerate(candidates):
                 pipeline.instantiate(params)
                 # results are shared only between candidates that differ in nothing but the clustering
                 self._beyond_clustering = repr({name: value for name, value in params.items() if name != "clustering"})
                 metric = self.metric()
                 self.train_clusters.append([])
                 self.hypotheses.append([])
+                self.vbx_iterations.append([])
                 for i, item in enumerate(self.prepared):
                     labels = None
+                    if vbx and item.front is not None:
+                        if i not in inferences:
+                            inferences[i] = self._vbx_file(item, thresholds, picks)
+                        inference = inferences[i]
+                        self._evaluate(item, None, metric,
+                                       vbx=None if inference is None else (inference, inference["job_of"][c]))
+                        self.train_clusters[-1].append(self._train_clusters)
+                        self.vbx_iterations[-1].append(self._vbx_iterations)
+                        continue
                     if agglomerative and item.front is not None and not item.front.silent:
                         key = (i, pipeline.clustering.method)
                         if key not in cuts:
@@ -188,6 +299,7 @@ class ClusteringTuner:
                             labels = cuts[key][row_of[float(pipeline.clustering.threshold)]]
                     self._evaluate(item, labels, metric)
                     self.train_clusters[-1].append(self._train_clusters)
+                    self.vbx_iterations[-1].append(None)
                 entries.append({"params": params, "loss": abs(metric)})
         finally:
             pipeline.training = previous
@@ -195,12 +307,14 @@ class ClusteringTuner:
         return {"entries": entries, "best": best_entry(entries, direction),
                 "shared_evaluations": self.shared_evaluations, "evaluations": self.evaluations}
 
-    def _evaluate(self, item: _Prepared, cut_labels, metric):
-        """one file under the currently instantiated candidate, accumulated into `metric`"""
+    def _evaluate(self, item: _Prepared, cut_labels, metric, vbx=None):
+        """one file under the currently instantiated candidate, accumulated into `metric`.  `vbx`: (the file's
+        inferences from `_vbx_file`, this candidate's job)"""
         pipeline, front, file = self.pipeline, item.front, item.file
         self.evaluations += 1
-        self._train_clusters = None
-        if front is None or not isinstance(getattr(pipeline, "clustering", None), AgglomerativeClustering):
+        self._train_clusters = self._vbx_iterations = None
+        batched = AgglomerativeClustering if not self.batch_vbx else (AgglomerativeClustering, VBxClustering)
+        if front is None or not isinstance(getattr(pipeline, "clustering", None), batched):
             # another clustering (or pipeline): the candidate through its own `__call__`; with `training` set a
             # SpeakerDiarization takes the front end from the cache that `prepare` filled
             return self._score(metric, file, get_diarization(pipeline(file)), None)
@@ -209,7 +323,19 @@ class ClusteringTuner:
         num_speakers, min_speakers, max_speakers = item.bounds
         clustering = pipeline.clustering
         train_labels = None
-        if cut_labels is None:       # one cluster whatever the candidate says (`_tree`)
+        if vbx is not None:
+            inference, job = vbx
+            q, history = inference["q"][job]
+            self._vbx_iterations = len(history)
+            if job not in inference["finished"]:      # (candidates that differ beyond the clustering share a job)
+                train, unit, _, _ = item.vbx
+                hard, _, centroids = clustering.after_vbx(
+                    front.embeddings, front.segmentations, train, unit, q, num_clusters=num_speakers,
+                    min_clusters=1 if min_speakers is None else min_speakers,
+                    max_clusters=np.inf if max_speakers is None else max_speakers, assign_on_device=True)
+                inference["finished"][job] = (hard, centroids, clustering.timings["vbx_speakers"])
+            hard, centroids, self._train_clusters = inference["finished"][job]
+        elif cut_labels is None:       # one cluster whatever the candidate says (`_tree`), or the pipeline's own route
             hard, centroids = pipeline._cluster_one(front, num_speakers, min_speakers, max_speakers)
         else:
             tree, train, chunk_idx, speaker_idx, (num, lo, hi) = item.trees[clustering.method]
