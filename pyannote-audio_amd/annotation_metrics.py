@@ -249,9 +249,7 @@ class _AnnotationMetric(BaseMetric):
         (`evaluation.Corpus.counts` takes those of all files in one device call)"""
         components = self.components_from_counts(counts)
         components[self.metric_name_] = self.compute_metric(components)
-        self.results_.append((uri or "NA", components))
-        for name in self.components_:
-            self.accumulated_[name] += components[name]
+        self.add_components(components, uri or "NA")
         return components if detailed else components[self.metric_name_]
 
     def report(self) -> dict:

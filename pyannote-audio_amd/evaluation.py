@@ -5,7 +5,9 @@
 `Corpus` lists the turns of all files once and, on a `cuda` device, uploads them once; `Corpus.counts(fill)` then
 gives every file's `annotation_counts(reference, hypothesis.support(fill), uem)` from one device call
 (`pa_annot_corpus_counts`, include/pyannote_amd.h) and one download.  That is the call the gap
-search repeats for every candidate: the corpus does not change between candidates, only `fill` does.
+search repeats for every candidate: the corpus does not change between candidates, only `fill` does.  `CorpusCall`
+is the one place that knows the table format of that call; `tuning.candidate_counts` fills it too, with rows that are
+already on the device.
 
 Reports are dicts (`_AnnotationMetric.report`); pandas is not required."""
 from __future__ import annotations
@@ -26,12 +28,91 @@ from . import ffi
 from .core import Annotation
 
 
+# ------------------------------------------------------------------------------- one `pa_annot_corpus` call
+def cut_slots(Nr: int, Nh: int, Nu: int) -> int:
+    """cut slots of a file with that many reference, hypothesis and uem rows (sized with a collar)"""
+    return 2 * (Nr + Nh + Nu) + 4 * Nr
+
+
+def output_values(Kr: int, Kh: int) -> int:
+    """values in the output block of a file with that many labels a side (`pa_annot_counts`)"""
+    return Kr * Kh + Kr + Kh + len(am._SCALARS)
+
+
+def corpus_workspace_bytes(hyp_rows: int, slots: int) -> int:
+    """`annot_corpus_workspace` (csrc/annot_metrics.hip) from the totals of a call, for sizing a call before it has
+    tables (tests/test_evaluation_cpu.py holds it to `pa_annot_corpus_workspace_bytes`)"""
+    return 256 + 36 * hyp_rows + 44 * slots
+
+
 def _int32(values) -> np.ndarray:
+    values = np.asarray(values)
+    if values.size and int(values.max()) > 0x7fffffff:
+        raise ValueError("more rows in one counts call than 32-bit tables index (a tuner: lower workspace_bytes)")
     return np.ascontiguousarray(values, dtype=np.int32)
 
 
 def _offsets(sizes) -> np.ndarray:
     return _int32(np.concatenate([[0], np.cumsum(sizes, dtype=np.int64)]))
+
+
+class CorpusCall:
+    """One `pa_annot_corpus` (include/pyannote_amd.h), its workspace and its result buffer, and
+    every tensor the struct points into: they live as long as this object.
+
+    Per file: `Nr`, `Nh`, `Nu` rows and `Kr`, `Kh` labels; per run (a hypothesis label of a file, files in order)
+    `run_sizes` rows, listed in `run_rows` as indices into the hypothesis rows.  `arrays`: "ref_seg", "hyp_seg",
+    "uem_seg" (float64 rows), "ref_label", "hyp_label" (None: the kernels label a row by its run), each a numpy array
+    -- uploaded here, with the tables, in ONE copy -- or a tensor on `device`, used where it lies."""
+
+    def __init__(self, device, Nr, Nh, Nu, Kr, Kh, run_sizes, run_rows, arrays: dict):
+        host = {"ref_off": _offsets(Nr), "hyp_off": _offsets(Nh), "uem_off": _offsets(Nu),
+                "cut_off": _offsets([cut_slots(a, b, c) for a, b, c in zip(Nr, Nh, Nu)]),
+                "out_off": _offsets([output_values(a, b) for a, b in zip(Kr, Kh)]),
+                "Kr": _int32(Kr), "Kh": _int32(Kh), "run_first": _offsets(Kh),
+                "run_off": _offsets(run_sizes), "run_rows": _int32(run_rows)}
+        F = len(host["Kr"])
+        upload = {name: np.ascontiguousarray(a, dtype=np.float64).ravel() if name.endswith("_seg") else _int32(a)
+                  for name, a in arrays.items() if isinstance(a, np.ndarray)}
+        upload.update(host)
+        starts = np.cumsum([0] + [(a.nbytes + 7) // 8 for a in upload.values()])      # every array starts on 8 bytes
+        packed = np.zeros(int(starts[-1]), dtype=np.float64)
+        for a, s, e in zip(upload.values(), starts, starts[1:]):
+            packed[s:e].view(a.dtype)[:len(a)] = a
+        packed = torch.from_numpy(packed).to(device)
+        struct = ffi.AnnotCorpus()
+        struct.F, struct.R = F, int(host["run_first"][-1])
+        for (name, a), s in zip(upload.items(), starts):
+            setattr(struct, name, packed.data_ptr() + 8 * int(s) if len(a) else None)
+        for name, a in arrays.items():
+            if isinstance(a, torch.Tensor):
+                setattr(struct, name, a.data_ptr() if a.numel() else None)
+        for name in ("ref_off", "hyp_off", "uem_off", "Kr", "Kh"):
+            setattr(struct, "h_" + name, host[name].ctypes.data)
+        self.device, self.struct, self._alive = device, struct, (host, packed, arrays)
+        ws_bytes = int(ffi.load().pa_annot_corpus_workspace_bytes(ctypes.byref(struct)))
+        if ws_bytes == 0:
+            raise ValueError("the tables are more than pa_annot_corpus_counts accepts (65535 files, "
+                             f"{am.MAX_LABELS} labels a side and 2^22 cuts a file)")
+        self._ws = torch.empty(ws_bytes, dtype=torch.uint8, device=device)
+        # [the files' output blocks][merged rows, int32, two to a float64]: one download
+        self.out_off = host["out_off"]
+        self.out = torch.empty(int(self.out_off[-1]) + (F + 1) // 2, dtype=torch.float64, device=device)
+
+    def run(self, fill: float, collar: float, skip_overlap: bool) -> torch.Tensor:
+        """`pa_annot_corpus_counts` -> the result buffer on the device; nothing is copied back here"""
+        merged = self.out[int(self.out_off[-1]):].view(torch.int32)
+        with torch.cuda.device(self.device):
+            ffi.check(ffi.load().pa_annot_corpus_counts(ctypes.byref(self.struct), float(fill), float(collar),
+                                                        int(bool(skip_overlap)), ffi.ptr(self.out), ffi.ptr(merged),
+                                                        ffi.ptr(self._ws), self._ws.numel(), ffi.stream()),
+                      "pa_annot_corpus_counts")
+        return self.out
+
+    def split(self, values: np.ndarray) -> tuple:
+        """the downloaded result buffer -> (per file its output values, per file its merged row count)"""
+        off = self.out_off
+        return [values[a:b] for a, b in zip(off[:-1], off[1:])], values[int(off[-1]):].view(np.int32)[:len(off) - 1]
 
 
 class Corpus:
@@ -71,74 +152,25 @@ class Corpus:
             self._upload()
 
     # ------------------------------------------------------------------------------------------- device side
-    @staticmethod
-    def _tables(rows) -> dict:
-        """the int32 tables of `pa_annot_corpus` (include/pyannote_amd.h) for the files' row tuples"""
-        Nr, Nh, Nu = ([len(r[i]) for r in rows] for i in (1, 4, 6))
-        Kr, Kh = [len(r[0]) for r in rows], [len(r[3]) for r in rows]
-        host = {"ref_off": _offsets(Nr), "hyp_off": _offsets(Nh), "uem_off": _offsets(Nu),
-                "cut_off": _offsets([2 * (a + b + c) + 4 * a for a, b, c in zip(Nr, Nh, Nu)]),
-                "out_off": _offsets([a * b + a + b + len(am._SCALARS) for a, b in zip(Kr, Kh)]),
-                "Kr": _int32(Kr), "Kh": _int32(Kh), "run_first": _offsets(Kh)}
-        run_sizes, run_rows = [], []
-        for f, r in enumerate(rows):
-            seg, lab = r[4], r[5]
-            order = np.lexsort((seg[:, 1], seg[:, 0], lab))     # by label, then (start, end): the order `support` walks
-            run_rows.append(host["hyp_off"][f] + order)
-            run_sizes.append(np.bincount(lab, minlength=Kh[f]))
-        host["run_off"] = _offsets(np.concatenate(run_sizes))
-        host["run_rows"] = _int32(np.concatenate(run_rows))
-        return host
-
     def _upload(self):
-        """one packed buffer: the float64 rows, then the int32 labels and tables of `pa_annot_corpus`"""
+        """the rows and labels of the files evaluated on the device, and their runs in the order `support` walks"""
         rows = [self._rows[f] for f in self._device_files]
-        F = len(rows)
-        host = self._tables(rows)
-        f64 = [np.concatenate([r[i].ravel() for r in rows]) for i in (1, 4, 6)]
-        i32 = [np.concatenate([r[i] for r in rows]).astype(np.int32) for i in (2, 5)]
-        names = ["ref_label", "hyp_label"] + list(host)
-        i32 += [host[name] for name in names[2:]]
-        sizes = [len(a) + (len(a) & 1) for a in i32]             # (every table starts on 8 bytes)
-        ints = np.zeros(sum(sizes), dtype=np.int32)
-        starts = np.concatenate([[0], np.cumsum(sizes)])
-        for a, s in zip(i32, starts):
-            ints[s:s + len(a)] = a
-        n64 = sum(len(a) for a in f64)
-        packed = torch.from_numpy(np.concatenate(f64 + [ints.view(np.float64)])).to(self.device)
-        words = packed[n64:].view(torch.int32)
-        struct = ffi.AnnotCorpus()
-        struct.F, struct.R = F, int(host["run_first"][-1])
-        at = 0
-        for name, a in zip(("ref_seg", "hyp_seg", "uem_seg"), f64):
-            setattr(struct, name, packed.data_ptr() + 8 * at if len(a) else None)
-            at += len(a)
-        for name, a, s in zip(names, i32, starts):
-            setattr(struct, name, words.data_ptr() + 4 * int(s) if len(a) else None)
-        for name in ("ref_off", "hyp_off", "uem_off", "Kr", "Kh"):
-            setattr(struct, "h_" + name, host[name].ctypes.data)
-        self._host, self._packed, self._struct = host, packed, struct
-        ws_bytes = int(ffi.load().pa_annot_corpus_workspace_bytes(ctypes.byref(struct)))
-        if ws_bytes == 0:
-            raise ValueError("the corpus is more than the device evaluation accepts (65535 files, "
-                             f"{am.MAX_LABELS} labels a side and 2^22 cuts a file)")
-        self._ws = torch.empty(ws_bytes, dtype=torch.uint8, device=self.device)
-        # [the files' output blocks][merged rows, int32, two to a float64]: one download
-        self._nout = int(host["out_off"][-1])
-        self._out = torch.empty(self._nout + (F + 1) // 2, dtype=torch.float64, device=self.device)
+        first, run_sizes, run_rows = 0, [], []
+        for _, _, _, hyp_labels, seg, lab, _ in rows:
+            run_rows.append(first + np.lexsort((seg[:, 1], seg[:, 0], lab)))     # by label, then (start, end)
+            run_sizes.append(np.bincount(lab, minlength=len(hyp_labels)))
+            first += len(seg)
+        names = ("ref_seg", "ref_label", "hyp_seg", "hyp_label", "uem_seg")
+        self._call = CorpusCall(self.device, *([len(r[i]) for r in rows] for i in (1, 4, 6, 0, 3)),
+                                np.concatenate(run_sizes), np.concatenate(run_rows),
+                                {name: np.concatenate([r[i] for r in rows]) for name, i in zip(names, (1, 2, 4, 5, 6))})
 
     def device_counts(self, fill: float, collar: float = 0.0, skip_overlap: bool = False) -> torch.Tensor:
         """`pa_annot_corpus_counts` on the uploaded corpus -> the device buffer (the output blocks of the files that
         are evaluated on the device, then their merged row counts as int32); nothing is copied back here"""
         if not self._device_files:
             raise RuntimeError("no file of this corpus is evaluated on a device")
-        merged = self._out[self._nout:].view(torch.int32)
-        with torch.cuda.device(self.device):
-            ffi.check(ffi.load().pa_annot_corpus_counts(ctypes.byref(self._struct), float(fill), float(collar),
-                                                        int(bool(skip_overlap)), ffi.ptr(self._out), ffi.ptr(merged),
-                                                        ffi.ptr(self._ws), self._ws.numel(), ffi.stream()),
-                      "pa_annot_corpus_counts")
-        return self._out
+        return self._call.run(fill, collar, skip_overlap)
 
     # ------------------------------------------------------------------------------------------------ counts
     def counts(self, fill: float, collar: float = 0.0, skip_overlap: bool = False) -> list:
@@ -151,11 +183,9 @@ class Corpus:
         flat: dict = {}
         rows_after: dict = {}
         if self._device_files:
-            host = self.device_counts(fill, collar, skip_overlap).cpu().numpy()
-            merged = host[self._nout:].view(np.int32)
-            off = self._host["out_off"]
+            values, merged = self._call.split(self.device_counts(fill, collar, skip_overlap).cpu().numpy())
             for k, f in enumerate(self._device_files):
-                flat[f], rows_after[f] = host[off[k]:off[k + 1]], int(merged[k])
+                flat[f], rows_after[f] = values[k], int(merged[k])
         results = []
         for f, (file, r) in enumerate(zip(self.files, self._rows)):
             ref_labels, ref_seg, ref_lab, hyp_labels, _, _, uem_seg = r

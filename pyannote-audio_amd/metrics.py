@@ -192,10 +192,14 @@ class BaseMetric:
         components[self.metric_name_] = self.compute_metric(components)
         if uri is None:
             uri = getattr(reference, "uri", None) or "NA"
+        self.add_components(components, uri)
+        return components if detailed else components[self.metric_name_]
+
+    def add_components(self, components: dict, uri: str):
+        """accumulates one file's components (with the file's value under the metric's name), computed anywhere"""
         self.results_.append((uri, components))
         for name in self.components_:
             self.accumulated_[name] += components[name]
-        return components if detailed else components[self.metric_name_]
 
     def __abs__(self):
         return self.compute_metric(self.accumulated_)

@@ -1,7 +1,8 @@
-"""Tuning on a corpus.  `DetectionTuner` (second half of this file) tunes the thresholds of the detection pipelines;
-`ClusteringTuner` the clustering of a `SpeakerDiarization` pipeline on a corpus: the search the reference's `optimize` command
-runs (src/pyannote/audio/__main__.py:116-283 -- the pipeline applied to every development file again for every
-candidate `clustering.threshold` / `min_cluster_size`), organised so that a candidate only pays for what depends on it.
+"""Tuning on a corpus.  `DetectionTuner` (below `ClusteringTuner`, after `candidate_counts`, the counts of all its
+candidates on a file) tunes the thresholds of the detection pipelines; `ClusteringTuner` the clustering of a
+`SpeakerDiarization` pipeline: the search the reference's `optimize` command runs
+(src/pyannote/audio/__main__.py:116-283 -- the pipeline applied to every development file again for every candidate
+`clustering.threshold` / `min_cluster_size`), organised so that a candidate only pays for what depends on it.
 
   once per file      the front end (both networks; kept in the file dict by the pipeline's training cache),
                      `filter_embeddings` and the dendrogram (it depends on `method`, not on the threshold)
@@ -28,22 +29,59 @@ from pathlib import Path
 from typing import Callable, Iterable, Optional
 
 import numpy as np
+import torch
 
+from . import annotation_metrics as am
 from . import distance
 from .clustering import AgglomerativeClustering, Dendrogram, VBxClustering
-from .evaluation import get_diarization
+from .evaluation import CorpusCall, corpus_workspace_bytes, cut_slots, get_diarization
+
+
+@dataclass
+class _Tree:
+    """what `BaseClustering.__call__` does before the cut, for one file and linkage method"""
+    tree: Dendrogram
+    train: np.ndarray          # the filtered embeddings the tree was built from
+    chunk_idx: np.ndarray
+    speaker_idx: np.ndarray
+    bounds: tuple              # (num, min, max) clusters of `set_num_clusters`
+
+
+@dataclass
+class _VBxFront:
+    """`VBxClustering.before_cut` of one file"""
+    train: np.ndarray
+    unit: np.ndarray
+    tree: Dendrogram
+    fea: object                # PLDA features on the device
+
+
+@dataclass
+class _Outcome:
+    """one (candidate, file): what its route found (`hard` None: still to be assigned from `train_labels`) and, once
+    its back end and metric have run, what later candidates with an equal clustering share"""
+    hard: Optional[np.ndarray] = None
+    centroids: Optional[np.ndarray] = None
+    train_labels: Optional[np.ndarray] = None
+    train_clusters: Optional[int] = None
+    vbx_iterations: Optional[int] = None
+    hypothesis: object = None
+    components: Optional[dict] = None
+    other: str = ""            # the candidate's parameters beyond the clustering
 
 
 @dataclass
 class _Prepared:
     """one file of the corpus: its validated dict, its (cached) front end, the speaker bounds of its
-    `pipeline_kwargs`, and per linkage method what the clustering needs before the cut"""
+    `pipeline_kwargs`, what the clustering needs before the cut, and what the candidates of one `evaluate` share
+    (`cuts`, `evaluated` and the "jobs" of `vbx` start empty with every `evaluate`)"""
     file: dict
     front: object
     bounds: tuple
-    trees: dict = field(default_factory=dict)     # method -> None or (tree, train, chunk_idx, speaker_idx, bounds)
-    evaluated: list = field(default_factory=list)  # [(train labels, hard_clusters, hypothesis, components, other params)]
-    vbx: object = False      # VBxClustering: False until asked, then None or (train, unit, tree, PLDA features on the device)
+    trees: dict = field(default_factory=dict)      # linkage method -> None or _Tree
+    vbx: dict = field(default_factory=dict)        # once asked: "front" -> None or _VBxFront, "jobs" -> `_vbx_file`
+    cuts: dict = field(default_factory=dict)       # linkage method -> the tree's `cuts` at the candidates' thresholds
+    evaluated: list = field(default_factory=list)  # [_Outcome] whose back end and metric were run
 
 
 def best_entry(entries: list, direction: str = "minimize") -> dict:
@@ -98,6 +136,9 @@ class ClusteringTuner:
     #: False: a VBxClustering candidate goes through the pipeline's own call on the cached front end, like any other
     #: clustering without a dendrogram to share (what tools/time_vbx_tuning.py measures the batched route against)
     batch_vbx: bool = True
+    #: "device" cuts every dendrogram with `pa_dendrogram_cuts` on the pipeline's GPU, "host" runs the same plan
+    #: through numpy (profiles/clustering_tuning_timing.txt has both at one audio-hour)
+    cut_on: str = "device"
 
     def __init__(self, pipeline, metric: Optional[Callable] = None):
         self.pipeline = pipeline
@@ -142,7 +183,7 @@ class ClusteringTuner:
         front = pipeline._cached_front_end(file, pipeline.setup_hook(file, None))
         return _Prepared(file=file, front=front, bounds=bounds)
 
-    def _tree(self, item: _Prepared):
+    def _tree(self, item: _Prepared) -> Optional[_Tree]:
         """what `BaseClustering.__call__` does before the cut, once per file and linkage method.  The tree is kept
         with the training copy it was built from: `dendrogram` normalises that copy in place for the geometric
         methods and `cluster_from_cut` takes the small-cluster centroids from it, so every method gets a fresh copy
@@ -161,15 +202,15 @@ class ClusteringTuner:
             else:
                 with distance.device_to_ourselves():
                     tree = Dendrogram(clustering.dendrogram(train))
-                item.trees[method] = (tree, train, chunk_idx, speaker_idx, bounds)
+                item.trees[method] = _Tree(tree, train, chunk_idx, speaker_idx, bounds)
         return item.trees[method]
 
-    def _vbx_front(self, item: _Prepared):
+    def _vbx_front(self, item: _Prepared) -> Optional[_VBxFront]:
         """`VBxClustering.before_cut`, once per file: None where the pipeline's own call decides (a silent file,
         fewer than two training embeddings)"""
-        if item.vbx is False:
+        if "front" not in item.vbx:
             front, clustering = item.front, self.pipeline.clustering
-            item.vbx = None
+            item.vbx["front"] = None
             if clustering.plda is not None and clustering.plda.lda_dimension != 128:
                 # `pa_vbx_run_batch` is built for the 128 PLDA dimensions of the published models
                 warnings.warn(f"ClusteringTuner: a PLDA of {clustering.plda.lda_dimension} dimensions is not batched; every "
@@ -179,30 +220,25 @@ class ClusteringTuner:
                     before = clustering.before_cut(front.embeddings, front.segmentations, num_clean_frames=front.clean)
                 if before is not None:
                     train, unit, Z, fea = before
-                    item.vbx = (train, unit, Dendrogram(Z), fea)
-        return item.vbx
+                    item.vbx["front"] = _VBxFront(train, unit, Dendrogram(Z), fea)
+        return item.vbx["front"]
 
     def _vbx_file(self, item: _Prepared, thresholds: list, picks: list) -> Optional[dict]:
         """every candidate's VB inference on one file: {"job_of": per candidate, "q": per job (responsibilities,
-        ELBO history), "finished": per job, filled by `_evaluate`}"""
+        ELBO history), "finished": per job, filled by `_vbx_route`}"""
         plan = self._vbx_front(item)
         if plan is None:
             return None
         clustering = self.pipeline.clustering
-        _, _, tree, fea = plan
-        rows = tree.cuts(thresholds, device=self.cut_device())
+        rows = plan.tree.cuts(thresholds, device=self.cut_device())
         rows = np.stack([np.unique(row, return_inverse=True)[1] for row in rows])
         inits, jobs, job_of = plan_vbx_jobs(rows, picks)
         starts = [clustering.initial_responsibilities(rows[t]) for t in inits]
-        results = clustering.vbx_batch(fea, starts, jobs, workspace_bytes=self.workspace_bytes)
+        results = clustering.vbx_batch(plan.fea, starts, jobs, workspace_bytes=self.workspace_bytes)
         for name, more in (("candidates", len(picks)), ("jobs", len(jobs)), ("initialisations", len(inits)),
                            ("calls", clustering.last_vbx_calls)):
             self.vbx_shared[name] = self.vbx_shared.get(name, 0) + more
         return {"job_of": job_of, "q": results, "finished": {}}
-
-    #: "device" cuts every dendrogram with `pa_dendrogram_cuts` on the pipeline's GPU, "host" runs the same plan
-    #: through numpy (profiles/clustering_tuning_timing.txt has both at one audio-hour)
-    cut_on: str = "device"
 
     def cut_device(self):
         return self.pipeline.clustering.device if self.cut_on == "device" else None
@@ -252,21 +288,24 @@ class ClusteringTuner:
         if not self.prepared:
             raise RuntimeError("ClusteringTuner: call prepare(files) first")
         pipeline = self.pipeline
-        agglomerative = isinstance(getattr(pipeline, "clustering", None), AgglomerativeClustering)
-        vbx = self.batch_vbx and isinstance(getattr(pipeline, "clustering", None), VBxClustering)
+        clustering = getattr(pipeline, "clustering", None)
+        # the route of every (candidate, file): None is the candidate through the pipeline's own `__call__`
+        route = self._cut_route if isinstance(clustering, AgglomerativeClustering) else \
+            self._vbx_route if self.batch_vbx and isinstance(clustering, VBxClustering) else None
         self.shared_evaluations = self.evaluations = 0
         self.train_clusters, self.hypotheses, self.vbx_iterations = [], [], []
         self.vbx_shared = {}
         for item in self.prepared:
-            item.evaluated = []
-        thresholds, cuts, inferences = [], {}, {}
-        if agglomerative or vbx:
-            thresholds = list(dict.fromkeys(float(params["clustering"]["threshold"]) for params in candidates))
-        if vbx and any(np.isnan(thresholds)):
-            raise ValueError("ClusteringTuner.evaluate: a threshold is NaN")
-        row_of = {t: k for k, t in enumerate(thresholds)}
-        picks = [(row_of[float(p["clustering"]["threshold"])], float(p["clustering"]["Fa"]), float(p["clustering"]["Fb"]))
-                 for p in candidates] if vbx else []
+            item.cuts, item.evaluated = {}, []
+            item.vbx.pop("jobs", None)
+        row_of, picks = {}, []       # threshold -> row of a file's cuts; VBx: per candidate (row, Fa, Fb)
+        if route is not None:
+            row_of = {t: k for k, t in enumerate(dict.fromkeys(float(p["clustering"]["threshold"]) for p in candidates))}
+        if route == self._vbx_route:
+            if any(np.isnan(list(row_of))):
+                raise ValueError("ClusteringTuner.evaluate: a threshold is NaN")
+            picks = [(row_of[float(p["clustering"]["threshold"])], float(p["clustering"]["Fa"]),
+                      float(p["clustering"]["Fb"])) for p in candidates]
         previous = pipeline.training
         pipeline.training = True      # (the generic path goes through the pipeline's call: cached front ends there too)
         entries = []
@@ -274,32 +313,15 @@ class ClusteringTuner:
             for c, params in enumerate(candidates):
                 pipeline.instantiate(params)
                 # results are shared only between candidates that differ in nothing but the clustering
-                self._beyond_clustering = repr({name: value for name, value in params.items() if name != "clustering"})
+                other = repr({name: value for name, value in params.items() if name != "clustering"})
                 metric = self.metric()
-                self.train_clusters.append([])
-                self.hypotheses.append([])
-                self.vbx_iterations.append([])
-                for i, item in enumerate(self.prepared):
-                    labels = None
-                    if vbx and item.front is not None:
-                        if i not in inferences:
-                            inferences[i] = self._vbx_file(item, thresholds, picks)
-                        inference = inferences[i]
-                        self._evaluate(item, None, metric,
-                                       vbx=None if inference is None else (inference, inference["job_of"][c]))
-                        self.train_clusters[-1].append(self._train_clusters)
-                        self.vbx_iterations[-1].append(self._vbx_iterations)
-                        continue
-                    if agglomerative and item.front is not None and not item.front.silent:
-                        key = (i, pipeline.clustering.method)
-                        if key not in cuts:
-                            plan = self._tree(item)
-                            cuts[key] = None if plan is None else plan[0].cuts(thresholds, device=self.cut_device())
-                        if cuts[key] is not None:
-                            labels = cuts[key][row_of[float(pipeline.clustering.threshold)]]
-                    self._evaluate(item, labels, metric)
-                    self.train_clusters[-1].append(self._train_clusters)
-                    self.vbx_iterations[-1].append(None)
+                done = []
+                for item in self.prepared:
+                    found = None if route is None or item.front is None else route(item, c, row_of, picks)
+                    done.append(self._evaluate(item, found, other, metric))
+                self.train_clusters.append([outcome.train_clusters for outcome in done])
+                self.vbx_iterations.append([outcome.vbx_iterations for outcome in done])
+                self.hypotheses.append([outcome.hypothesis for outcome in done])
                 entries.append({"params": params, "loss": abs(metric)})
         finally:
             pipeline.training = previous
@@ -307,69 +329,95 @@ class ClusteringTuner:
         return {"entries": entries, "best": best_entry(entries, direction),
                 "shared_evaluations": self.shared_evaluations, "evaluations": self.evaluations}
 
-    def _evaluate(self, item: _Prepared, cut_labels, metric, vbx=None):
-        """one file under the currently instantiated candidate, accumulated into `metric`.  `vbx`: (the file's
-        inferences from `_vbx_file`, this candidate's job)"""
+    def _cut_route(self, item: _Prepared, c: int, row_of: dict, picks: list) -> _Outcome:
+        """the candidate's row of the file's cuts -> training labels.  Nothing found: a silent file, or one cluster
+        whatever the candidate says (`_tree`)"""
+        clustering = self.pipeline.clustering
+        method = clustering.method
+        if item.front.silent:
+            return _Outcome()
+        if method not in item.cuts:
+            plan = self._tree(item)
+            item.cuts[method] = None if plan is None else plan.tree.cuts(list(row_of), device=self.cut_device())
+        if item.cuts[method] is None:
+            return _Outcome()
+        plan = item.trees[method]
+        num, lo, hi = plan.bounds
+        train_labels = clustering.cluster_from_cut(plan.train, plan.tree,
+                                                   item.cuts[method][row_of[float(clustering.threshold)]],
+                                                   min_clusters=lo, max_clusters=hi, num_clusters=num)
+        return _Outcome(train_labels=train_labels, train_clusters=int(np.max(train_labels)) + 1)
+
+    def _vbx_route(self, item: _Prepared, c: int, row_of: dict, picks: list) -> _Outcome:
+        """the candidate's job among the file's inferences (`_vbx_file`, once per file) -> hard clusters.  Nothing
+        found where `_vbx_front` leaves the file to the pipeline"""
+        if "jobs" not in item.vbx:
+            item.vbx["jobs"] = self._vbx_file(item, list(row_of), picks)
+        inference = item.vbx["jobs"]
+        if inference is None:
+            return _Outcome()
+        front, clustering = item.front, self.pipeline.clustering
+        num_speakers, min_speakers, max_speakers = item.bounds
+        job = inference["job_of"][c]
+        q, history = inference["q"][job]
+        if job not in inference["finished"]:      # (candidates that differ beyond the clustering share a job)
+            plan = item.vbx["front"]
+            hard, _, centroids = clustering.after_vbx(
+                front.embeddings, front.segmentations, plan.train, plan.unit, q, num_clusters=num_speakers,
+                min_clusters=1 if min_speakers is None else min_speakers,
+                max_clusters=np.inf if max_speakers is None else max_speakers, assign_on_device=True)
+            inference["finished"][job] = (hard, centroids, clustering.timings["vbx_speakers"])
+        hard, centroids, kept = inference["finished"][job]
+        return _Outcome(hard=hard, centroids=centroids, train_clusters=kept, vbx_iterations=len(history))
+
+    def _evaluate(self, item: _Prepared, found: Optional[_Outcome], other: str, metric) -> _Outcome:
+        """one file under the currently instantiated candidate, accumulated into `metric`: the tail all routes share.
+        `found`: what the route gave, None for the candidate through the pipeline's own `__call__`.  -> the outcome
+        with its hypothesis: that of an earlier candidate with the same `other` parameters and an equal clustering
+        of this file, whose back end and metric components are shared, or its own"""
         pipeline, front, file = self.pipeline, item.front, item.file
         self.evaluations += 1
-        self._train_clusters = self._vbx_iterations = None
-        batched = AgglomerativeClustering if not self.batch_vbx else (AgglomerativeClustering, VBxClustering)
-        if front is None or not isinstance(getattr(pipeline, "clustering", None), batched):
-            # another clustering (or pipeline): the candidate through its own `__call__`; with `training` set a
+        if found is None or front.silent:
+            # no route: another clustering (or pipeline) through its own `__call__`; with `training` set a
             # SpeakerDiarization takes the front end from the cache that `prepare` filled
-            return self._score(metric, file, get_diarization(pipeline(file)), None)
-        if front.silent:
-            return self._score(metric, file, get_diarization(pipeline._empty_output(file)), None)
+            output = pipeline(file) if found is None else pipeline._empty_output(file)
+            found = _Outcome(hypothesis=get_diarization(output))
+            self._score(metric, file, found.hypothesis)
+            return found
         num_speakers, min_speakers, max_speakers = item.bounds
-        clustering = pipeline.clustering
-        train_labels = None
-        if vbx is not None:
-            inference, job = vbx
-            q, history = inference["q"][job]
-            self._vbx_iterations = len(history)
-            if job not in inference["finished"]:      # (candidates that differ beyond the clustering share a job)
-                train, unit, _, _ = item.vbx
-                hard, _, centroids = clustering.after_vbx(
-                    front.embeddings, front.segmentations, train, unit, q, num_clusters=num_speakers,
-                    min_clusters=1 if min_speakers is None else min_speakers,
-                    max_clusters=np.inf if max_speakers is None else max_speakers, assign_on_device=True)
-                inference["finished"][job] = (hard, centroids, clustering.timings["vbx_speakers"])
-            hard, centroids, self._train_clusters = inference["finished"][job]
-        elif cut_labels is None:       # one cluster whatever the candidate says (`_tree`), or the pipeline's own route
-            hard, centroids = pipeline._cluster_one(front, num_speakers, min_speakers, max_speakers)
-        else:
-            tree, train, chunk_idx, speaker_idx, (num, lo, hi) = item.trees[clustering.method]
-            train_labels = clustering.cluster_from_cut(train, tree, cut_labels, min_clusters=lo, max_clusters=hi,
-                                                       num_clusters=num)
-            self._train_clusters = int(np.max(train_labels)) + 1
-            for known in item.evaluated:       # the same training labels: the same assignment, not computed again
-                if known[0] is not None and known[4] == self._beyond_clustering \
-                        and np.array_equal(known[0], train_labels):
-                    return self._share(metric, file, known)
-            hard, _, centroids = clustering.assign_embeddings(
-                front.embeddings, chunk_idx, speaker_idx, train_labels,
-                constrained=clustering.constrained_assignment, device_embeddings=front.dev_emb)
-        for known in item.evaluated:
-            if known[4] == self._beyond_clustering and np.array_equal(known[1], hard):
-                return self._share(metric, file, known)
+        same = [known for known in item.evaluated if known.other == other]
+        known = None
+        if found.train_labels is not None:       # the same training labels: the same assignment, not computed again
+            known = next((k for k in same if k.train_labels is not None
+                          and np.array_equal(k.train_labels, found.train_labels)), None)
+            if known is None:
+                plan, clustering = item.trees[pipeline.clustering.method], pipeline.clustering
+                found.hard, _, found.centroids = clustering.assign_embeddings(
+                    front.embeddings, plan.chunk_idx, plan.speaker_idx, found.train_labels,
+                    constrained=clustering.constrained_assignment, device_embeddings=front.dev_emb)
+        elif found.hard is None:                 # no route found anything: the pipeline's own clustering
+            found.hard, found.centroids = pipeline._cluster_one(front, num_speakers, min_speakers, max_speakers)
+        if known is None:
+            known = next((k for k in same if np.array_equal(k.hard, found.hard)), None)
+        if known is not None:
+            self.shared_evaluations += 1
+            found.hypothesis = known.hypothesis
+            self._score(metric, file, known.hypothesis, known.components)
+            return found
         fresh = replace(front, marks=[("start", time.perf_counter())], enqueued={})
-        output = pipeline._back_end(fresh, hard, centroids, min_speakers, max_speakers, pipeline.setup_hook(file, None))
-        hypothesis = get_diarization(output)
-        components = self._score(metric, file, hypothesis, None)
-        item.evaluated.append((train_labels, hard, hypothesis, components, self._beyond_clustering))
+        output = pipeline._back_end(fresh, found.hard, found.centroids, min_speakers, max_speakers,
+                                    pipeline.setup_hook(file, None))
+        found.hypothesis, found.other = get_diarization(output), other
+        found.components = self._score(metric, file, found.hypothesis)
+        item.evaluated.append(found)
+        return found
 
-    def _share(self, metric, file, known):
-        self.shared_evaluations += 1
-        self._score(metric, file, known[2], known[3])
-
-    def _score(self, metric, file, hypothesis, components):
+    @staticmethod
+    def _score(metric, file, hypothesis, components=None):
         """accumulates one file into `metric` and returns its components: computed by the metric, or -- for the
         package's metrics, whose accumulation is a sum of component dicts -- copied from an equal evaluation"""
-        self.hypotheses[-1].append(hypothesis)
         if components is not None and hasattr(metric, "accumulated_") and hasattr(metric, "results_"):
-            metric.results_.append((getattr(file["annotation"], "uri", None) or "NA", dict(components)))
-            for name in metric.accumulated_:
-                metric.accumulated_[name] += components[name]
+            metric.add_components(dict(components), getattr(file["annotation"], "uri", None) or "NA")
             return components
         computed = metric(file["annotation"], hypothesis, uem=file.get("annotated"), detailed=True)
         return computed if isinstance(computed, dict) else None
@@ -399,6 +447,62 @@ def _ranges(starts: np.ndarray, lengths: np.ndarray) -> np.ndarray:
     return np.repeat(starts - first, lengths) + np.arange(total, dtype=np.int64)
 
 
+def candidate_counts(item: _Detection, rows, offsets, counts, entry_jobs, todo, names, collar: float,
+                     skip_overlap: bool, device, workspace_bytes: int) -> dict:
+    """The metric's integrals of one file for the entries `todo` of `entry_jobs` (an entry: one job of the sweep per
+    class of `names`; `rows`, `offsets`, `counts`: the sweep's rows, where job j's begin, and how many it has).
+    -> entry -> (hypothesis labels in `labels()` order, the Kr Kh + Kr + Kh + 7 values of `pa_annot_counts`).
+    On `device`: `pa_annot_corpus_counts` with one corpus entry per (file, candidate) -- the reference and uem rows
+    repeated on the device, the hypothesis rows where the sweep left them (a job's rows are sorted: runs are plain
+    ranges), only the tables uploaded; one download per call, calls chunked at the entry point's limits and at
+    `workspace_bytes`.  Without a device, or for an entry beyond those limits: the host sweep."""
+    order = sorted(range(len(names)), key=lambda k: str(names[k]))         # `Annotation.labels()`
+    Nr, Nu, Kr = len(item.ref_seg), len(item.uem_seg), len(item.ref_labels)
+    labels, runs, Nh, slots = {}, {}, {}, {}
+    for e in todo:       # classes without rows are not labels of the hypothesis
+        picked = [k for k in order if counts[entry_jobs[e, k]] > 0]
+        labels[e] = [names[k] for k in picked]
+        runs[e] = np.array([int(entry_jobs[e, k]) for k in picked], dtype=np.int64)
+        Nh[e] = int(counts[runs[e]].sum())
+        slots[e] = cut_slots(Nr, Nh[e], Nu)
+    out = {}
+    entries = [e for e in todo if device is not None and Kr <= am.MAX_LABELS and slots[e] <= (1 << 22)]
+    if entries:
+        if device not in item.device_rows:
+            item.device_rows[device] = (torch.from_numpy(np.ascontiguousarray(item.ref_seg)).to(device),
+                                        torch.from_numpy(item.ref_lab.astype(np.int32)).to(device),
+                                        torch.from_numpy(np.ascontiguousarray(item.uem_seg)).to(device))
+        ref_seg, ref_lab, uem_seg = item.device_rows[device]
+        hyp = rows.to(device).contiguous()
+    at = 0
+    while at < len(entries):
+        chunk, hyp_rows, used = [], 0, 0
+        while at < len(entries) and len(chunk) < 65535 and (not chunk or corpus_workspace_bytes(
+                hyp_rows + Nh[entries[at]], used + slots[entries[at]]) <= workspace_bytes):
+            chunk.append(entries[at])
+            hyp_rows += Nh[entries[at]]
+            used += slots[entries[at]]
+            at += 1
+        F = len(chunk)
+        jobs = np.concatenate([runs[e] for e in chunk])
+        # (every entry reads the same reference and uem rows: repeated, so that the offset tables stay offsets)
+        call = CorpusCall(device, [Nr] * F, [Nh[e] for e in chunk], [Nu] * F, [Kr] * F, [len(runs[e]) for e in chunk],
+                          counts[jobs], _ranges(offsets[jobs], counts[jobs]),
+                          {"ref_seg": ref_seg.repeat(F, 1), "ref_label": ref_lab.repeat(F),
+                           "uem_seg": uem_seg.repeat(F, 1), "hyp_seg": hyp})
+        values, _ = call.split(call.run(0.0, collar, skip_overlap).cpu().numpy())
+        out.update({e: (labels[e], v) for e, v in zip(chunk, values)})
+    rest = [e for e in todo if e not in out]
+    if rest:
+        host_rows = rows.cpu().numpy()
+        for e in rest:
+            seg = np.concatenate([host_rows[offsets[j]:offsets[j + 1]] for j in runs[e]] or [np.zeros((0, 2))])
+            lab = np.repeat(np.arange(len(runs[e]), dtype=np.int32), counts[runs[e]])
+            out[e] = (labels[e], am._host_counts(item.ref_seg, item.ref_lab, Kr, seg, lab, len(labels[e]),
+                                                 item.uem_seg, collar, skip_overlap))
+    return out
+
+
 class DetectionTuner:
     """`DetectionTuner(pipeline).prepare(files).sweep(onsets, offsets, min_duration_ons, min_duration_offs)` for a
     `VoiceActivityDetection` or `MultiLabelSegmentation` pipeline -> {"entries": [{"params", "loss"} per candidate],
@@ -420,11 +524,10 @@ class DetectionTuner:
     Annotations built from the region lists.  `keep_hypotheses`: also keep every candidate's Annotations in
     `self.hypotheses[candidate][file]`.  The pipeline is left instantiated with the last candidate."""
 
-    #: bound on the workspace of one counts call (44 bytes per cut slot) and on the sweep's
+    #: bound on the workspace of one counts call (`evaluation.corpus_workspace_bytes`) and on the sweep's
     workspace_bytes: int = 1 << 30
 
     def __init__(self, pipeline, metric: Optional[Callable] = None, keep_hypotheses: bool = False):
-        from . import annotation_metrics as am
         from .multilabel import MultiLabelSegmentation
         from .voice_activity_detection import VoiceActivityDetection
         self.pipeline = pipeline
@@ -464,8 +567,6 @@ class DetectionTuner:
         return self
 
     def _prepare_one(self, file) -> _Detection:
-        import torch
-        from . import annotation_metrics as am
         from collections.abc import MutableMapping
         pipeline = self.pipeline
         origin, file = file, pipeline.prepare_one(file)
@@ -566,7 +667,6 @@ class DetectionTuner:
         """any list of parameter dicts (as `pipeline.instantiate` takes them), in order"""
         if not self.prepared:
             raise RuntimeError("DetectionTuner: call prepare(files) first")
-        from . import annotation_metrics as am
         candidates = list(candidates)
         K = len(self.classes)
         lanes, jobs, picks = {}, {}, []
@@ -587,8 +687,8 @@ class DetectionTuner:
 
         probe = self.metric()
         by_counts = hasattr(probe, "add_counts") and hasattr(probe, "collar") and hasattr(probe, "skip_overlap")
-        self._counts_device = am._device(getattr(probe, "device", None)) if by_counts else None
-        self._variant = (float(probe.collar), bool(probe.skip_overlap)) if by_counts else None
+        variant = (float(probe.collar), bool(probe.skip_overlap)) if by_counts else None
+        device = am._device(getattr(probe, "device", None)) if by_counts else None
         # distinct job tuples: two candidates with the same detectors share their counts
         distinct = {}
         entry_of = [distinct.setdefault(pick, len(distinct)) for pick in picks]
@@ -599,18 +699,19 @@ class DetectionTuner:
         self.collisions = 0
         for item in self.prepared:
             self._evaluate_file(item, (lane_class, onset, offset, job_lane, d_on, d_off), job_class, entry_jobs,
-                                entry_of, metrics, by_counts)
+                                entry_of, metrics, variant, device)
         entries = [{"params": params, "loss": abs(metric)} for params, metric in zip(candidates, metrics)]
         direction = self.pipeline.get_direction()
         return {"entries": entries, "best": best_entry(entries, direction),
                 "shared": {"candidates": len(candidates), "detectors": len(candidates) * K, "lanes": len(lanes),
                            "jobs": len(jobs), "counted": len(distinct), "collisions": self.collisions}}
 
-    def _evaluate_file(self, item: _Detection, tables, job_class, entry_jobs, entry_of, metrics, by_counts):
-        """one sweep and one counts call for all candidates, then every candidate's metric takes the file"""
-        from . import annotation_metrics as am
+    def _evaluate_file(self, item: _Detection, tables, job_class, entry_jobs, entry_of, metrics, variant, device):
+        """one sweep and one counts call for all candidates, then every candidate's metric takes the file.
+        `variant`: the (collar, skip_overlap) of metrics that take counts (on `device`), None for any other metric"""
         from . import frames as frame_ops
         K = len(self.classes)
+        by_counts = variant is not None
         want_tracks = K > 1 or self.keep_hypotheses or not by_counts
         rows, tracks, offsets = frame_ops.binarize_regions_sweep(
             item.scores, item.frames, *tables, return_tracks=want_tracks, to_host=False,
@@ -622,7 +723,8 @@ class DetectionTuner:
         host = None
         if by_counts:
             todo = [e for e in range(len(entry_jobs)) if e not in flagged]
-            flat = self._counts(item, rows, offsets, counts, entry_jobs, todo)
+            flat = candidate_counts(item, rows, offsets, counts, entry_jobs, todo,
+                                    [self._labels(k) for k in range(K)], *variant, device, self.workspace_bytes)
         need_annotations = self.keep_hypotheses or not by_counts or flagged
         if need_annotations:
             host = (rows.cpu().numpy(), tracks.cpu().numpy())
@@ -661,7 +763,6 @@ class DetectionTuner:
         """entries in which two classes hold a row with equal start, end and track position: the pipeline's
         Annotation is keyed by (segment, track name), so the later class overwrites the earlier one's row there.
         Those candidates are scored on the Annotation itself."""
-        import torch
         if rows.shape[0] == 0:
             return set()
         dev = rows.device
@@ -688,114 +789,6 @@ class DetectionTuner:
             if len(seen) > 1 and any(a & b for i, a in enumerate(seen) for b in seen[i + 1:]):
                 flagged.add(e)
         return flagged
-
-    def _counts(self, item: _Detection, rows, offsets, counts, entry_jobs, todo) -> dict:
-        """entry -> (hypothesis labels in `labels()` order, the Kr Kh + Kr + Kh + 7 values of `pa_annot_counts`)"""
-        from . import annotation_metrics as am
-        collar, skip_overlap = self._variant
-        names = [self._labels(k) for k in range(entry_jobs.shape[1])]
-        order = sorted(range(len(names)), key=lambda k: str(names[k]))         # `Annotation.labels()`
-        plans = {}
-        for e in todo:
-            runs = [int(entry_jobs[e, k]) for k in order if counts[entry_jobs[e, k]] > 0]
-            labels = [names[k] for k in order if counts[entry_jobs[e, k]] > 0]
-            plans[e] = (labels, np.array(runs, dtype=np.int64))
-        out = {}
-        device = self._counts_device
-        Nr, Nu, Kr = len(item.ref_seg), len(item.uem_seg), len(item.ref_labels)
-        on_device = [e for e in todo if device is not None and Kr <= am.MAX_LABELS
-                     and 2 * (Nr + Nu + int(counts[plans[e][1]].sum())) + 4 * Nr <= (1 << 22)]
-        if on_device:
-            out.update(self._device_counts(item, rows, offsets, counts, plans, on_device, device, collar,
-                                           skip_overlap))
-        rest = [e for e in todo if e not in out]
-        if rest:
-            host_rows = rows.cpu().numpy()
-            for e in rest:
-                labels, runs = plans[e]
-                seg = np.concatenate([host_rows[offsets[j]:offsets[j + 1]] for j in runs] or [np.zeros((0, 2))])
-                lab = np.repeat(np.arange(len(runs), dtype=np.int32), counts[runs]) if len(runs) \
-                    else np.zeros(0, dtype=np.int32)
-                out[e] = (labels, am._host_counts(item.ref_seg, item.ref_lab, Kr, seg, lab, len(labels), item.uem_seg,
-                                                  collar, skip_overlap))
-        return out
-
-    def _device_counts(self, item, rows, offsets, counts, plans, entries, device, collar, skip_overlap) -> dict:
-        """`pa_annot_corpus_counts` with one corpus entry per (file, candidate): the reference and uem rows repeated
-        on the device, the hypothesis rows where the sweep left them (a job's rows are sorted: runs are plain
-        ranges), only the offset tables built here.  One download per call; calls are chunked at the entry point's
-        limits and at `workspace_bytes`."""
-        import ctypes
-        import torch
-        from . import annotation_metrics as am
-        from . import ffi
-        lib = ffi.load()
-        Nr, Nu, Kr = len(item.ref_seg), len(item.uem_seg), len(item.ref_labels)
-        if device not in item.device_rows:
-            item.device_rows[device] = (torch.from_numpy(np.ascontiguousarray(item.ref_seg)).to(device),
-                                        torch.from_numpy(item.ref_lab.astype(np.int32)).to(device),
-                                        torch.from_numpy(np.ascontiguousarray(item.uem_seg)).to(device))
-        ref_seg, ref_lab, uem_seg = item.device_rows[device]
-        hyp = rows.to(device).contiguous()
-        out = {}
-        Nh = {e: int(counts[plans[e][1]].sum()) for e in entries}
-        slots = {e: 2 * (Nr + Nh[e] + Nu) + 4 * Nr for e in entries}
-        at = 0
-        while at < len(entries):
-            chunk, used = [], 0
-            while at < len(entries) and len(chunk) < 65535 and \
-                    (not chunk or 44 * (used + slots[entries[at]]) + 36 * sum(Nh[e] for e in chunk) <=
-                     self.workspace_bytes):
-                chunk.append(entries[at])
-                used += slots[entries[at]]
-                at += 1
-            F = len(chunk)
-            Kh = [len(plans[e][0]) for e in chunk]
-            runs = np.concatenate([plans[e][1] for e in chunk]) if sum(Kh) else np.zeros(0, dtype=np.int64)
-            host = {"ref_off": np.arange(F + 1, dtype=np.int64) * Nr, "uem_off": np.arange(F + 1, dtype=np.int64) * Nu,
-                    "hyp_off": np.concatenate([[0], np.cumsum([Nh[e] for e in chunk])]),
-                    "cut_off": np.concatenate([[0], np.cumsum([slots[e] for e in chunk])]),
-                    "out_off": np.concatenate([[0], np.cumsum([Kr * k + Kr + k + len(am._SCALARS) for k in Kh])]),
-                    "Kr": np.full(F, Kr), "Kh": np.array(Kh), "run_first": np.concatenate([[0], np.cumsum(Kh)]),
-                    "run_off": np.concatenate([[0], np.cumsum(counts[runs])]),
-                    "run_rows": _ranges(offsets[runs], counts[runs])}
-            if max(int(v.max()) if len(v) else 0 for v in host.values()) > 0x7fffffff:
-                raise ValueError("more rows in one counts call than 32-bit tables index: lower workspace_bytes")
-            host = {name: np.ascontiguousarray(v, dtype=np.int32) for name, v in host.items()}
-            sizes = [len(a) + (len(a) & 1) for a in host.values()]
-            starts = np.concatenate([[0], np.cumsum(sizes)])
-            packed = np.zeros(int(starts[-1]), dtype=np.int32)
-            for a, s in zip(host.values(), starts):
-                packed[s:s + len(a)] = a
-            words = torch.from_numpy(packed).to(device)
-            struct = ffi.AnnotCorpus()
-            struct.F, struct.R = F, int(host["run_first"][-1])
-            # (every entry reads the same reference and uem rows: repeated, so that the offset tables stay offsets)
-            refs, labs, uems = ref_seg.repeat(F, 1), ref_lab.repeat(F), uem_seg.repeat(F, 1)
-            struct.ref_seg = refs.data_ptr() if Nr else None
-            struct.ref_label = labs.data_ptr() if Nr else None
-            struct.uem_seg = uems.data_ptr() if Nu else None
-            struct.hyp_seg = hyp.data_ptr() if hyp.numel() else None
-            struct.hyp_label = None                       # (the kernels label a row by its run)
-            for name, a, s in zip(host, host.values(), starts):
-                setattr(struct, name, words.data_ptr() + 4 * int(s) if len(a) else None)
-            for name in ("ref_off", "hyp_off", "uem_off", "Kr", "Kh"):
-                setattr(struct, "h_" + name, host[name].ctypes.data)
-            with torch.cuda.device(device):
-                ws_bytes = int(lib.pa_annot_corpus_workspace_bytes(ctypes.byref(struct)))
-                if ws_bytes == 0:
-                    raise ValueError("pa_annot_corpus_counts refuses the candidates' tables")
-                ws = torch.empty(ws_bytes, dtype=torch.uint8, device=device)
-                nout = int(host["out_off"][-1])
-                buffer = torch.empty(nout + (F + 1) // 2, dtype=torch.float64, device=device)
-                merged = buffer[nout:].view(torch.int32)
-                ffi.check(lib.pa_annot_corpus_counts(ctypes.byref(struct), 0.0, collar, int(skip_overlap),
-                                                     ffi.ptr(buffer), ffi.ptr(merged), ffi.ptr(ws), ws_bytes,
-                                                     ffi.stream()), "pa_annot_corpus_counts")
-                values = buffer.cpu().numpy()
-            for i, e in enumerate(chunk):
-                out[e] = (plans[e][0], values[host["out_off"][i]:host["out_off"][i + 1]])
-        return out
 
 
 def write_config(config_yml, result: dict, name: str) -> Path:

@@ -94,8 +94,9 @@ def test_multilabel_equals_the_literal_loop(checkpoint, gpu_device, shared):
 def test_batched_counts_equal_the_single_call(checkpoint, gpu_device):
     import pyannote_audio_amd as pa
     from pyannote_audio_amd import annotation_metrics as am
+    from pyannote_audio_amd import ffi
     from pyannote_audio_amd import frames as frame_ops
-    from pyannote_audio_amd.tuning import DetectionTuner
+    from pyannote_audio_amd.tuning import DetectionTuner, candidate_counts
     pipeline = pa.MultiLabelSegmentation(segmentation=checkpoint).to(gpu_device)
     files = dt.audio_corpus(dt.CLASSES + ["other"], seed=32, durations=(31.0,))
     tuner = DetectionTuner(pipeline).prepare(files)
@@ -110,17 +111,30 @@ def test_batched_counts_equal_the_single_call(checkpoint, gpu_device):
     assert counts[5] == 0 and counts[:5].min() > 0
     entry_jobs = np.array([[0, 1, 2], [3, 4, 5], [6, 1, 5], [3, 1, 2], [0, 4, 5]])
     host_rows = rows.cpu().numpy()
+    everything = list(range(len(entry_jobs)))
+    order = sorted(range(3), key=lambda k: dt.CLASSES[k])
     for collar, skip_overlap in ((0.0, False), (0.25, True)):
-        tuner._counts_device, tuner._variant = gpu_device, (collar, skip_overlap)
-        batched = tuner._counts(item, rows, offsets, counts, entry_jobs, list(range(len(entry_jobs))))
-        for e, picked in enumerate(entry_jobs):
-            labels, values = batched[e]
-            order = sorted(range(3), key=lambda k: dt.CLASSES[k])
+        singles = []
+        for picked in entry_jobs:
             runs = [picked[k] for k in order if counts[picked[k]]]
-            assert labels == [dt.CLASSES[k] for k in order if counts[picked[k]]]
             seg = np.concatenate([host_rows[offsets[j]:offsets[j + 1]] for j in runs])
             lab = np.repeat(np.arange(len(runs), dtype=np.int32), counts[runs])
-            single = am.device_counts(item.ref_seg, item.ref_lab, len(item.ref_labels), seg, lab, len(runs),
-                                      item.uem_seg, collar, skip_overlap, gpu_device).cpu().numpy()
-            assert values.shape == single.shape and values.sum() > 0
-            assert np.array_equal(values.view(np.int64), single.view(np.int64)), (collar, e)
+            singles.append(am.device_counts(item.ref_seg, item.ref_lab, len(item.ref_labels), seg, lab, len(runs),
+                                            item.uem_seg, collar, skip_overlap, gpu_device).cpu().numpy())
+        # the default budget takes the five entries in one call; at 1 byte every entry is a call of its own
+        for budget, calls in ((DetectionTuner.workspace_bytes, 1), (1, len(entry_jobs))):
+            ffi.prof_enable(True)
+            try:
+                ffi.prof_report()
+                batched = candidate_counts(item, rows, offsets, counts, entry_jobs, everything, tuner.classes, collar,
+                                           skip_overlap, gpu_device, budget)
+                torch.cuda.synchronize()
+                report = ffi.prof_report()
+            finally:
+                ffi.prof_enable(False)
+            assert report["k_annot_corpus_counts"]["launches"] == calls
+            for e, picked in enumerate(entry_jobs):
+                labels, values = batched[e]
+                assert labels == [dt.CLASSES[k] for k in order if counts[picked[k]]]
+                assert values.shape == singles[e].shape and values.sum() > 0
+                assert np.array_equal(values.view(np.int64), singles[e].view(np.int64)), (collar, budget, e)

@@ -242,6 +242,31 @@ def test_corpus_counts_on_the_host():
             corpus.counts(0.0, collar=bad)
 
 
+@pytest.mark.parametrize("files", [
+    [],                                                          # F = 0: the alignment slack alone
+    [(0, 0, 0, 0, 0)],                                           # an empty file
+    [(5, 7, 1, 2, 3), (0, 0, 0, 0, 0), (12, 1, 2, 4, 1)],
+    [(3, 0, 1, 2, 0), (0, 9, 1, 0, 64), (1000, 2000, 3, 64, 64), (1, 1, 1, 1, 1)],
+], ids=["no-file", "empty-file", "three-files", "four-files"])
+def test_workspace_formula_is_the_library_s(files):
+    """`evaluation.corpus_workspace_bytes` (callers size their chunks with it before any table exists) against
+    `pa_annot_corpus_workspace_bytes`, which reads F, R and the five host tables only.  Per file: reference,
+    hypothesis, uem rows, reference and hypothesis labels."""
+    import ctypes
+    from pyannote_audio_amd import ffi
+    from pyannote_audio_amd.evaluation import corpus_workspace_bytes, cut_slots
+    struct = ffi.AnnotCorpus()
+    struct.F, struct.R = len(files), sum(f[4] for f in files)
+    columns = np.array(files, dtype=np.int64).reshape(len(files), 5).T
+    tables = [np.concatenate([[0], np.cumsum(column)]).astype(np.int32) for column in columns[:3]] + \
+             [np.ascontiguousarray(column, dtype=np.int32) for column in columns[3:]]
+    for name, table in zip(("ref_off", "hyp_off", "uem_off", "Kr", "Kh"), tables):
+        setattr(struct, "h_" + name, table.ctypes.data)
+    want = int(ffi.load().pa_annot_corpus_workspace_bytes(ctypes.byref(struct)))
+    assert want > 0
+    assert corpus_workspace_bytes(sum(f[1] for f in files), sum(cut_slots(f[0], f[1], f[2]) for f in files)) == want
+
+
 # ----------------------------------------------------------------------------------------------- benchmark
 class StubOutput:
     def __init__(self, speaker_diarization):

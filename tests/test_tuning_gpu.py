@@ -125,7 +125,7 @@ def test_training_cache(pipeline, monkeypatch):
 
 def quantile_thresholds(tuner, levels) -> list:
     """thresholds from the merge heights of the files' own dendrograms, so that the cuts differ by construction"""
-    heights = np.concatenate([tuner._tree(item)[0].Z[:, 2] for item in tuner.prepared])
+    heights = np.concatenate([tuner._tree(item).tree.Z[:, 2] for item in tuner.prepared])
     return [float(t) for t in np.quantile(heights, levels)]
 
 
@@ -140,7 +140,7 @@ def test_sweep_equals_the_literal_loop(pipeline, monkeypatch, forced):
     tuner = ClusteringTuner(pipeline).prepare(files)
     assert pipeline.training is False and calls == {"segmentation": 3, "embedding": 3}
     assert all("training_cache/front_end" in file for file in files)
-    sizes_of_training_sets = [tuner._tree(item)[1].shape[0] for item in tuner.prepared]
+    sizes_of_training_sets = [tuner._tree(item).train.shape[0] for item in tuner.prepared]
     print("training embeddings per file:", sizes_of_training_sets)
     assert min(sizes_of_training_sets) >= 8
     levels = np.linspace(0.15, 0.97, 4 if forced else 9)
@@ -178,7 +178,7 @@ def test_thresholds_between_the_same_heights_share_their_evaluation(pipeline):
     pipeline.instantiate(pipeline.default_parameters())
     files = corpus()
     tuner = ClusteringTuner(pipeline).prepare(files)
-    heights = np.unique(np.concatenate([tuner._tree(item)[0].Z[:, 2] for item in tuner.prepared]))
+    heights = np.unique(np.concatenate([tuner._tree(item).tree.Z[:, 2] for item in tuner.prepared]))
     i = int(np.argmax(np.diff(heights[:-1])))            # the widest gap between two adjacent heights of any file
     low, high = heights[i], heights[i + 1]
     inside = [float(low + (high - low) / 3), float(low + 2 * (high - low) / 3)]

@@ -116,8 +116,8 @@ def test_sweep_vbx_equals_the_literal_loop(pipeline, monkeypatch, capped):
     assert pipeline.training is False and calls == {"segmentation": 3, "embedding": 3}
     plans = [tuner._vbx_front(item) for item in tuner.prepared]
     assert all(plan is not None for plan in plans)
-    print("training embeddings per file:", [plan[0].shape[0] for plan in plans])
-    heights = np.concatenate([plan[2].Z[:, 2] for plan in plans])
+    print("training embeddings per file:", [plan.train.shape[0] for plan in plans])
+    heights = np.concatenate([plan.tree.Z[:, 2] for plan in plans])
     thresholds = [float(t) for t in np.quantile(heights, (0.35, 0.75, 0.95))]
 
     result = tuner.sweep_vbx(thresholds, FAS, FBS)

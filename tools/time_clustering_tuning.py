@@ -153,7 +153,7 @@ def main():
     # (c) first: its dendrograms give the thresholds
     t_prepare, tuner = clock(lambda: ClusteringTuner(pipeline).prepare(files))
     trees = [tuner._tree(item) for item in tuner.prepared]
-    heights = np.concatenate([plan[0].Z[:, 2] for plan in trees])
+    heights = np.concatenate([plan.tree.Z[:, 2] for plan in trees])
     thresholds = [float(t) for t in np.quantile(heights, np.linspace(0.5, 0.9995, args.thresholds))]
     tuner.sweep(thresholds[:2])                                   # warm-up
     sweeps = {"device": [], "host": []}
@@ -187,7 +187,7 @@ def main():
     med_c = statistics.median(sweeps["device"])
     spread_b = (max(seconds_b) - min(seconds_b)) * len(candidates)
     spread_a = (max(seconds_a) - min(seconds_a)) * len(candidates)
-    train = [plan[1].shape[0] for plan in trees]
+    train = [plan.train.shape[0] for plan in trees]
     lines = [
         f"tools/time_clustering_tuning.py --minutes {' '.join(f'{m:g}' for m in args.minutes)} --thresholds "
         f"{args.thresholds} --repeats {args.repeats}",

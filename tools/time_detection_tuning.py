@@ -164,7 +164,7 @@ def hour_sized(device, repeats: int) -> list:
     from multilabel_oracle import smooth_scores
     from pyannote_audio_amd import frames as frame_ops
     from pyannote_audio_amd.core import Annotation, Segment, SlidingWindow, SlidingWindowFeature
-    from pyannote_audio_amd.tuning import DetectionTuner, _Detection
+    from pyannote_audio_amd.tuning import DetectionTuner, _Detection, candidate_counts
     from pyannote_audio_amd import annotation_metrics as am
     from time_annotation_metrics import bench_turns
     T, L, J = 213334, 256, 16
@@ -182,15 +182,13 @@ def hour_sized(device, repeats: int) -> list:
     ref_labels, ref_seg, ref_lab = am._rows(reference)
     item = _Detection(file={"uri": "hour"}, scores=scores, frames=window, ref_labels=ref_labels, ref_seg=ref_seg,
                       ref_lab=ref_lab, uem_seg=am._uem_rows([Segment(0.0, 3600.0)]))
-    tuner = DetectionTuner.__new__(DetectionTuner)
-    tuner.multilabel, tuner.classes = False, ["SPEECH"]
-    tuner._counts_device, tuner._variant = device, (0.0, False)
     entry_jobs = np.arange(L * J, dtype=np.int64)[:, None]
 
     def once():
         rows, _, offsets = frame_ops.binarize_regions_sweep(scores, window, *tables, to_host=False)
-        return rows, offsets, tuner._counts(item, rows, offsets, np.diff(offsets), entry_jobs,
-                                            list(range(len(entry_jobs))))
+        return rows, offsets, candidate_counts(item, rows, offsets, np.diff(offsets), entry_jobs,
+                                               list(range(len(entry_jobs))), ["SPEECH"], 0.0, False, device,
+                                               DetectionTuner.workspace_bytes)
 
     rows, offsets, _ = once()                                     # warm-up
     sweep_ms, counts_ms, calls = [], [], 0

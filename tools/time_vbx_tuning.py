@@ -247,7 +247,7 @@ def main():
 
     t_prepare, tuner = clock(lambda: ClusteringTuner(pipeline).prepare(files))
     plans = [tuner._vbx_front(item) for item in tuner.prepared]
-    heights = np.concatenate([plan[2].Z[:, 2] for plan in plans])
+    heights = np.concatenate([plan.tree.Z[:, 2] for plan in plans])
     thresholds = [float(t) for t in np.quantile(heights, levels)]
     Fas, Fbs = FAS[:args.grid], FBS[:args.grid]
     tuner.sweep_vbx(thresholds[:1], Fas[:1], Fbs[:2])                         # warm-up of both routes
@@ -278,7 +278,7 @@ def main():
     hour_file = corpus([args.hour], device)[0]
     phase_lines, same_parts = phases(pipeline, hour_file, candidates[0], levels, args.repeats)
 
-    train = [plan[0].shape[0] for plan in plans]
+    train = [plan.train.shape[0] for plan in plans]
     lines = [
         f"tools/time_vbx_tuning.py --minutes {' '.join(f'{m:g}' for m in args.minutes)} --hour {args.hour:g} --grid "
         f"{args.grid} --literal {args.literal} --repeats {args.repeats}",
