@@ -913,6 +913,37 @@ int pa_dendrogram_cuts(const double* tl_own, const double* tl_parent, const int3
                        int n, const double* thresholds, long T, int32_t* labels, int32_t* num_clusters, void* ws,
                        size_t ws_bytes, void* stream);
 
+/* ---- KMeans (pipelines/clustering.py:483-547 and 624-645: sklearn.cluster.KMeans, dense, k-means++, lloyd) ---- */
+
+/* the largest K and D pa_kmeans_f64 takes */
+int pa_kmeans_max_clusters(void);
+int pa_kmeans_max_dim(void);
+/* bytes of `workspace` below (0: a size pa_kmeans_f64 refuses) */
+size_t pa_kmeans_workspace_bytes(int N, int D, int K, int n_init);
+/* scikit-learn 1.7.2's KMeans(n_clusters=K, init="k-means++", algorithm="lloyd") with unit sample weights on the
+ * float64 rows X (N, D), for n_init initialisations at once (they are jobs of one set of launches), in float64 with a
+ * fixed order of additions (no floating-point atomics, no dependence on the grid): bit-reproducible from call to call.
+ * The random draws are the caller's, taken in sklearn's order from one RandomState: first (n_init) int32 = the first
+ * centre's row, uniforms (n_init, K - 1, T) float64 with T = 2 + int(log(K)) = the draws of every further centre.
+ * X is centred on its column means; tolv = tol * mean of the column variances.  k-means++ per centre: candidates
+ * min(searchsorted(cumsum(closest), u * pot), N - 1), the one with the smallest potential (the first of equals) wins.
+ * Lloyd: label = first argmin_j |C_j|^2 - 2 x.C_j; centres = member means; the centres are replaced, then: the same
+ * labels as in the iteration before -> strict stop; else sum |C_new - C|^2 <= tolv -> tol stop; after a tol stop or
+ * max_iter iterations the rows are assigned once more.  inertia = sum |x - C_label|^2.
+ * round_iterations > 0: the iterations are enqueued that many at a time, the jobs' done flags are read back after
+ * every round (one stream synchronisation each) and the loop ends once every job has stopped; <= 0: all max_iter
+ * iterations are enqueued without a read-back (the workgroups of a stopped job return at entry).
+ * Outputs, on the device, per initialisation: labels (n_init, N) int32; centers (n_init, K, D) float64 in the
+ * caller's coordinates; inertia (n_init); picks (n_init, K) int32 = the rows k-means++ chose; status (n_init, 4) int32
+ * = iterations, stop kind (0 strict, 1 tol, 2 max_iter), empty-cluster flag, non-finite flag.  A job whose cluster
+ * comes up empty stops there with its flag raised (sklearn would relocate points: the caller falls back); non-finite
+ * input raises the last flag of every job and nothing else is written.  With a flag set, labels, centers and inertia of
+ * that job are not meaningful.  Returns 3, before any launch, for K < 2, K > pa_kmeans_max_clusters(), D outside
+ * 1..pa_kmeans_max_dim(), N < K, N >= 2^24, n_init outside 1..65535, max_iter < 1 or a workspace that is too small. */
+int pa_kmeans_f64(const double* X, int N, int D, int K, int n_init, const int32_t* first, const double* uniforms,
+                  int max_iter, double tol, int round_iterations, int32_t* labels, double* centers, double* inertia,
+                  int32_t* picks, int32_t* status, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

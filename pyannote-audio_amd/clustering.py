@@ -7,9 +7,13 @@ What runs where
                              bit-identical to SciPy incl. ties), cosine cdist of every embedding to the
                              centroids, the PLDA projection and the VB iterations of VBx (one file: `_vbx`; the
                              candidates of a tuning sweep: `vbx_batch`), the constrained assignment of all chunks
-                             for such a sweep (`constrained_argmax_device`)
-  host, SciPy / sklearn      `fcluster` on the (GPU-built) dendrogram, Hungarian assignment, KMeans --
-                             the very library calls the reference makes, O(N) or tiny
+                             for such a sweep (`constrained_argmax_device`), KMeans (`distance.kmeans`,
+                             csrc/kmeans.hip: KMeansClustering and the forced speaker counts of VBx; scikit-learn's
+                             labels for the same values in float64 -- float32 rows of an over-split cloud can differ
+                             from the reference's float32 run in a few boundary points)
+  host, SciPy / sklearn      `fcluster` on the (GPU-built) dendrogram, Hungarian assignment -- the very library
+                             calls the reference makes, O(N) or tiny; KMeans only with `kmeans_on_device = False`,
+                             off the GPU, or when the device route gives up (an empty cluster, sizes beyond its limits)
   host, this file            everything between those calls, organised around array operations instead
                              of the reference's per-cluster / per-iteration Python loops:
                                * `segment_means`: all cluster centroids from one stable sort (contiguous
@@ -289,6 +293,25 @@ class BaseClustering(Pipeline):
         hard = self.constrained_argmax(soft) if constrained else np.argmax(soft, axis=2)
         return hard, soft, centroids
 
+    #: KMeans on the device (`distance.kmeans`) when the object lives on a GPU; False: always scikit-learn's call
+    kmeans_on_device: bool = True
+
+    def kmeans_labels(self, vectors: np.ndarray, num_clusters: int) -> np.ndarray:
+        """`KMeans(n_clusters=num_clusters, n_init=3, random_state=42, copy_x=False).fit_predict(vectors)`
+        (clustering.py:545-547, 635-637).  On a GPU with `kmeans_on_device`: `distance.kmeans`, scikit-learn's labels
+        for the same values in float64; where that route does not apply or gives up (None), and on the host, the
+        scikit-learn call itself.  `timings["kmeans"]`: seconds, `timings["kmeans_route"]`: "device" or "host"."""
+        t0 = time.perf_counter()
+        labels = None
+        if self.kmeans_on_device and getattr(self.device, "type", None) == "cuda":
+            labels = distance.kmeans(vectors, num_clusters, self.device, n_init=3, random_state=42)
+        route = "host" if labels is None else "device"
+        if labels is None:
+            from sklearn.cluster import KMeans
+            labels = KMeans(n_clusters=num_clusters, n_init=3, random_state=42, copy_x=False).fit_predict(vectors)
+        self.timings.update(kmeans=time.perf_counter() - t0, kmeans_route=route)
+        return labels
+
     def _single_cluster(self, embeddings: np.ndarray, train_embeddings: np.ndarray):
         C, S, _ = embeddings.shape
         return (np.zeros((C, S), dtype=np.int8), np.ones((C, S, 1)),
@@ -432,8 +455,9 @@ class AgglomerativeClustering(BaseClustering):
 
 
 class KMeansClustering(BaseClustering):
-    """clustering.py:483-547.  scikit-learn's KMeans on the host -- the reference's own call; not part
-    of the accelerated 3.1 / community-1 paths (it needs an explicit number of speakers)."""
+    """clustering.py:483-547.  KMeans with an explicit number of speakers: on a GPU `distance.kmeans` (csrc/kmeans.hip),
+    scikit-learn's labels for the same values in float64; unplaced, on the host or with `kmeans_on_device = False`
+    scikit-learn's KMeans, the reference's own call (`kmeans_labels`)."""
 
     expects_num_clusters: bool = True
 
@@ -451,8 +475,7 @@ class KMeansClustering(BaseClustering):
         if self.metric == "cosine":
             with np.errstate(divide="ignore", invalid="ignore"):
                 embeddings /= np.linalg.norm(embeddings, axis=-1, keepdims=True)
-        from sklearn.cluster import KMeans
-        return KMeans(n_clusters=num_clusters, n_init=3, random_state=42, copy_x=False).fit_predict(embeddings)
+        return self.kmeans_labels(embeddings, num_clusters)
 
 
 class VBxClustering(BaseClustering):
@@ -616,9 +639,8 @@ class VBxClustering(BaseClustering):
         elif found > max_clusters:
             num_clusters = max_clusters
         if num_clusters and num_clusters != found:
-            from sklearn.cluster import KMeans
             constrained = False
-            km = KMeans(n_clusters=num_clusters, n_init=3, random_state=42, copy_x=False).fit_predict(unit)
+            km = self.kmeans_labels(unit, num_clusters)
             centroids = segment_means(train, km, num_clusters)
         soft = self._similarities(embeddings, centroids)
         if constrained:

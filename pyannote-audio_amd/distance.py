@@ -256,3 +256,93 @@ def cdist(A, B: np.ndarray, metric: str = "cosine", device=None) -> np.ndarray:
     ffi.check(lib.pa_cdist_cosine_f64(ffi.ptr(Ad), A.shape[0], ffi.ptr(Bd), B.shape[0], A.shape[1],
                                       ffi.ptr(out), ffi.ptr(norms), ffi.stream()), "pa_cdist_cosine_f64")
     return out.cpu().numpy()
+
+
+#: Lloyd iterations enqueued between two reads of the done flags (`pa_kmeans_f64`; 0: all `max_iter` at once, no
+#: read-back).  The choice is measured in profiles/kmeans_timing.txt.
+KMEANS_ROUND_ITERATIONS = 8
+
+
+def kmeans_draws(n: int, num_clusters: int, n_init: int, random_state: int):
+    """the random draws of sklearn's k-means++ for `n_init` initialisations, in its order of consumption from one
+    `RandomState(random_state)`: first (n_init) int32 = the first centre's row, uniforms (n_init, K - 1, T) float64 with
+    T = 2 + int(log(K)).  None of them depends on the data."""
+    rs = np.random.RandomState(random_state)
+    T = 2 + int(np.log(num_clusters))
+    first = np.empty(n_init, dtype=np.int32)
+    uniforms = np.empty((n_init, num_clusters - 1, T), dtype=np.float64)
+    weights = np.ones(n) / n
+    for i in range(n_init):
+        first[i] = rs.choice(n, p=weights)
+        for c in range(num_clusters - 1):
+            uniforms[i, c] = rs.uniform(size=T)
+    return first, uniforms
+
+
+def kmeans_select(labels: np.ndarray, inertia: np.ndarray, num_clusters: int) -> int:
+    """the initialisation `KMeans.fit` keeps: the first, replaced by a later one only if its inertia is smaller AND its
+    labelling is not the same partition under a renaming (sklearn's `_is_same_clustering`)"""
+    best = 0
+    for i in range(1, len(labels)):
+        if not inertia[i] < inertia[best]:
+            continue
+        # the same partition <=> the pairs (label here, label there) pair every label with exactly one other
+        pairs = np.unique(labels[i].astype(np.int64) * num_clusters + labels[best])
+        if len(np.unique(pairs // num_clusters)) != len(pairs):
+            best = i
+    return best
+
+
+@ffi.on_device(lambda X, num_clusters, device, **kw: device)
+def kmeans(X: np.ndarray, num_clusters: int, device, n_init: int = 3, random_state: int = 42, max_iter: int = 300,
+           tol: float = 1e-4, details: bool = False):
+    """labels (N) int32 of `sklearn.cluster.KMeans(n_clusters=num_clusters, n_init=n_init, random_state=random_state,
+    max_iter=max_iter, tol=tol).fit_predict` FOR THE SAME VALUES IN FLOAT64, numbering included, computed on the GPU
+    (`pa_kmeans_f64`, csrc/kmeans.hip): the random draws are taken on the host (they do not depend on the data) and
+    uploaded once, all initialisations run as jobs of one set of launches, and the choice among them is made here from
+    ONE download.  float64 throughout with a fixed order of additions: bit-reproducible from call to call.  For float32
+    rows scikit-learn computes in float32; where k-means over-splits a homogeneous cloud that rounding can move a
+    few boundary points (KMeans section).
+    None when the device route does not apply or gave up -- no CUDA device, a size outside the kernel's limits,
+    non-finite rows, a cluster that comes up empty (sklearn then relocates points; not built here): the caller makes
+    the sklearn call.  `details=True`: (labels, dict of the per-initialisation outputs `labels`, `centers`, `inertia`,
+    `picks`, `status` and the winner's index `best`)."""
+    X = np.asarray(X)
+    n, dim = X.shape
+    K, J = int(num_clusters), int(n_init)
+    if getattr(device, "type", None) != "cuda" or not torch.cuda.is_available():
+        return None
+    if K == 1:
+        labels = np.zeros(n, dtype=np.int32)
+        return (labels, None) if details else labels
+    lib = ffi.load()
+    if J < 1 or max_iter < 1 or lib.pa_kmeans_workspace_bytes(n, dim, K, J) == 0 or not np.isfinite(X).all():
+        return None
+    first, uniforms = kmeans_draws(n, K, J, random_state)
+    try:
+        ws = torch.empty(lib.pa_kmeans_workspace_bytes(n, dim, K, J), dtype=torch.uint8, device=device)
+    except torch.cuda.OutOfMemoryError:
+        return None
+    Xd = torch.from_numpy(np.ascontiguousarray(X)).to(device).to(torch.float64)
+    first_d, uniforms_d = torch.from_numpy(first).to(device), torch.from_numpy(uniforms).to(device)
+    # one buffer, one download: centres (J, K, D) and inertia (J) as doubles, then labels (J, n), picks (J, K) and
+    # status (J, 4) as int32
+    doubles, ints = J * K * dim + J, J * n + J * K + J * 4
+    buffer = torch.zeros(doubles + (ints + 1) // 2, dtype=torch.float64, device=device)
+    centers, inertia = buffer[:J * K * dim], buffer[J * K * dim:doubles]
+    tail = buffer[doubles:].view(torch.int32)
+    labels, picks, status = tail[:J * n], tail[J * n:J * n + J * K], tail[J * n + J * K:ints]
+    ffi.check(lib.pa_kmeans_f64(ffi.ptr(Xd), n, dim, K, J, ffi.ptr(first_d), ffi.ptr(uniforms_d), int(max_iter),
+                                float(tol), KMEANS_ROUND_ITERATIONS, ffi.ptr(labels), ffi.ptr(centers),
+                                ffi.ptr(inertia), ffi.ptr(picks), ffi.ptr(status), ffi.ptr(ws), ws.numel(),
+                                ffi.stream()), "pa_kmeans_f64")
+    host = buffer.cpu().numpy()
+    host_ints = host[doubles:].view(np.int32)
+    out = {"centers": host[:J * K * dim].reshape(J, K, dim), "inertia": host[J * K * dim:doubles],
+           "labels": host_ints[:J * n].reshape(J, n), "picks": host_ints[J * n:J * n + J * K].reshape(J, K),
+           "status": host_ints[J * n + J * K:ints].reshape(J, 4)}
+    if out["status"][:, 2:].any():      # an empty cluster or non-finite values: sklearn's call
+        return None
+    out["best"] = kmeans_select(out["labels"], out["inertia"], K)
+    labels = out["labels"][out["best"]].copy()
+    return (labels, out) if details else labels

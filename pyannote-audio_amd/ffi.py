@@ -326,6 +326,11 @@ _OPTIONAL: list[tuple] = [
     ("pa_dendrogram_cuts_workspace_bytes", [C.c_int, C.c_long], C.c_size_t),
     ("pa_dendrogram_cuts", [c_fp, c_fp, c_fp, c_fp, C.c_int, c_fp, C.c_long, c_fp, c_fp, c_fp, C.c_size_t, c_fp],
      C.c_int),
+    ("pa_kmeans_max_clusters", [], C.c_int),
+    ("pa_kmeans_max_dim", [], C.c_int),
+    ("pa_kmeans_workspace_bytes", [C.c_int, C.c_int, C.c_int, C.c_int], C.c_size_t),
+    ("pa_kmeans_f64", [c_fp, C.c_int, C.c_int, C.c_int, C.c_int, c_fp, c_fp, C.c_int, C.c_double, C.c_int, c_fp, c_fp,
+                       c_fp, c_fp, c_fp, c_fp, C.c_size_t, c_fp], C.c_int),
 ]
 
 
