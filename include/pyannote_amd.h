@@ -539,16 +539,13 @@ int pa_centroid_means(const float* X, int D, const int* rows, const int* offsets
  * pa_pdist_f64), OVERWRITTEN when the heap kernel runs;  Z: (n-1, 4) doubles in SciPy's layout [id_a, id_b,
  * height, size].  Two kernels behind one call (csrc/linkage_fast.hip, csrc/linkage.hip): a heap-free merge on a
  * square copy of the matrix over 1 / 8 / 16 workgroups, and -- only when two rows ever tie for the smallest lower
- * bound, i.e. when SciPy's heap order would matter -- the exact replay of SciPy's heap on the condensed matrix.
+ * bound, i.e. when SciPy's heap order would matter -- the exact replay of SciPy's heap on the condensed matrix
+ * by ONE workgroup.  The number of workgroups of the heap-free merge only depends on n (PA_LINKAGE_FAST_WGS
+ * overrides it for experiments).
  * The workspace holds the square copy (8 n^2 bytes; PA_LINKAGE_FAST_MAX_GB caps it, default 96). */
 size_t pa_linkage_workspace_bytes(int n);
 int pa_linkage_centroid_f64(double* D, int n, double* Z, void* workspace, size_t workspace_bytes,
                             void* stream);
-/* The same with the placement hint of earlier rounds (`alone`: nothing else competes for the GPU); since round 4
- * the hint is ignored -- the number of workgroups only depends on n (PA_LINKAGE_FAST_WGS / PA_LINKAGE_WGS
- * override it for experiments).  Results are identical either way. */
-int pa_linkage_centroid_f64_ex(double* D, int n, double* Z, void* workspace, size_t workspace_bytes, int alone,
-                               void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Single, complete, average, weighted and Ward linkage (csrc/linkage_chain.hip), bit-identical to

@@ -85,7 +85,7 @@ ProfScope::~ProfScope() {
 extern "C" {
 
 
-int pa_version(void) { return 101; }
+int pa_version(void) { return 102; }
 const char* pa_last_error(void) { return pa::g_err; }
 
 void pa_prof_enable(int on) {

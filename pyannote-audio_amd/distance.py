@@ -8,9 +8,7 @@ reproduce that summation order with explicit `__dmul_rn/__dadd_rn` (see csrc/clu
 problems stay in SciPy: the launch + copy overhead exceeds the work."""
 from __future__ import annotations
 
-import contextlib
 import os
-import threading
 import time
 
 import numpy as np
@@ -71,21 +69,6 @@ def centroid_means(X: torch.Tensor, rows: np.ndarray, labels: np.ndarray, num_se
     return out.cpu().numpy()
 
 
-_hint = threading.local()
-
-
-@contextlib.contextmanager
-def device_to_ourselves():
-    """Inside this block the calling thread promises that nothing else keeps the GPU busy (one file applied on its
-    own, the last file of a batch): `linkage_centroid` may then spread the merge over several workgroups."""
-    previous = getattr(_hint, "alone", False)
-    _hint.alone = True
-    try:
-        yield
-    finally:
-        _hint.alone = previous
-
-
 @ffi.on_device(lambda X, device: device)
 def linkage_centroid(X: np.ndarray, device) -> np.ndarray:
     """scipy.cluster.hierarchy.linkage(X, method="centroid", metric="euclidean") entirely on the GPU:
@@ -119,8 +102,7 @@ def linkage_centroid(X: np.ndarray, device) -> np.ndarray:
     ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)] if os.environ.get("PA_LINKAGE_EVENTS") == "1" else None
     if ev:
         ev[0].record()
-    ffi.check(lib.pa_linkage_centroid_f64_ex(ffi.ptr(cond), n, ffi.ptr(Z), ffi.ptr(ws), ws.numel(),
-                                             1 if getattr(_hint, "alone", False) else 0, ffi.stream()),
+    ffi.check(lib.pa_linkage_centroid_f64(ffi.ptr(cond), n, ffi.ptr(Z), ffi.ptr(ws), ws.numel(), ffi.stream()),
               "pa_linkage_centroid_f64")
     if ev:
         ev[1].record()

@@ -232,7 +232,6 @@ _OPTIONAL: list[tuple] = [
     ("pa_centroid_means", [c_fp, C.c_int, c_fp, c_fp, C.c_int, c_fp, c_fp], C.c_int),
     ("pa_linkage_workspace_bytes", [C.c_int], C.c_size_t),
     ("pa_linkage_centroid_f64", [c_fp, C.c_int, c_fp, c_fp, C.c_size_t, c_fp], C.c_int),
-    ("pa_linkage_centroid_f64_ex", [c_fp, C.c_int, c_fp, c_fp, C.c_size_t, C.c_int, c_fp], C.c_int),
     ("pa_pdist_cosine_f64", [c_fp, C.c_int, C.c_int, c_fp, c_fp, c_fp], C.c_int),
     ("pa_nonfinite_flag_f64", [c_fp, C.c_long, c_fp, c_fp], C.c_int),
     ("pa_linkage_chain_workspace_bytes", [C.c_int], C.c_size_t),

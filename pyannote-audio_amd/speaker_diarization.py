@@ -18,7 +18,6 @@ persistent workgroup on one CU: 15 % of a sequential step with 255 CUs idle).  `
 (parallel.set_shard) splits the chunk range of ONE file across GPUs instead."""
 from __future__ import annotations
 
-import contextlib
 import math
 import os
 import textwrap
@@ -30,7 +29,6 @@ from typing import Any, Callable, Iterable, Iterator, List, Mapping, MutableMapp
 import numpy as np
 import torch
 
-from . import distance
 from . import ffi
 from . import frames as frame_ops
 from . import parallel
@@ -649,8 +647,7 @@ class SpeakerDiarization(Pipeline):
         front = self._cached_front_end(file, hook) if self.training else self._front_end(file, hook)
         if front.silent:
             return self._empty_output(file)
-        with distance.device_to_ourselves():      # one file on its own: no front end runs beside its clustering
-            hard, centroids = self._cluster_one(front, num_speakers, min_speakers, max_speakers)
+        hard, centroids = self._cluster_one(front, num_speakers, min_speakers, max_speakers)
         return self._back_end(front, hard, centroids, min_speakers, max_speakers, hook)
 
     def apply_batch(self, files: Iterable[AudioFile], num_speakers: Optional[int] = None,
@@ -738,9 +735,7 @@ class SpeakerDiarization(Pipeline):
             if front.silent:
                 out = self._empty_output(front.file)
             else:
-                # `alone`: the last file's merge has the GPU to itself (distance.device_to_ourselves)
-                hint = distance.device_to_ourselves() if alone else contextlib.nullcontext()
-                with torch.cuda.device(device), torch.cuda.stream(side), hint:
+                with torch.cuda.device(device), torch.cuda.stream(side):
                     hard, centroids = self._cluster_one(front, num_speakers, min_speakers, max_speakers)
                     out = self._back_end(front, hard, centroids, min_speakers, max_speakers, file_hook)
                     side.synchronize()

@@ -32,7 +32,6 @@ import numpy as np
 import torch
 
 from . import annotation_metrics as am
-from . import distance
 from .clustering import AgglomerativeClustering, Dendrogram, VBxClustering
 from .evaluation import CorpusCall, corpus_workspace_bytes, cut_slots, get_diarization
 
@@ -200,8 +199,7 @@ class ClusteringTuner:
             if bounds[2] < 2 or train.shape[0] < 2:
                 item.trees[method] = None       # one cluster whatever the candidate says: the pipeline's own path
             else:
-                with distance.device_to_ourselves():
-                    tree = Dendrogram(clustering.dendrogram(train))
+                tree = Dendrogram(clustering.dendrogram(train))
                 item.trees[method] = _Tree(tree, train, chunk_idx, speaker_idx, bounds)
         return item.trees[method]
 
@@ -216,8 +214,7 @@ class ClusteringTuner:
                 warnings.warn(f"ClusteringTuner: a PLDA of {clustering.plda.lda_dimension} dimensions is not batched; every "
                               "VBx candidate goes through the pipeline's own call")
             elif front is not None and not front.silent and clustering.plda is not None:
-                with distance.device_to_ourselves():
-                    before = clustering.before_cut(front.embeddings, front.segmentations, num_clean_frames=front.clean)
+                before = clustering.before_cut(front.embeddings, front.segmentations, num_clean_frames=front.clean)
                 if before is not None:
                     train, unit, Z, fea = before
                     item.vbx["front"] = _VBxFront(train, unit, Dendrogram(Z), fea)

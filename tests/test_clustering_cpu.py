@@ -135,29 +135,3 @@ def test_unplaced_clustering_object_is_the_reference_stand_alone_use():
     b = on_host(embeddings=emb.copy(), segmentations=seg, min_clusters=1, max_clusters=np.inf)
     for u, v in zip(a, b):
         assert np.array_equal(u, v, equal_nan=True)
-
-
-def test_merge_placement_hint_is_thread_local_and_nests():
-    """`distance.device_to_ourselves()` (one file on its own / last file of a batch -> the dendrogram merge may use
-    several workgroups) only marks the calling thread and restores the previous state on exit."""
-    import threading
-    from pyannote_audio_amd import distance
-
-    def alone():
-        return getattr(distance._hint, "alone", False)
-
-    assert not alone()
-    seen = {}
-    with distance.device_to_ourselves():
-        assert alone()
-        t = threading.Thread(target=lambda: seen.setdefault("other", alone()))
-        t.start()
-        t.join()
-        with distance.device_to_ourselves():
-            assert alone()
-        assert alone()
-        with pytest.raises(RuntimeError):
-            with distance.device_to_ourselves():
-                raise RuntimeError("boom")
-        assert alone()
-    assert not alone() and seen == {"other": False}

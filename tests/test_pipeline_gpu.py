@@ -162,19 +162,18 @@ def test_linkage_centroid_bit_exact_vs_scipy(gpu_device, n, d, dup, seed):
     assert len(bad) == 0, f"first differing merge {bad[0]}: {got[bad[0]]} vs {want[bad[0]]}"
 
 
-@pytest.mark.parametrize("n,workgroups", [(12300, None), (3000, 4), (12300, 1), (13100, 2)])
-def test_linkage_multi_workgroup_vs_scipy(gpu_device, n, workgroups, monkeypatch):
+@pytest.mark.parametrize("n", [3000, 11054, 11055, 12300, 13100])
+def test_linkage_heap_kernel_on_exact_ties_vs_scipy(gpu_device, n):
     """the heap kernel of csrc/linkage.hip on data WITH exact ties (duplicated rows: the heap-free merge gives up at
-    its first pop and the gated heap kernel recomputes the dendrogram): the default at N = 12 300 (one workgroup,
-    heap in global memory), a forced 4-workgroup run (the multi-workgroup form, opt-in through PA_LINKAGE_WGS) on a
-    small problem, a forced single workgroup, and two workgroups at N = 13 100 (the first round size whose
-    12 (N - 1) heap bytes exceed the LDS budget: multi-workgroup form with the heap in global memory) --
-    bit-identical to SciPy."""
+    its first pop and the gated heap kernel recomputes the dendrogram), bit-identical to SciPy: N = 3 000 (heap and
+    neighbour candidates in LDS, 16-bit keys), N = 12 300 and 13 100 (heap in global memory, int keys) and the two
+    sizes on either side of the switch between the two instantiations.  The launcher keeps the heap in LDS while
+    round16(14 (N - 1)) + 4 ceil(N / 32) + 16 <= LK_LDS_MAX = 160 * 1024 - 7680 = 156 160 bytes (`lds16` in
+    pa_linkage_centroid_f64): N = 11 054 needs 154 752 + 1 400 = 156 152, N = 11 055 needs 154 768 + 1 400 =
+    156 168."""
     from scipy.cluster.hierarchy import linkage
     from scipy.spatial.distance import pdist
     from pyannote_audio_amd import distance
-    if workgroups is not None:
-        monkeypatch.setenv("PA_LINKAGE_WGS", str(workgroups))
     rng = np.random.default_rng(n)
     centers = rng.standard_normal((4, 32))
     X = (centers[rng.integers(0, 4, n)] + 0.5 * rng.standard_normal((n, 32))).astype(np.float32)
@@ -189,14 +188,13 @@ def test_linkage_multi_workgroup_vs_scipy(gpu_device, n, workgroups, monkeypatch
 
 
 @pytest.mark.parametrize("n", [2, 3, 65])
-def test_linkage_multi_workgroup_small_sizes(gpu_device, n, monkeypatch):
-    """the multi-workgroup form of the heap kernel (3 workgroups) at sizes where a workgroup's slice of the z pass is
-    empty or shorter than a wave.  Every row appears three times, so from N = 3 on the two smallest lower bounds tie
-    at the first pop (both 0) and the heap-free merge hands over; N = 2 is below its smallest size."""
+def test_linkage_heap_kernel_small_sizes(gpu_device, n):
+    """the heap kernel at sizes where most waves of its workgroup have no row of the z pass, or only part of a wave
+    has one.  Every row appears three times, so from N = 3 on the two smallest lower bounds tie at the first pop
+    (both 0) and the heap-free merge hands over; N = 2 is below its smallest size."""
     from scipy.cluster.hierarchy import linkage
     from scipy.spatial.distance import pdist
     from pyannote_audio_amd import distance
-    monkeypatch.setenv("PA_LINKAGE_WGS", "3")
     rng = np.random.default_rng(n)
     X = rng.standard_normal(((n + 2) // 3, 32)).astype(np.float32)
     X /= np.linalg.norm(X, axis=1, keepdims=True)
@@ -211,20 +209,16 @@ def test_linkage_multi_workgroup_small_sizes(gpu_device, n, monkeypatch):
         assert st[8] == 1, "expected: heap-free merge gave up on a tie"
 
 
-@pytest.mark.parametrize("workgroups", [None, 3])
-def test_linkage_heap_pending_overflow(gpu_device, workgroups, monkeypatch):
+def test_linkage_heap_pending_overflow(gpu_device, monkeypatch):
     """the heap kernel (heap-free merge switched off) when one merge lowers more lower bounds than its pending list
     holds (LK_PEND = 256): 600 random unit vectors plus the pair +u/2, -u/2 in the last two rows.  That pair is the
     closest (distance 1.0 against 1.035 for the runner-up) and its centroid, the origin, is nearer to every other
     row than that row's neighbour was, so the first merge refreshes all 600 rows at once and the replay reads the
-    candidate bitmap instead of the list -- in the single- and in the multi-workgroup form, bit-identical to SciPy
-    (whose dendrogram has no tied heights here)."""
+    candidate bitmap instead of the list -- bit-identical to SciPy (whose dendrogram has no tied heights here)."""
     from scipy.cluster.hierarchy import linkage
     from scipy.spatial.distance import pdist
     from pyannote_audio_amd import distance
     monkeypatch.setenv("PA_LINKAGE_FAST", "0")
-    if workgroups is not None:
-        monkeypatch.setenv("PA_LINKAGE_WGS", str(workgroups))
     rng = np.random.default_rng(11)
     X = rng.standard_normal((600, 256))
     X /= np.linalg.norm(X, axis=1, keepdims=True)

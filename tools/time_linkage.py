@@ -1,6 +1,9 @@
-"""Times the dendrogram merge kernel (csrc/linkage.hip) for 1 .. 16 workgroups and checks every variant against
-SciPy (small n) or against the single-workgroup kernel (large n).
+"""Times the dendrogram merge (csrc/linkage_fast.hip + csrc/linkage.hip): the default, the heap-free merge forced to
+8 and 16 workgroups, and the heap kernel alone; checks every leg against SciPy (small n) or against the first leg
+(large n).
 usage (GPU box): python tools/time_linkage.py [n ...]     (default 7000 20000 57000)
+LK_LEGS (default "0,-8,-16,heap") picks the legs: 0 = the default (heap-free merge first, its own choice of
+workgroups), -G = the heap-free merge forced to G workgroups, heap = PA_LINKAGE_FAST=0, the heap kernel alone.
 If gpurun_out/bench_train_emb.npy exists (PA_BENCH_DUMP_EMB=1 python bench.py ...) it is timed first."""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -14,14 +17,19 @@ rng = np.random.default_rng(0)
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def run(X, G):
-    os.environ["PA_LINKAGE_WGS"] = str(G)
+def run(X, env):
+    for name in ("PA_LINKAGE_FAST", "PA_LINKAGE_FAST_WGS"):
+        os.environ.pop(name, None)
+    os.environ.update(env)
     distance.linkage_centroid(X[:64].copy(), dev)
     torch.cuda.synchronize()
     t = time.perf_counter()
     Z = distance.linkage_centroid(X.copy(), dev)
     dt = time.perf_counter() - t
-    return Z, dt, describe(len(X))
+    info = describe(len(X))
+    for name in env:
+        os.environ.pop(name, None)
+    return Z, dt, info
 
 
 def describe(n):
@@ -29,7 +37,7 @@ def describe(n):
     fast = (f"heap-free merge: status {st[8]} workgroups {st[13]} repairs/merge {st[9] / n:.2f} re-publishes/merge "
             f"{st[14] / n:.2f} cycles(pop, pass)/merge {[int(c / n) for c in st[10:12]]}") if st[12] else "heap-free merge: off"
     heap = (f"heap kernel: retries/merge {st[0] / n:.2f} heap-updates/merge {st[1] / n:.2f} overflows {st[2]} "
-            f"cycles(find, wait, pass, replay)/merge {[int(c / n) for c in st[3:7]]}") if st[7] else "heap kernel: skipped"
+            f"cycles(find, record, pass, replay)/merge {[int(c / n) for c in st[3:7]]}") if st[7] else "heap kernel: skipped"
     return fast + " | " + heap
 
 
@@ -39,29 +47,17 @@ def sweep(name, X, scipy_check):
         t = time.perf_counter()
         ref = linkage(pdist(X), "centroid")
         print(f"{name}: scipy pdist + linkage {1e3 * (time.perf_counter() - t):.0f} ms", flush=True)
-    for G in [int(g) for g in os.environ.get("LK_GS", "0,-8,-16,1").split(",")]:
-        # G = 0: the default (heap-free merge first, its own choice of workgroups); G < 0: the heap-free merge forced
-        # to -G workgroups; G >= 1: PA_LINKAGE_FAST=0, the heap kernel with G workgroups
-        if G <= 0:
-            os.environ.pop("PA_LINKAGE_FAST", None)
-            os.environ.pop("PA_LINKAGE_WGS", None)
-            os.environ.pop("PA_LINKAGE_FAST_WGS", None)
-            if G < 0:
-                os.environ["PA_LINKAGE_FAST_WGS"] = str(-G)
-            distance.linkage_centroid(X[:64].copy(), dev)
-            torch.cuda.synchronize()
-            t = time.perf_counter()
-            Z = distance.linkage_centroid(X.copy(), dev)
-            dt = time.perf_counter() - t
-            info = describe(len(X))
-            os.environ.pop("PA_LINKAGE_FAST_WGS", None)
+    for leg in os.environ.get("LK_LEGS", "0,-8,-16,heap").split(","):
+        if leg == "heap":
+            env, label = {"PA_LINKAGE_FAST": "0"}, "heap kernel"
+        elif int(leg) == 0:
+            env, label = {}, "default"
         else:
-            os.environ["PA_LINKAGE_FAST"] = "0"
-            Z, dt, info = run(X, G)
-            os.environ.pop("PA_LINKAGE_FAST", None)
+            env, label = {"PA_LINKAGE_FAST_WGS": str(-int(leg))}, f"heap-free x{-int(leg)}"
+        Z, dt, info = run(X, env)
         if ref is None:
             ref = Z
-        print(f"{name}: n={len(X)} workgroups={G:2d} {1e3 * dt:8.1f} ms  identical={np.array_equal(Z, ref)}  {info}",
+        print(f"{name}: n={len(X)} {label:14s} {1e3 * dt:8.1f} ms  identical={np.array_equal(Z, ref)}  {info}",
               flush=True)
 
 
@@ -78,4 +74,3 @@ for n in [int(a) for a in sys.argv[1:]] or [7000, 20000, 57000]:
     if n >= 20000 and os.environ.get("LK_NODUP") != "1":           # exact ties (duplicated rows): the heap-free merge gives up at its first pop
         X[n // 2: n // 2 + 500] = X[:500]
         sweep("synthetic + 500 duplicated rows", X, False)
-os.environ.pop("PA_LINKAGE_WGS", None)
