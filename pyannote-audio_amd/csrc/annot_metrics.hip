@@ -223,8 +223,29 @@ static bool annot_cut_count(int Nr, int Nh, int Nu, bool collar, long* M) {
   return *M <= ANN_MAX_CUTS;
 }
 
-// workspace: [cuts M f64][sorted M f64][rec_r M u64][rec_h M u64][rec_d M f64][rank M i32]
-static size_t annot_workspace(long M) { return 256 + (size_t)M * (5 * 8 + 4); }
+// The workspace of both entry points: 256 bytes of slack (the caller's pointer need not be aligned), then the arrays
+// back to back.  NhT hypothesis rows of all files of a corpus (0 for pa_annot_counts), M cut slots.
+constexpr size_t ANN_SLACK = 256;
+struct AnnotBufs {
+  double *tmp_seg, *m_seg;             // (NhT, 2) each: the merged hypothesis rows of stage A
+  double *cuts, *sorted, *rec_d;       // (M) each, like the next three
+  unsigned long long *rec_r, *rec_h;
+  int* rank;
+  int32_t* m_lab;                      // (NhT)
+};
+static AnnotBufs annot_layout(Carver& c, long NhT, long M) {
+  AnnotBufs b;
+  b.tmp_seg = c.take<double>(2 * NhT, 8);
+  b.m_seg = c.take<double>(2 * NhT, 8);
+  b.cuts = c.take<double>(M, 8);
+  b.sorted = c.take<double>(M, 8);
+  b.rec_r = c.take<unsigned long long>(M, 8);
+  b.rec_h = c.take<unsigned long long>(M, 8);
+  b.rec_d = c.take<double>(M, 8);
+  b.rank = c.take<int>(M, 4);
+  b.m_lab = c.take<int32_t>(NhT, 4);
+  return b;
+}
 
 // ------------------------------------------------------------------------------------------------ a corpus
 // F files in one call (pa_annot_corpus_counts).  Stage A fills the within-label gaps of every file's hypothesis
@@ -389,12 +410,6 @@ static bool annot_corpus_plan(const pa_annot_corpus* c, bool collar, CorpusPlan*
   return true;
 }
 
-// workspace: [tmp_seg 2 NhT f64][m_seg 2 NhT f64][cuts Mt f64][sorted Mt f64][rec_r Mt u64][rec_h Mt u64]
-//            [rec_d Mt f64][rank Mt i32][m_lab NhT i32]
-static size_t annot_corpus_workspace(const CorpusPlan& p) {
-  return 256 + (size_t)p.NhT * (4 * 8 + 4) + (size_t)p.Mt * (5 * 8 + 4);
-}
-
 }  // namespace pa
 
 extern "C" {
@@ -402,7 +417,7 @@ extern "C" {
 size_t pa_annot_counts_workspace_bytes(int Nr, int Nh, int Nu) {
   long M;
   if (!pa::annot_cut_count(Nr, Nh, Nu, true, &M)) return 0;
-  return pa::annot_workspace(M);
+  return pa::carved_bytes([&](pa::Carver& c) { pa::annot_layout(c, 0, M); }, pa::ANN_SLACK);
 }
 
 int pa_annot_counts(const double* ref_seg, const int32_t* ref_label, int Nr, int Kr, const double* hyp_seg,
@@ -419,31 +434,27 @@ int pa_annot_counts(const double* ref_seg, const int32_t* ref_label, int Nr, int
   PA_REQUIRE(out && (Nr == 0 || (ref_seg && ref_label)) && (Nh == 0 || (hyp_seg && hyp_label)) &&
                  (Nu == 0 || uem_seg),
              "pa_annot_counts: null array");
-  PA_REQUIRE(ws && ws_bytes >= pa::annot_workspace(M), "pa_annot_counts: workspace of %zu bytes, %zu needed",
-             ws_bytes, pa::annot_workspace(M));
+  pa::Carver carver(ws, pa::ANN_SLACK);
+  const pa::AnnotBufs a = pa::annot_layout(carver, 0, M);
+  PA_REQUIRE(ws && ws_bytes >= carver.bytes(), "pa_annot_counts: workspace of %zu bytes, %zu needed", ws_bytes,
+             carver.bytes());
   hipStream_t s = (hipStream_t)stream;
   const pa::AnnotShape sh{Nr, Nh, Nu, with_collar ? 1 : 0};
   const int m = (int)M, nint = m > 0 ? m - 1 : 0;
   const int nout = Kr * Kh + Kr + Kh + pa::ANN_SCALARS;
-  char* base = (char*)(((uintptr_t)ws + 255) & ~(uintptr_t)255);
-  double* cuts = (double*)base;
-  double* sorted = cuts + m;
-  unsigned long long* rec_r = (unsigned long long*)(sorted + m);
-  unsigned long long* rec_h = rec_r + m;
-  double* rec_d = (double*)(rec_h + m);
-  int* rank = (int*)(rec_d + m);
   pa::ProfScope prof("k_annot_counts", stream, 0.0, 44.0 * m + 8.0 * nout);
   if (nint > 0) {
     const int grid = pa::cdiv(m, pa::ANN_THREADS);
     hipLaunchKernelGGL(pa::k_annot_cuts, dim3(grid), dim3(pa::ANN_THREADS), 0, s, ref_seg, hyp_seg, uem_seg, sh,
-                       0.5 * collar, cuts);
-    hipLaunchKernelGGL(pa::k_annot_rank, dim3(grid), dim3(pa::ANN_THREADS), 0, s, cuts, m, sorted, rank);
+                       0.5 * collar, a.cuts);
+    hipLaunchKernelGGL(pa::k_annot_rank, dim3(grid), dim3(pa::ANN_THREADS), 0, s, a.cuts, m, a.sorted, a.rank);
     hipLaunchKernelGGL(pa::k_annot_intervals, dim3(pa::cdiv(nint, pa::ANN_THREADS)), dim3(pa::ANN_THREADS), 0, s,
-                       sorted, rank, ref_label, hyp_label, sh, Kr, Kh, skip_overlap ? 1 : 0, rec_r, rec_h, rec_d);
+                       a.sorted, a.rank, ref_label, hyp_label, sh, Kr, Kh, skip_overlap ? 1 : 0, a.rec_r, a.rec_h,
+                       a.rec_d);
   }
   // (without intervals the sums are empty: the kernel writes the zeros)
-  hipLaunchKernelGGL(pa::k_annot_reduce, dim3(nout), dim3(pa::ANN_THREADS), 0, s, rec_r, rec_h, rec_d, nint, Kr, Kh,
-                     out);
+  hipLaunchKernelGGL(pa::k_annot_reduce, dim3(nout), dim3(pa::ANN_THREADS), 0, s, a.rec_r, a.rec_h, a.rec_d, nint, Kr,
+                     Kh, out);
   PA_CHECK_LAUNCH("pa_annot_counts");
   return 0;
 }
@@ -451,7 +462,7 @@ int pa_annot_counts(const double* ref_seg, const int32_t* ref_label, int Nr, int
 size_t pa_annot_corpus_workspace_bytes(const pa_annot_corpus* corpus) {
   pa::CorpusPlan p;
   if (!pa::annot_corpus_plan(corpus, true, &p)) return 0;
-  return pa::annot_corpus_workspace(p);
+  return pa::carved_bytes([&](pa::Carver& c) { pa::annot_layout(c, p.NhT, p.Mt); }, pa::ANN_SLACK);
 }
 
 int pa_annot_corpus_counts(const pa_annot_corpus* corpus, double fill, double collar, int skip_overlap, double* out,
@@ -471,32 +482,27 @@ int pa_annot_corpus_counts(const pa_annot_corpus* corpus, double fill, double co
                  (c.h_ref_off[c.F] == 0 || (c.ref_seg && c.ref_label)) &&
                  (p.NhT == 0 || (c.hyp_seg && c.run_rows)) && (c.h_uem_off[c.F] == 0 || c.uem_seg),
              "pa_annot_corpus_counts: null array");
-  PA_REQUIRE(ws && ws_bytes >= pa::annot_corpus_workspace(p),
-             "pa_annot_corpus_counts: workspace of %zu bytes, %zu needed", ws_bytes, pa::annot_corpus_workspace(p));
+  pa::Carver carver(ws, pa::ANN_SLACK);
+  const pa::AnnotBufs a = pa::annot_layout(carver, p.NhT, p.Mt);
+  PA_REQUIRE(ws && ws_bytes >= carver.bytes(), "pa_annot_corpus_counts: workspace of %zu bytes, %zu needed", ws_bytes,
+             carver.bytes());
   hipStream_t s = (hipStream_t)stream;
-  char* base = (char*)(((uintptr_t)ws + 255) & ~(uintptr_t)255);
-  double* tmp_seg = (double*)base;
-  double* m_seg = tmp_seg + 2 * p.NhT;
-  double* cuts = m_seg + 2 * p.NhT;
-  double* sorted = cuts + p.Mt;
-  unsigned long long* rec_r = (unsigned long long*)(sorted + p.Mt);
-  unsigned long long* rec_h = rec_r + p.Mt;
-  double* rec_d = (double*)(rec_h + p.Mt);
-  int* rank = (int*)(rec_d + p.Mt);
-  int32_t* m_lab = rank + p.Mt;
   const int col = with_collar ? 1 : 0;
   pa::ProfScope prof("k_annot_corpus_counts", stream, 0.0, 44.0 * p.Mt + 68.0 * p.NhT);
   const dim3 block(pa::ANN_THREADS);
-  hipLaunchKernelGGL(pa::k_annot_support, dim3(c.F), block, 0, s, c, fill, tmp_seg, m_seg, m_lab, merged_rows);
+  hipLaunchKernelGGL(pa::k_annot_support, dim3(c.F), block, 0, s, c, fill, a.tmp_seg, a.m_seg, a.m_lab,
+                     merged_rows);
   if (p.max_cuts > 1) {
     const dim3 grid(pa::cdiv(p.max_cuts, pa::ANN_THREADS), c.F);
-    hipLaunchKernelGGL(pa::k_annot_corpus_cuts, grid, block, 0, s, c, merged_rows, m_seg, col, 0.5 * collar, cuts);
-    hipLaunchKernelGGL(pa::k_annot_corpus_rank, grid, block, 0, s, c, merged_rows, col, cuts, sorted, rank);
+    hipLaunchKernelGGL(pa::k_annot_corpus_cuts, grid, block, 0, s, c, merged_rows, a.m_seg, col, 0.5 * collar,
+                       a.cuts);
+    hipLaunchKernelGGL(pa::k_annot_corpus_rank, grid, block, 0, s, c, merged_rows, col, a.cuts, a.sorted, a.rank);
     hipLaunchKernelGGL(pa::k_annot_corpus_intervals, dim3(pa::cdiv(p.max_cuts - 1, pa::ANN_THREADS), c.F), block, 0,
-                       s, c, merged_rows, m_lab, col, skip_overlap ? 1 : 0, sorted, rank, rec_r, rec_h, rec_d);
+                       s, c, merged_rows, a.m_lab, col, skip_overlap ? 1 : 0, a.sorted, a.rank, a.rec_r, a.rec_h,
+                       a.rec_d);
   }
-  hipLaunchKernelGGL(pa::k_annot_corpus_reduce, dim3(p.max_out, c.F), block, 0, s, c, merged_rows, col, rec_r, rec_h,
-                     rec_d, out);
+  hipLaunchKernelGGL(pa::k_annot_corpus_reduce, dim3(p.max_out, c.F), block, 0, s, c, merged_rows, col, a.rec_r,
+                     a.rec_h, a.rec_d, out);
   PA_CHECK_LAUNCH("pa_annot_corpus_counts");
   return 0;
 }

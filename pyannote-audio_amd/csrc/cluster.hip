@@ -8,6 +8,8 @@
 // plain operators under `#pragma clang fp contract(off)` (HIP's __dmul_rn/__dadd_rn are ordinary
 // operators defined in a header, which the default -ffp-contract=fast still fuses).  HBM-bound on the condensed
 // output for large N (8 B per pair); the arithmetic (3 flop per pair and k) is far from the fp64 peak.
+#include <stdlib.h>
+
 #include "common.h"
 #include "cosine_f64.h"   // dot2way, row norms and the clipped quotient, shared with verification.hip
 
@@ -72,10 +74,45 @@ __global__ __launch_bounds__(256) void k_pdist_f64(const double* __restrict__ X,
     }
 }
 
+// one thread per row (the block size does not touch the values)
 __global__ void k_row_norms_f64(const double* __restrict__ X, int N, int D, double* __restrict__ nrm) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= N) return;
   nrm[i] = row_norm_f64(X + (long)i * D, D);
+}
+
+// condensed (SciPy pdist order) -> square symmetric, leading dimension ld (multiple of 8 doubles); 64 x 64 tiles,
+// the mirror tile transposed through LDS so that both are written in whole lines.  grid = (nt, nt), bj >= bi works.
+__global__ __launch_bounds__(256) void k_square_from_condensed(const double* __restrict__ cond, int n, long ld,
+                                                                double* __restrict__ S) {
+  const int bi = blockIdx.y, bj = blockIdx.x;
+  if (bj < bi) return;
+  __shared__ double tile[64][65];
+  const int tid = threadIdx.x;
+  for (int e = tid; e < 4096; e += 256) {
+    const int r = e >> 6, c = e & 63;
+    const long i = bi * 64 + r, j = bj * 64 + c;
+    double v = 0.0;
+    if (i < n && j < n && i != j) {
+      const long a = i < j ? i : j, b = i < j ? j : i;
+      v = cond[(long)n * a - (a * (a + 1) / 2) + (b - a - 1)];
+    }
+    tile[r][c] = v;
+    if (i < n && j < n) S[i * ld + j] = v;
+  }
+  if (bi == bj) return;
+  __syncthreads();
+  for (int e = tid; e < 4096; e += 256) {
+    const int r = e >> 6, c = e & 63;
+    const long j = bj * 64 + r, i = bi * 64 + c;
+    if (i < n && j < n) S[j * ld + i] = tile[c][r];
+  }
+}
+
+bool square_fits(int n) {
+  const char* g = getenv("PA_LINKAGE_FAST_MAX_GB");
+  const double cap = (g != nullptr && atof(g) > 0 ? atof(g) : 96.0) * 1e9;
+  return 8.0 * (double)n * (double)square_ld(n) <= cap && n <= 150000;
 }
 
 // out[i][j] = 1 - clip(<a_i, b_j> / (|a_i| |b_j|));  grid = NA, block = 128 (threads stride over j)
@@ -127,6 +164,15 @@ __global__ __launch_bounds__(256) void k_centroid_means(const float* __restrict_
 
 }  // namespace pa
 
+void pa_square_from_condensed(const double* cond, int n, long ld, double* S, void* stream) {
+  const int nt = pa::cdiv(n, 64);
+  hipLaunchKernelGGL(pa::k_square_from_condensed, dim3(nt, nt), dim3(256), 0, (hipStream_t)stream, cond, n, ld, S);
+}
+
+void pa_row_norms_f64(const double* X, int N, int D, double* nrm, void* stream) {
+  hipLaunchKernelGGL(pa::k_row_norms_f64, dim3(pa::cdiv(N, 128)), dim3(128), 0, (hipStream_t)stream, X, N, D, nrm);
+}
+
 extern "C" {
 
 // means of the rows of X (float32, row-major, D columns) selected by rows[offsets[k] .. offsets[k+1]) for every
@@ -156,9 +202,8 @@ int pa_cdist_cosine_f64(const double* A, int NA, const double* B, int NB, int D,
   if (NA <= 0 || NB <= 0) return 0;
   hipStream_t st = (hipStream_t)stream;
   pa::ProfScope prof("k_cdist_cosine_f64", stream, 2.0 * D * (double)NA * NB, 8.0 * ((double)NA * D + (double)NB * D + (double)NA * NB));
-  hipLaunchKernelGGL(pa::k_row_norms_f64, dim3(pa::cdiv(NA, 128)), dim3(128), 0, st, A, NA, D, norms);
-  hipLaunchKernelGGL(pa::k_row_norms_f64, dim3(pa::cdiv(NB, 128)), dim3(128), 0, st, B, NB, D,
-                     norms + NA);
+  pa_row_norms_f64(A, NA, D, norms, stream);
+  pa_row_norms_f64(B, NB, D, norms + NA, stream);
   hipLaunchKernelGGL(pa::k_cdist_cosine_f64, dim3(NA), dim3(128), (size_t)D * sizeof(double), st, A, B,
                      NB, D, norms, norms + NA, out);
   PA_CHECK_LAUNCH("pa_cdist_cosine_f64");

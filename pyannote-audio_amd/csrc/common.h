@@ -28,8 +28,31 @@ PA_INTERNAL int pa_mfcc_frontend(const float* wav, long wav_len, long chunk_stri
 PA_INTERNAL int pa_stats_pool_rows_any(const float* feat, int B, int T0, int Tp, int C, int ld, const float* masks,
                                        int S, int Fm, const int* nearest_idx, float* stats, int ld_stats,
                                        const float* aff_scale, const float* aff_shift, void* stream);
+// csrc/cluster.hip -> csrc/linkage_fast.hip, csrc/linkage_chain.hip, csrc/verification.hip
+// S (n x ld, symmetric, zero diagonal) from the condensed matrix `cond` in pa_pdist_f64's order
+PA_INTERNAL void pa_square_from_condensed(const double* cond, int n, long ld, double* S, void* stream);
+// nrm[i] = row_norm_f64 of row i of X (N, D) (cosine_f64.h)
+PA_INTERNAL void pa_row_norms_f64(const double* X, int N, int D, double* nrm, void* stream);
 
+#include "workspace.h"
 namespace pa {
+
+// The square symmetric copy the linkage kernels merge on (csrc/cluster.hip): its leading dimension, a multiple of 8
+// doubles, and whether n points may have one -- PA_LINKAGE_FAST_MAX_GB caps its bytes (default 96 GB: n = 110 k) and
+// n <= 150 000 keeps an enormous cap from promising sizes nobody has run.  Both linkage paths ask here.
+inline long square_ld(int n) { return ((long)n + 7) & ~7L; }
+PA_INTERNAL bool square_fits(int n);
+
+// csrc/linkage_fast.hip -> csrc/linkage.hip: the heap-free merge in front of the heap kernel, its part of the workspace
+struct LfState {
+  double *S, *mind0;          // (n, square_ld(n)) square symmetric matrix; (n) initial lower bounds
+  int *nb0, *g_size, *g_cid;  // (n) each: initial neighbour candidates, sizes and ids of the multi-workgroup form
+  unsigned long long* mail;   // tagged granules of the exchange
+  int* status;                // the gate of the heap kernel: 0 = the dendrogram is complete
+};
+PA_INTERNAL bool lf_wanted(int n);
+PA_INTERNAL void lf_layout(Carver& c, int n, LfState& s);
+PA_INTERNAL int lf_launch(const double* cond, int n, double* Z, const LfState& s, long long* stats, hipStream_t st);
 
 void set_error(const char* fmt, ...);
 
@@ -74,6 +97,17 @@ __device__ __forceinline__ double wave_sum_d(double v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
   return v;
+}
+
+// a row scan's candidate (linkage.hip, linkage_chain.hip) and its lexicographic "first minimum": the smaller value wins,
+// equal values -> the smaller index; i < 0 = empty; NaN never wins
+struct MinPair {
+  double d;
+  int i;
+};
+__device__ __forceinline__ MinPair min_pair(MinPair a, MinPair b) {
+  if (b.i >= 0 && (a.i < 0 || b.d < a.d || (b.d == a.d && b.i < a.i))) return b;
+  return a;
 }
 
 // Block-wide sum for blocks of NW waves; `red` is an LDS array of >= NW floats.

@@ -63,12 +63,6 @@ struct KmState {
   double tol;
 };
 
-__device__ __forceinline__ double km_butterfly(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 // the columns lane, lane + 64, ... of a row; columns past D read as zero
 __device__ __forceinline__ void km_load_row(const double* __restrict__ row, int D, int lane, double (&x)[KM_CHUNKS]) {
 #pragma unroll
@@ -90,7 +84,7 @@ __device__ __forceinline__ double km_sqdist(const double (&x)[KM_CHUNKS], const 
       s += t * t;
     }
   }
-  return km_butterfly(s);
+  return wave_sum_d(s);
 }
 
 // first argmin over the centres of |c|^2 - 2 x.c (what sklearn's lloyd_iter minimises), the same in every lane
@@ -106,7 +100,7 @@ __device__ __forceinline__ int km_nearest(const double (&x)[KM_CHUNKS], const do
       const int d = lane + 64 * m;
       if (d < D) s += x[m] * c[d];
     }
-    const double v = csq[k] - 2.0 * km_butterfly(s);
+    const double v = csq[k] - 2.0 * wave_sum_d(s);
     if (k == 0 || v < best_v) best = k, best_v = v;
   }
   return best;
@@ -116,7 +110,7 @@ __device__ __forceinline__ int km_nearest(const double (&x)[KM_CHUNKS], const do
 __device__ __forceinline__ double km_wave_ordered_sum(const double* __restrict__ p, long n, int lane) {
   double s = 0.0;
   for (long i = lane; i < n; i += 64) s += p[i];
-  return km_butterfly(s);
+  return wave_sum_d(s);
 }
 
 // ---- preparation: column means, centred rows, tolerance ------------------------------------------------------------
@@ -254,7 +248,7 @@ __global__ __launch_bounds__(KM_T) void k_km_pp_adopt(KmState s, int c) {
   if (w == 0) {
     double sq = 0.0;
     for (int d = lane; d < s.D; d += 64) sq += x[d] * x[d];
-    sq = km_butterfly(sq);
+    sq = wave_sum_d(sq);
     if (lane == 0) s.csq[(size_t)(j * 2) * s.K + c] = sq;
   }
 }
@@ -390,8 +384,8 @@ __global__ __launch_bounds__(KM_T) void k_km_update(KmState s) {
     shift += t * t;
     sq += v * v;
   }
-  shift = km_butterfly(shift);
-  sq = km_butterfly(sq);
+  shift = wave_sum_d(shift);
+  sq = wave_sum_d(sq);
   if (lane == 0) red[0][w] = shift, red[1][w] = sq;
   __syncthreads();
   if (threadIdx.x == 0) {
@@ -486,13 +480,38 @@ __global__ __launch_bounds__(KM_T) void k_km_finish(KmState s) {
   for (int i = threadIdx.x; i < s.K * s.D; i += KM_T) out[i] = C[i] + s.mean[i % s.D];
 }
 
-static size_t km_align(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
-
 static int km_trials(int K) { return 2 + (K >= 3) + (K >= 8) + (K >= 21) + (K >= 55); }   // 2 + int(log(K)), K <= 64
 
 static bool km_supported(int N, int D, int K, int n_init) {
   return K >= 2 && K <= KM_MAX_K && D >= 1 && D <= KM_MAX_D && N >= K && N < (1 << 24) && n_init >= 1 &&
          n_init <= 65535;
+}
+
+// The workspace of pa_kmeans_f64, one 256-byte-aligned block per array: the KmState fields the caller does not give
+static KmState km_layout(Carver& c, int N, int D, int K, int n_init) {
+  KmState s;
+  const size_t n = N, d = D, k = K, J = n_init, T = km_trials(K), NB = (n + KM_ROWS - 1) / KM_ROWS;
+  s.Xc = c.take<double>(n * d);
+  s.mean = c.take<double>(d + 1);
+  s.tolv = s.mean + d;
+  s.closest = c.take<double>(J * n);
+  s.nd = c.take<double>(J * T * n);
+  s.potpart = c.take<double>(J * T * NB);
+  s.pot = c.take<double>(J);
+  s.C = c.take<double>(J * 2 * k * d);
+  s.csq = c.take<double>(J * 2 * k);
+  s.part = c.take<double>(J * NB * k * d);
+  s.shiftpart = c.take<double>(J * k);
+  s.inpart = c.take<double>(J * NB);
+  s.cnt = c.take<int>(J * NB * k);
+  s.changed = c.take<int>(J * NB);
+  s.cand = c.take<int>(J * T);
+  s.counts = c.take<int>(J * k);
+  s.done = c.take<int>(J);
+  s.cur = c.take<int>(J);
+  s.N = N, s.D = D, s.K = K, s.J = n_init, s.T = (int)T, s.NB = (int)NB;
+  s.DC = std::min(D, KM_ACC / K);
+  return s;
 }
 
 }  // namespace pa
@@ -503,13 +522,8 @@ int pa_kmeans_max_clusters(void) { return pa::KM_MAX_K; }
 int pa_kmeans_max_dim(void) { return pa::KM_MAX_D; }
 
 size_t pa_kmeans_workspace_bytes(int N, int D, int K, int n_init) {
-  using pa::km_align;
   if (!pa::km_supported(N, D, K, n_init)) return 0;
-  const size_t n = N, d = D, k = K, J = n_init, T = pa::km_trials(K), NB = (n + pa::KM_ROWS - 1) / pa::KM_ROWS;
-  return km_align(8 * n * d) + km_align(8 * (d + 1)) + km_align(8 * J * n) + km_align(8 * J * T * n) +
-         km_align(8 * J * T * NB) + km_align(8 * J) + km_align(8 * J * 2 * k * d) + km_align(8 * J * 2 * k) +
-         km_align(8 * J * NB * k * d) + km_align(8 * J * k) + km_align(8 * J * NB) + km_align(4 * J * NB * k) +
-         km_align(4 * J * NB) + km_align(4 * J * T) + km_align(4 * J * k) + 2 * km_align(4 * J);
+  return pa::carved_bytes([&](pa::Carver& c) { pa::km_layout(c, N, D, K, n_init); });
 }
 
 int pa_kmeans_f64(const double* X, int N, int D, int K, int n_init, const int32_t* first, const double* uniforms,
@@ -522,38 +536,13 @@ int pa_kmeans_f64(const double* X, int N, int D, int K, int n_init, const int32_
   PA_REQUIRE(N < (1 << 24), "pa_kmeans_f64: 2^24 rows or more");
   PA_REQUIRE(n_init >= 1 && n_init <= 65535, "pa_kmeans_f64: n_init outside 1..65535");
   PA_REQUIRE(max_iter >= 1, "pa_kmeans_f64: max_iter below 1");
-  PA_REQUIRE(workspace_bytes >= pa_kmeans_workspace_bytes(N, D, K, n_init), "pa_kmeans_f64: workspace too small");
-  using pa::km_align;
-  const size_t n = N, d = D, k = K, J = n_init, T = pa::km_trials(K), NB = (n + pa::KM_ROWS - 1) / pa::KM_ROWS;
-  char* w = (char*)workspace;
-  auto take = [&](size_t bytes) {
-    char* p = w;
-    w += km_align(bytes);
-    return p;
-  };
-  pa::KmState s;
+  pa::Carver carver(workspace);
+  pa::KmState s = pa::km_layout(carver, N, D, K, n_init);
+  PA_REQUIRE(workspace_bytes >= carver.bytes(), "pa_kmeans_f64: workspace too small");
   s.X = X, s.first = first, s.uniforms = uniforms;
-  s.Xc = (double*)take(8 * n * d);
-  s.mean = (double*)take(8 * (d + 1));
-  s.tolv = s.mean + d;
-  s.closest = (double*)take(8 * J * n);
-  s.nd = (double*)take(8 * J * T * n);
-  s.potpart = (double*)take(8 * J * T * NB);
-  s.pot = (double*)take(8 * J);
-  s.C = (double*)take(8 * J * 2 * k * d);
-  s.csq = (double*)take(8 * J * 2 * k);
-  s.part = (double*)take(8 * J * NB * k * d);
-  s.shiftpart = (double*)take(8 * J * k);
-  s.inpart = (double*)take(8 * J * NB);
-  s.cnt = (int*)take(4 * J * NB * k);
-  s.changed = (int*)take(4 * J * NB);
-  s.cand = (int*)take(4 * J * T);
-  s.counts = (int*)take(4 * J * k);
-  s.done = (int*)take(4 * J);
-  s.cur = (int*)take(4 * J);
   s.labels = labels, s.centers = centers, s.inertia = inertia, s.picks = picks, s.status = status;
-  s.N = N, s.D = D, s.K = K, s.J = n_init, s.T = (int)T, s.NB = (int)NB, s.max_iter = max_iter, s.tol = tol;
-  s.DC = std::min(D, pa::KM_ACC / K);
+  s.max_iter = max_iter, s.tol = tol;
+  const size_t n = N, d = D, k = K, J = n_init, NB = s.NB;
   hipStream_t st = (hipStream_t)stream;
   const dim3 row_grid((unsigned)NB, (unsigned)J), job_grid((unsigned)J);
   const size_t acc_bytes = (size_t)K * s.DC * 8;

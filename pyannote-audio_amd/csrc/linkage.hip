@@ -98,15 +98,6 @@ struct Heap {
   }
 };
 
-struct MinPair {
-  double d;
-  int i;
-};
-// lexicographic "first minimum": smaller value wins, equal values -> smaller index; NaN never wins
-__device__ __forceinline__ MinPair min_pair(MinPair a, MinPair b) {
-  if (b.i >= 0 && (a.i < 0 || b.d < a.d || (b.d == a.d && b.i < a.i))) return b;
-  return a;
-}
 // first minimum over the 64 lanes of a wave, valid in every lane
 __device__ __forceinline__ MinPair wave_min_pair(MinPair best) {
 #pragma unroll
@@ -435,29 +426,28 @@ __global__ __launch_bounds__(LK_T) void k_linkage_centroid(double* __restrict__ 
 
 constexpr size_t LK_LDS_MAX = 160 * 1024 - 7680;  // dynamic LDS budget (static part: ~6.5 KB)
 
-inline size_t lk_align(size_t v) { return (v + 255) & ~(size_t)255; }
-
-// linkage_fast.hip: the heap-free merge that runs first; the kernel of this file is its gated fallback
-bool lf_wanted(int n);
-size_t lf_workspace_bytes(int n);
-int lf_launch(const double* cond, int n, double* Z, void* workspace, long long* stats, int** gate_out,
-              hipStream_t st);
-
-// Byte offsets of the heap kernel's state in the workspace: size (at 0), cluster_id, neighbour, kbi, ibk (int) +
-// heap values (double); the three heap arrays are used only when the heap does not fit into LDS
-struct LkLayout {
-  size_t cid, nb, kbi, ibk, hv, end;
+// The workspace of pa_linkage_centroid_f64 in 256-byte-aligned blocks: the heap kernel's state (the three heap arrays
+// are used only when the heap does not fit into LDS), the fast path's when it is wanted (linkage_fast.hip), then 16
+// int64 development counters, 8 + 8: the LAST 128 bytes, where distance.linkage_centroid reads them.
+struct LkState {
+  int *size, *cid, *nb, *kbi, *ibk;
+  double* hv;
+  bool fast;
+  LfState lf;
+  long long* stats;
 };
-inline LkLayout lk_layout(int n) {
-  const size_t ni = lk_align(sizeof(int) * (size_t)n), nd = lk_align(sizeof(double) * (size_t)n);
-  LkLayout l;
-  l.cid = ni;
-  l.nb = l.cid + ni;
-  l.kbi = l.nb + ni;
-  l.ibk = l.kbi + ni;
-  l.hv = l.ibk + ni;
-  l.end = l.hv + nd;
-  return l;
+static LkState lk_layout(Carver& c, int n) {
+  LkState s;
+  s.size = c.take<int>(n);
+  s.cid = c.take<int>(n);
+  s.nb = c.take<int>(n);
+  s.kbi = c.take<int>(n);
+  s.ibk = c.take<int>(n);
+  s.hv = c.take<double>(n);
+  s.fast = lf_wanted(n);
+  if (s.fast) lf_layout(c, n, s.lf);
+  s.stats = c.take<long long>(16, 128);
+  return s;
 }
 // dynamic LDS of the candidate bitmap (one bit per row)
 inline size_t lk_cand_bytes(int n) { return 4 * (size_t)((n + 31) / 32) + 16; }
@@ -466,34 +456,27 @@ inline size_t lk_cand_bytes(int n) { return 4 * (size_t)((n + 31) / 32) + 16; }
 
 extern "C" {
 
-// layout: [heap kernel state][fast path: square matrix + row state][16 int64 counters: 8 heap kernel, 8 fast path]
 size_t pa_linkage_workspace_bytes(int n) {
   if (n < 2) return 0;
-  return pa::lk_layout(n).end + pa::lf_workspace_bytes(n) + 128;
+  return pa::carved_bytes([&](pa::Carver& c) { pa::lk_layout(c, n); });
 }
 
 // D: condensed distance matrix (n*(n-1)/2 doubles), OVERWRITTEN.  Z: (n-1, 4) doubles, SciPy layout.
 int pa_linkage_centroid_f64(double* D, int n, double* Z, void* workspace, size_t workspace_bytes,
                             void* stream) {
   if (n < 2) return 0;
-  PA_REQUIRE(workspace_bytes >= pa_linkage_workspace_bytes(n), "pa_linkage_centroid_f64: workspace too small");
-  const pa::LkLayout l = pa::lk_layout(n);
-  unsigned char* w = (unsigned char*)workspace;
-  int* size = (int*)w;
-  int* cid = (int*)(w + l.cid);
-  int* nb = (int*)(w + l.nb);
-  int* kbi = (int*)(w + l.kbi);
-  int* ibk = (int*)(w + l.ibk);
-  double* hv = (double*)(w + l.hv);
-  long long* stats = (long long*)(w + pa_linkage_workspace_bytes(n) - 128);
+  pa::Carver carver(workspace);
+  const pa::LkState s = pa::lk_layout(carver, n);
+  PA_REQUIRE(workspace_bytes >= carver.bytes(), "pa_linkage_centroid_f64: workspace too small");
   hipStream_t st = (hipStream_t)stream;
   // the merge loop is O(N^2) memory traffic in total; algorithmic bytes ~ 3 rows of 8*N per merge
   pa::ProfScope prof("k_linkage_centroid", stream, 9.0 * n * (double)n, 24.0 * n * (double)n);
-  if (hipMemsetAsync(stats, 0, 128, st) != hipSuccess) return 1;
+  if (hipMemsetAsync(s.stats, 0, 128, st) != hipSuccess) return 1;
   // ---- the heap-free merge first (linkage_fast.hip); its status word gates the exact heap replay below
   int* gate = nullptr;
-  if (pa::lf_wanted(n)) {
-    if (pa::lf_launch(D, n, Z, w + l.end, stats + 8, &gate, st) != 0) return 1;
+  if (s.fast) {
+    if (pa::lf_launch(D, n, Z, s.lf, s.stats + 8, st) != 0) return 1;
+    gate = s.lf.status;
     PA_CHECK_LAUNCH("pa_linkage_centroid_f64 (fast path)");
   }
   // `big_lds`: the instantiation keeps its heap in dynamic LDS beyond the default limit (the attribute is set on
@@ -502,7 +485,8 @@ int pa_linkage_centroid_f64(double* D, int n, double* Z, void* workspace, size_t
     if (big_lds)
       (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
                                 (int)pa::LK_LDS_MAX);
-    hipLaunchKernelGGL(kernel, dim3(1), dim3(pa::LK_T), lds, st, D, n, Z, size, cid, hv, kbi, ibk, nb, stats, gate);
+    hipLaunchKernelGGL(kernel, dim3(1), dim3(pa::LK_T), lds, st, D, n, Z, s.size, s.cid, s.hv, s.kbi, s.ibk, s.nb,
+                       s.stats, gate);
   };
   // 16-bit keys: heap values, kbi, ibk and neighbours (14 bytes per row) + the candidate bitmap in LDS
   const size_t cand_bytes = pa::lk_cand_bytes(n);

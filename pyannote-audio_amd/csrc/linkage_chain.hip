@@ -7,8 +7,8 @@
 // Why a kernel: both algorithms are N-1 dependent merges with O(N) independent work per step -- a row scan for the
 // nearest neighbour, a Lance-Williams update of one row and column -- that SciPy walks on one host core after the
 // whole condensed matrix crossed PCIe.  Here the matrix stays in HBM: a SQUARE SYMMETRIC copy (8 n ld bytes in the
-// workspace, built by k_lc_expand) makes the scan of row x and the update of row y contiguous; in condensed layout
-// the i < x half of a row is a stride-n gather.
+// workspace, built by pa_square_from_condensed of cluster.hip) makes the scan of row x and the update of row y
+// contiguous; in condensed layout the i < x half of a row is a stride-n gather.
 //
 // ONE persistent 1024-thread workgroup (a multi-workgroup form is out of scope), __syncthreads between phases, no
 // grid barrier and no spinning on memory.  Two kernels:
@@ -43,30 +43,21 @@ constexpr int LC_U = 8;  // row elements per thread in flight (one audio-hour = 
 
 enum { LC_OK = 0, LC_ERR_CHAIN = 1, LC_ERR_NO_NEIGHBOUR = 2 };
 
-struct LcMin {
-  double d;
-  int i;
-};
-// lexicographic "first minimum": smaller value wins, equal values -> smaller index; i < 0 = empty; NaN never wins
-__device__ __forceinline__ LcMin lc_min(LcMin a, LcMin b) {
-  if (b.i >= 0 && (a.i < 0 || b.d < a.d || (b.d == a.d && b.i < a.i))) return b;
-  return a;
-}
 // first minimum over the workgroup, valid in every thread.  `red`: LC_W slots nobody else touches until the next
 // barrier but one (the callers alternate between two sets).  ONE barrier.
-__device__ __forceinline__ LcMin lc_block_min(LcMin best, LcMin* red) {
+__device__ __forceinline__ MinPair lc_block_min(MinPair best, MinPair* red) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) {
-    LcMin other;
+    MinPair other;
     other.d = __shfl_xor(best.d, o, 64);
     other.i = __shfl_xor(best.i, o, 64);
-    best = lc_min(best, other);
+    best = min_pair(best, other);
   }
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = best;
   __syncthreads();
-  LcMin r = red[0];
+  MinPair r = red[0];
 #pragma unroll
-  for (int q = 1; q < LC_W; ++q) r = lc_min(r, red[q]);
+  for (int q = 1; q < LC_W; ++q) r = min_pair(r, red[q]);
   return r;
 }
 
@@ -81,37 +72,14 @@ __device__ __forceinline__ double lc_update(double a, double b, double c, int nx
   return sqrt((ni + nx) * t * a * a + (ni + ny) * t * b * b - ni * t * c * c);
 }
 
-// condensed -> square symmetric, leading dimension ld, zero diagonal.  grid = (tiles, tiles), upper tiles only;
-// block = 256 over a 64 x 64 tile: both the direct and the mirrored tile are written along rows.
-__global__ __launch_bounds__(256) void k_lc_expand(const double* __restrict__ cond, int n, long ld,
-                                                    double* __restrict__ S) {
-  const int bi = blockIdx.y, bj = blockIdx.x;
-  if (bj < bi) return;
-  __shared__ double tile[64][65];
-  const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
-  for (int r = ty; r < 64; r += 4) {
-    const long i = bi * 64 + r, j = bj * 64 + tx;
-    double v = 0.0;
-    if (i < n && j < n && i != j) v = i < j ? cond[n * i - i * (i + 1) / 2 + (j - i - 1)] : cond[n * j - j * (j + 1) / 2 + (i - j - 1)];
-    tile[r][tx] = v;
-    if (i < n && j < n) S[i * ld + j] = v;
-  }
-  if (bi == bj) return;  // (a diagonal tile is its own mirror image)
-  __syncthreads();
-  for (int r = ty; r < 64; r += 4) {
-    const long j = bj * 64 + r, i = bi * 64 + tx;
-    if (i < n && j < n) S[j * ld + i] = tile[tx][r];
-  }
-}
-
 // nn_chain(D, n, method): raw[k] = (x, y, height, size) for k = 0 .. n-2, x < y cluster SLOTS (not ids).
 template <int METHOD, bool LDS_STATE>
 __global__ __launch_bounds__(LC_T) void k_lc_nn_chain(double* __restrict__ S, int n, long ld, double* __restrict__ raw,
                                                        int* __restrict__ g_size, int* __restrict__ g_chain,
                                                        int* __restrict__ status) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char lc_lds[];
-  __shared__ LcMin red[2][LC_W];
-  int* const size = LDS_STATE ? reinterpret_cast<int*>(lc_lds) : g_size;
+  extern __shared__ __attribute__((aligned(16))) unsigned char lc_smem[];
+  __shared__ MinPair red[2][LC_W];
+  int* const size = LDS_STATE ? reinterpret_cast<int*>(lc_smem) : g_size;
   int* const chain = LDS_STATE ? size + n : g_chain;
   const int tid = threadIdx.x;
   for (int i = tid; i < n; i += LC_T) size[i] = 1;
@@ -137,7 +105,7 @@ __global__ __launch_bounds__(LC_T) void k_lc_nn_chain(double* __restrict__ S, in
     for (;;) {
       // ---- nearest active neighbour of x; the previous chain element is preferred on equal distance
       const double* row = S + (long)x * ld;
-      LcMin best{__builtin_inf(), -1};
+      MinPair best{__builtin_inf(), -1};
       for (int i0 = tid; i0 < n; i0 += LC_U * LC_T) {
         double d[LC_U];
         bool act[LC_U];
@@ -230,9 +198,9 @@ template <bool LDS_STATE>
 __global__ __launch_bounds__(LC_T) void k_lc_mst_single(const double* __restrict__ S, int n, long ld,
                                                          double* __restrict__ raw, int* __restrict__ g_size,
                                                          double* __restrict__ dmin, int* __restrict__ status) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char lc_lds[];
-  __shared__ LcMin red[2][LC_W];
-  int* const size = LDS_STATE ? reinterpret_cast<int*>(lc_lds) : g_size;
+  extern __shared__ __attribute__((aligned(16))) unsigned char lc_smem[];
+  __shared__ MinPair red[2][LC_W];
+  int* const size = LDS_STATE ? reinterpret_cast<int*>(lc_smem) : g_size;
   const int tid = threadIdx.x;
   for (int i = tid; i < n; i += LC_T) {
     size[i] = 1;
@@ -242,7 +210,7 @@ __global__ __launch_bounds__(LC_T) void k_lc_mst_single(const double* __restrict
   for (int k = 0; k < n - 1; ++k) {
     if ((x & (LC_T - 1)) == tid) size[x] = 0;  // merged[x] = 1, by its owner
     const double* row = S + (long)x * ld;
-    LcMin best{__builtin_inf(), -1};
+    MinPair best{__builtin_inf(), -1};
     for (int i0 = tid; i0 < n; i0 += LC_U * LC_T) {
       double d[LC_U], m[LC_U];
       bool act[LC_U];
@@ -289,11 +257,6 @@ __global__ __launch_bounds__(256) void k_lc_nonfinite(const double* __restrict__
   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < count; i += (long)gridDim.x * 256)
     bad |= !(fabs(v[i]) < __builtin_inf());
   if (__any(bad) && (threadIdx.x & 63) == 0) *flag = 1;  // (racing writers all store 1)
-}
-
-__global__ void k_lc_row_norms(const double* __restrict__ X, int N, int D, double* __restrict__ nrm) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < N) nrm[i] = row_norm_f64(X + (long)i * D, D);
 }
 
 constexpr int LC_PT = 64;  // pairs tile edge
@@ -366,38 +329,26 @@ __global__ __launch_bounds__(256) void k_lc_pdist_cosine(const double* __restric
 
 constexpr size_t LC_LDS_MAX = 160 * 1024 - 1024;  // dynamic LDS budget (static part: 512 B)
 
-inline size_t lc_align(size_t v) { return (v + 255) & ~(size_t)255; }
-inline long lc_ld(int n) { return ((long)n + 7) & ~7L; }
-
-// The cap of the square copy.  TWIN of lf_wanted (linkage_fast.hip, which this change leaves as it is): the same
-// environment variable, the same 96 GB default and the same n <= 150 000, so that the centroid path and this one give
-// up at the same sizes -- change both together.  (150 000 points are 180 GB of square matrix: beyond the default cap
-// anyway; the bound only keeps an enormous PA_LINKAGE_FAST_MAX_GB from promising sizes nobody has run.)
-static bool lc_fits(int n) {
-  const char* g = getenv("PA_LINKAGE_FAST_MAX_GB");
-  const double cap = (g != nullptr && atof(g) > 0 ? atof(g) : 96.0) * 1e9;
-  return 8.0 * (double)n * (double)lc_ld(n) <= cap && n <= 150000;
-}
-
-// workspace: [status + padding: 256 B][size: n int][chain: n int][Dmin: n double][square matrix: n x ld double]
-struct LcLayout {
-  size_t size, chain, dmin, square, end;
+// The workspace of pa_linkage_chain_f64 in 256-byte-aligned blocks: the status word with its padding, size[] and the
+// chain (used when they do not live in LDS), Dmin of single linkage, the square matrix
+struct LcState {
+  int *status, *size, *chain;
+  double *dmin, *S;
 };
-inline LcLayout lc_layout(int n) {
-  const size_t ni = lc_align(sizeof(int) * (size_t)n), nd = lc_align(sizeof(double) * (size_t)n);
-  LcLayout l;
-  l.size = 256;
-  l.chain = l.size + ni;
-  l.dmin = l.chain + ni;
-  l.square = l.dmin + nd;
-  l.end = l.square + lc_align(8 * (size_t)n * (size_t)lc_ld(n));
-  return l;
+static LcState lc_layout(Carver& c, int n) {
+  LcState s;
+  s.status = c.take<int>(64);
+  s.size = c.take<int>(n);
+  s.chain = c.take<int>(n);
+  s.dmin = c.take<double>(n);
+  s.S = c.take<double>((size_t)n * (size_t)square_ld(n));
+  return s;
 }
 
 // dynamic LDS of the merge kernels: size[] and the chain for nn_chain (8 n B: up to n = 20 352), size[] alone for
 // single linkage (4 n B: up to n = 40 704); 0 = the state lives in the workspace.  PA_LINKAGE_CHAIN_LDS=0 asks for
 // that form at every n (the form large n takes; tests).
-static size_t lc_lds_bytes(int n, int method) {
+static size_t lc_smem_bytes(int n, int method) {
   const char* e = getenv("PA_LINKAGE_CHAIN_LDS");
   if (e != nullptr && atoi(e) == 0) return 0;
   const size_t bytes = (method == PA_LINKAGE_SINGLE ? 4 : 8) * (size_t)n;
@@ -417,7 +368,7 @@ int pa_pdist_cosine_f64(const double* X, int N, int D, double* out, double* norm
   const int nt = pa::cdiv(N, pa::LC_PT);
   pa::ProfScope prof("k_pdist_cosine_f64", stream, 2.0 * D * ((double)N * (N - 1) / 2),
                      8.0 * ((double)N * D + (double)N * (N - 1) / 2));
-  hipLaunchKernelGGL(pa::k_lc_row_norms, dim3(pa::cdiv(N, 128)), dim3(128), 0, st, X, N, D, norms);
+  pa_row_norms_f64(X, N, D, norms, stream);
   hipLaunchKernelGGL(pa::k_lc_pdist_cosine, dim3(nt, nt), dim3(256), 0, st, X, N, D, norms, out);
   PA_CHECK_LAUNCH("pa_pdist_cosine_f64");
   return 0;
@@ -438,8 +389,8 @@ int pa_nonfinite_flag_f64(const double* v, long count, int* flag, void* stream) 
 
 // 0: n < 2, or the square copy exceeds the cap (the caller keeps the host path)
 size_t pa_linkage_chain_workspace_bytes(int n) {
-  if (n < 2 || !pa::lc_fits(n)) return 0;
-  return pa::lc_layout(n).end;
+  if (n < 2 || !pa::square_fits(n)) return 0;
+  return pa::carved_bytes([&](pa::Carver& c) { pa::lc_layout(c, n); });
 }
 
 int pa_linkage_chain_f64(const double* D, int n, int method, double* raw, void* workspace, size_t workspace_bytes,
@@ -449,37 +400,32 @@ int pa_linkage_chain_f64(const double* D, int n, int method, double* raw, void* 
                  method == PA_LINKAGE_WEIGHTED || method == PA_LINKAGE_WARD,
              "pa_linkage_chain_f64: unknown method %d", method);
   PA_REQUIRE(D && raw && workspace, "pa_linkage_chain_f64: null array");
-  PA_REQUIRE(pa::lc_fits(n), "pa_linkage_chain_f64: the square matrix of %d points exceeds PA_LINKAGE_FAST_MAX_GB", n);
-  PA_REQUIRE(workspace_bytes >= pa_linkage_chain_workspace_bytes(n), "pa_linkage_chain_f64: workspace too small");
-  const pa::LcLayout l = pa::lc_layout(n);
-  unsigned char* w = (unsigned char*)workspace;
-  int* status = (int*)w;
-  int* size = (int*)(w + l.size);
-  int* chain = (int*)(w + l.chain);
-  double* dmin = (double*)(w + l.dmin);
-  double* S = (double*)(w + l.square);
-  const long ld = pa::lc_ld(n);
+  PA_REQUIRE(pa::square_fits(n),
+             "pa_linkage_chain_f64: the square matrix of %d points exceeds PA_LINKAGE_FAST_MAX_GB", n);
+  pa::Carver carver(workspace);
+  const pa::LcState s = pa::lc_layout(carver, n);
+  PA_REQUIRE(workspace_bytes >= carver.bytes(), "pa_linkage_chain_f64: workspace too small");
+  const long ld = pa::square_ld(n);
   hipStream_t st = (hipStream_t)stream;
   // ~3 row scans + 1 update (2 rows in, row + column out) per merge
   pa::ProfScope prof("k_linkage_chain", stream, 4.0 * n * (double)n, 8.0 * 7.0 * n * (double)n);
   // the status word stays non-zero unless the merge kernel runs to its end
-  if (hipMemsetAsync(status, 0xFF, 256, st) != hipSuccess) return 1;
-  const int nt = pa::cdiv(n, 64);
-  hipLaunchKernelGGL(pa::k_lc_expand, dim3(nt, nt), dim3(256), 0, st, D, n, ld, S);
+  if (hipMemsetAsync(s.status, 0xFF, 256, st) != hipSuccess) return 1;
+  pa_square_from_condensed(D, n, ld, s.S, stream);
   PA_CHECK_LAUNCH("pa_linkage_chain_f64 (square copy)");
-  const size_t lds_bytes = pa::lc_lds_bytes(n, method);
+  const size_t lds_bytes = pa::lc_smem_bytes(n, method);
   const bool lds = lds_bytes != 0;
   // one workgroup; `state`: the chain (nn_chain) or Dmin (single linkage).  (The attribute is set on every call: it
   // belongs to the current device, not to the process.)
   auto launch = [&](auto kernel, auto* state) {
     if (lds)
       (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pa::LC_LDS_MAX);
-    hipLaunchKernelGGL(kernel, dim3(1), dim3(pa::LC_T), lds_bytes, st, S, n, ld, raw, size, state, status);
+    hipLaunchKernelGGL(kernel, dim3(1), dim3(pa::LC_T), lds_bytes, st, s.S, n, ld, raw, s.size, state, s.status);
   };
 #define PA_LC_CHAIN(M)                                          \
   case M:                                                       \
-    if (lds) launch(pa::k_lc_nn_chain<M, true>, chain);         \
-    else launch(pa::k_lc_nn_chain<M, false>, chain);            \
+    if (lds) launch(pa::k_lc_nn_chain<M, true>, s.chain);       \
+    else launch(pa::k_lc_nn_chain<M, false>, s.chain);          \
     break;
   switch (method) {
     PA_LC_CHAIN(PA_LINKAGE_COMPLETE)
@@ -487,8 +433,8 @@ int pa_linkage_chain_f64(const double* D, int n, int method, double* raw, void* 
     PA_LC_CHAIN(PA_LINKAGE_WEIGHTED)
     PA_LC_CHAIN(PA_LINKAGE_WARD)
     default:
-      if (lds) launch(pa::k_lc_mst_single<true>, dmin);
-      else launch(pa::k_lc_mst_single<false>, dmin);
+      if (lds) launch(pa::k_lc_mst_single<true>, s.dmin);
+      else launch(pa::k_lc_mst_single<false>, s.dmin);
   }
 #undef PA_LC_CHAIN
   PA_CHECK_LAUNCH("pa_linkage_chain_f64");

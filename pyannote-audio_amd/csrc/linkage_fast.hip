@@ -16,7 +16,7 @@
 // What made the heap kernel 25 us per merge (round 3, N = 7 176: pass 29 k cycles, find 14 k, replay 12 k, waits 5 k)
 // and what replaces it:
 //   * column accesses D[z][x], D[z][y] for z < x in the CONDENSED matrix (one cache line per lane): the merge works
-//     on a SQUARE symmetric copy (k_lf_square, N x ld doubles; 412 MB at N = 7 176, 26 GB at 57 k -- HBM3E is
+//     on a SQUARE symmetric copy (cluster.hip, N x ld doubles; 412 MB at N = 7 176, 26 GB at 57 k -- HBM3E is
 //     288 GB): rows x and y are read coalesced, the new row y is written coalesced, only the mirror column
 //     D[z][y] is scattered -- as stores, which nothing waits for individually.
 //   * `dist == D[x][neighbor[x]]`, a dependent global load per pop: replaced by an EXACT bit per row, maintained
@@ -66,6 +66,7 @@ constexpr int LF_T = 1 << LF_SH;
 constexpr int LF_W = LF_T / 64;
 constexpr int LF_PU = 4;    // rows per thread whose matrix loads are in flight together
 constexpr int LF_MAXG = 16;
+constexpr int LF_MAIL_GRANULES = 2 * LF_MAXG * 16;   // 8-byte granules of the mailbox: two parities x 16 records of 16
 constexpr lf_u64 LF_INF = 0x7ff0000000000000ULL;   // key of "no bound": +inf (NaN and negatives sort above)
 constexpr lf_u32 LF_ABORT = 0xAB0127u;              // granule 13 of a record: "I gave up, leave"
 
@@ -127,34 +128,6 @@ __device__ __forceinline__ lf_u32 lf_rl(lf_u32 v, int lane) { return (lf_u32)__b
 template <int Q>
 __device__ __forceinline__ lf_u32 lf_quad(lf_u32 v) {   // value of quad lane Q
   return (lf_u32)__builtin_amdgcn_update_dpp((int)v, (int)v, Q * 0x55, 0xf, 0xf, false);
-}
-
-// condensed (SciPy pdist order) -> square symmetric, leading dimension ld (multiple of 8 doubles); 64 x 64 tiles,
-// the mirror tile transposed through LDS so that both are written in whole lines.  grid = (nt, nt), bj >= bi works.
-__global__ __launch_bounds__(256) void k_lf_square(const double* __restrict__ cond, int n, long ld,
-                                                    double* __restrict__ S) {
-  const int bi = blockIdx.y, bj = blockIdx.x;
-  if (bj < bi) return;
-  __shared__ double tile[64][65];
-  const int tid = threadIdx.x;
-  for (int e = tid; e < 4096; e += 256) {
-    const int r = e >> 6, c = e & 63;
-    const long i = bi * 64 + r, j = bj * 64 + c;
-    double v = 0.0;
-    if (i < n && j < n && i != j) {
-      const long a = i < j ? i : j, b = i < j ? j : i;
-      v = cond[(long)n * a - (a * (a + 1) / 2) + (b - a - 1)];
-    }
-    tile[r][c] = v;
-    if (i < n && j < n) S[i * ld + j] = v;
-  }
-  if (bi == bj) return;
-  __syncthreads();
-  for (int e = tid; e < 4096; e += 256) {
-    const int r = e >> 6, c = e & 63;
-    const long j = bj * 64 + r, i = bi * 64 + c;
-    if (i < n && j < n) S[j * ld + i] = tile[c][r];
-  }
 }
 
 // find_min_dist(n, D, size, x) of the initial state for every row: first minimum of row x over i > x, from the
@@ -697,25 +670,25 @@ __global__ __launch_bounds__(LF_T) void k_linkage_fast(double* __restrict__ S, l
 
 constexpr size_t LF_LDS_MAX = 160 * 1024 - 6144;   // dynamic LDS budget (static part: exchange buffers, ~2.7 KB)
 
-inline size_t lf_align(size_t v) { return (v + 255) & ~(size_t)255; }
-inline long lf_ld(int n) { return ((long)n + 7) & ~7L; }
-
 // the fast path wants N x ld doubles more: PA_LINKAGE_FAST=0 switches it off, PA_LINKAGE_FAST_MAX_GB caps the square
-// matrix (default 96 GB: N = 110 k)
+// matrix (square_fits)
 bool lf_wanted(int n) {
   if (n < 3) return false;
   const char* e = getenv("PA_LINKAGE_FAST");
   if (e != nullptr && atoi(e) == 0) return false;
-  const char* g = getenv("PA_LINKAGE_FAST_MAX_GB");
-  const double cap = (g != nullptr && atof(g) > 0 ? atof(g) : 96.0) * 1e9;
-  return 8.0 * (double)n * (double)lf_ld(n) <= cap && n <= 150000;
+  return square_fits(n);
 }
 
-// bytes the fast path adds to the linkage workspace: square matrix + initial candidates + sizes / ids + mail + status
-size_t lf_workspace_bytes(int n) {
-  if (!lf_wanted(n)) return 0;
-  const size_t ni = lf_align(sizeof(int) * (size_t)n), nd = lf_align(sizeof(double) * (size_t)n);
-  return lf_align(8 * (size_t)n * (size_t)lf_ld(n)) + 3 * ni + nd + lf_align(2 * LF_MAXG * 16 * 8) + 256;
+// what the fast path adds to the linkage workspace, in 256-byte-aligned blocks: the square matrix, the initial
+// candidates, sizes / ids, the initial bounds, the mail granules and the status word (with its padding)
+void lf_layout(Carver& c, int n, LfState& s) {
+  s.S = c.take<double>((size_t)n * (size_t)square_ld(n));
+  s.nb0 = c.take<int>(n);
+  s.g_size = c.take<int>(n);
+  s.g_cid = c.take<int>(n);
+  s.mind0 = c.take<double>(n);
+  s.mail = c.take<unsigned long long>(LF_MAIL_GRANULES);
+  s.status = c.take<int>(64);
 }
 
 // workgroups of the merge: 1 up to N = 1 024, 8 up to 12 000, 16 above (measured on MI355X, profiles/r4_linkage_*:
@@ -744,27 +717,14 @@ static long long lf_poll_limit_ticks() {
   return (long long)(ms * (double)khz);
 }
 
-// launches square conversion + initial candidates + the merge kernel on `st`; *gate_out = device address of the
-// status word (0 after the kernel = Z is complete).  `stats`: 8 int64 of development counters.
-int lf_launch(const double* cond, int n, double* Z, void* workspace, long long* stats, int** gate_out,
-              hipStream_t st) {
-  const size_t ni = lf_align(sizeof(int) * (size_t)n), nd = lf_align(sizeof(double) * (size_t)n);
-  const long ld = lf_ld(n);
-  unsigned char* w = (unsigned char*)workspace;
-  double* S = (double*)w;
-  w += lf_align(8 * (size_t)n * (size_t)ld);
-  int* nb0 = (int*)w;
-  int* g_size = (int*)(w + ni);
-  int* g_cid = (int*)(w + 2 * ni);
-  double* mind0 = (double*)(w + 3 * ni);
-  lf_u64* mail = (lf_u64*)(w + 3 * ni + nd);
-  int* status = (int*)(w + 3 * ni + nd + lf_align(2 * LF_MAXG * 16 * 8));
-  *gate_out = status;
-  if (hipMemsetAsync(mail, 0, 2 * LF_MAXG * 16 * 8, st) != hipSuccess) return 1;
-  if (hipMemsetAsync(status, 0xff, sizeof(int), st) != hipSuccess) return 1;   // "not run" = take the heap
-  const int nt = cdiv(n, 64);
-  hipLaunchKernelGGL(k_lf_square, dim3(nt, nt), dim3(256), 0, st, cond, n, ld, S);
-  hipLaunchKernelGGL(k_lf_row_nearest, dim3(cdiv(n - 1, 4)), dim3(256), 0, st, cond, n, nb0, mind0);
+// launches square conversion + initial candidates + the merge kernel on `st`; the status word s.status gates the heap
+// kernel (0 after the kernel = Z is complete).  `stats`: 8 int64 of development counters.
+int lf_launch(const double* cond, int n, double* Z, const LfState& s, long long* stats, hipStream_t st) {
+  const long ld = square_ld(n);
+  if (hipMemsetAsync(s.mail, 0, LF_MAIL_GRANULES * 8, st) != hipSuccess) return 1;
+  if (hipMemsetAsync(s.status, 0xff, sizeof(int), st) != hipSuccess) return 1;   // "not run" = take the heap
+  pa_square_from_condensed(cond, n, ld, s.S, st);
+  hipLaunchKernelGGL(k_lf_row_nearest, dim3(cdiv(n - 1, 4)), dim3(256), 0, st, cond, n, s.nb0, s.mind0);
   const int G = lf_num_workgroups(n);
   const int SL = cdiv(cdiv(n, LF_T), G);
   const long long poll_limit = lf_poll_limit_ticks();
@@ -772,15 +732,15 @@ int lf_launch(const double* cond, int n, double* Z, void* workspace, long long* 
     const size_t lds = (size_t)SL * LF_T * 14;
     (void)hipFuncSetAttribute((const void*)k_linkage_fast<unsigned short, false>,
                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)LF_LDS_MAX);
-    hipLaunchKernelGGL((k_linkage_fast<unsigned short, false>), dim3(1), dim3(LF_T), lds, st, S, ld, n, Z, nb0, mind0,
-                       g_size, g_cid, mail, 1, SL, poll_limit, status, stats);
+    hipLaunchKernelGGL((k_linkage_fast<unsigned short, false>), dim3(1), dim3(LF_T), lds, st, s.S, ld, n, Z, s.nb0,
+                       s.mind0, s.g_size, s.g_cid, s.mail, 1, SL, poll_limit, s.status, stats);
   } else {
     const size_t lds = (size_t)SL * LF_T * 16;
     if (lds > LF_LDS_MAX) return 0;   // (status stays "not run": the heap kernel does the work)
     (void)hipFuncSetAttribute((const void*)k_linkage_fast<unsigned int, true>,
                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)LF_LDS_MAX);
-    hipLaunchKernelGGL((k_linkage_fast<unsigned int, true>), dim3(8 * G), dim3(LF_T), lds, st, S, ld, n, Z, nb0, mind0,
-                       g_size, g_cid, mail, G, SL, poll_limit, status, stats);
+    hipLaunchKernelGGL((k_linkage_fast<unsigned int, true>), dim3(8 * G), dim3(LF_T), lds, st, s.S, ld, n, Z, s.nb0,
+                       s.mind0, s.g_size, s.g_cid, s.mail, G, SL, poll_limit, s.status, stats);
   }
   return 0;
 }

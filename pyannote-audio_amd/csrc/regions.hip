@@ -211,26 +211,23 @@ __global__ __launch_bounds__(RG_THREADS) void k_regions_finish(int K, RegionPara
   if (tid == 0) counts[k] = n3;
 }
 
+// The workspace of pa_binarize_regions in 256-byte-aligned blocks
 struct RegionWorkspace {
-  double* raw;
-  uint32_t *tile_map, *state_in, *events;
-  int *chunk_cnt, *chunk_off, *n_raw;
-  size_t bytes;
+  double* raw;                              // (K, capacity, 2)
+  uint32_t *tile_map, *state_in, *events;   // (ntiles), (ntiles), (T)
+  int *chunk_cnt, *chunk_off, *n_raw;       // (K, nchunks) each, (RG_MAXK)
 };
 
-static RegionWorkspace region_workspace(void* base, int T, int K, int capacity) {
+static RegionWorkspace region_workspace(Carver& c, int T, int K, int capacity) {
   const size_t ntiles = cdiv(T, RG_TILE), nchunks = cdiv(T, RG_CHUNK);
-  auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
-  char* p = (char*)base;
   RegionWorkspace w;
-  w.raw = (double*)p;         p += up(sizeof(double) * 2 * (size_t)K * capacity);
-  w.tile_map = (uint32_t*)p;  p += up(4 * ntiles);
-  w.state_in = (uint32_t*)p;  p += up(4 * ntiles);
-  w.events = (uint32_t*)p;    p += up(4 * (size_t)T);
-  w.chunk_cnt = (int*)p;      p += up(4 * (size_t)K * nchunks);
-  w.chunk_off = (int*)p;      p += up(4 * (size_t)K * nchunks);
-  w.n_raw = (int*)p;          p += up(4 * RG_MAXK);
-  w.bytes = (size_t)(p - (char*)base);
+  w.raw = c.take<double>(2 * (size_t)K * capacity);
+  w.tile_map = c.take<uint32_t>(ntiles);
+  w.state_in = c.take<uint32_t>(ntiles);
+  w.events = c.take<uint32_t>(T);
+  w.chunk_cnt = c.take<int>((size_t)K * nchunks);
+  w.chunk_off = c.take<int>((size_t)K * nchunks);
+  w.n_raw = c.take<int>(RG_MAXK);
   return w;
 }
 
@@ -240,7 +237,7 @@ extern "C" {
 
 size_t pa_binarize_regions_workspace_bytes(int T, int K, int capacity) {
   if (T < 2 || K <= 0 || K > pa::RG_MAXK || capacity < 0) return 0;
-  return pa::region_workspace(nullptr, T, K, capacity).bytes;
+  return pa::carved_bytes([&](pa::Carver& c) { pa::region_workspace(c, T, K, capacity); });
 }
 
 int pa_binarize_regions(const float* scores, int T, int K, const float* onset, const float* offset,
@@ -260,9 +257,10 @@ int pa_binarize_regions(const float* scores, int T, int K, const float* onset, c
     return 0;
   }
   PA_REQUIRE(scores && (regions || capacity == 0), "pa_binarize_regions: null scores / regions");
-  const pa::RegionWorkspace w = pa::region_workspace(workspace, T, K, capacity);
-  PA_REQUIRE(workspace && workspace_bytes >= w.bytes, "pa_binarize_regions: workspace of %zu bytes, %zu needed",
-             workspace_bytes, w.bytes);
+  pa::Carver carver(workspace);
+  const pa::RegionWorkspace w = pa::region_workspace(carver, T, K, capacity);
+  PA_REQUIRE(workspace && workspace_bytes >= carver.bytes(), "pa_binarize_regions: workspace of %zu bytes, %zu needed",
+             workspace_bytes, carver.bytes());
   pa::RegionParams p;
   for (int k = 0; k < pa::RG_MAXK; ++k) {
     p.onset[k] = k < K ? onset[k] : 0.f;

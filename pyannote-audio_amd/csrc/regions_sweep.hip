@@ -306,35 +306,42 @@ __global__ __launch_bounds__(RG_THREADS) void k_sweep_remove(const SweepJob* __r
 }
 
 // ------------------------------------------------------------------------------------------------ host side
-static size_t sw_up(size_t b) { return (b + 255) & ~(size_t)255; }
-
-// what one group of a launch batch needs: tile maps, entry states, event words, chunk counts and offsets
-static size_t sweep_group_bytes(int T) {
-  const size_t ntiles = cdiv(T, RG_TILE), nchunks = cdiv(T, RG_CHUNK);
-  return 2 * sw_up(4 * ntiles) + sw_up(4 * (size_t)T) + 2 * sw_up(4 * RG_MAXK * nchunks);
-}
-
-// what does not depend on the batch: group table, per-lane tables, the three row buffers, per-job tables
-static size_t sweep_fixed_bytes(int groups, int L, int M, long raw_rows, long job_rows) {
-  return 256 + sw_up(sizeof(SweepGroup) * (size_t)groups) + 3 * sw_up(4 * ((size_t)L + 1)) +
-         2 * sw_up(16 * (size_t)raw_rows) + sw_up(sizeof(SweepJob) * (size_t)M) + 2 * sw_up(4 * ((size_t)M + 1)) +
-         sw_up(16 * (size_t)job_rows);
-}
-
-struct SweepBatch {
-  uint32_t *tile_map, *state_in, *events;
+// The workspace of pa_regions_sweep_count / _emit in 256-byte-aligned blocks behind 256 bytes of slack (the caller's
+// pointer need not be aligned).  First what does not depend on the launch batch (the counting phase passes M =
+// raw_rows = job_rows = 0), then the arrays of a batch of `per` groups, a group's share of each rounded up to 256
+// bytes: fixed + per * each bytes in all.
+struct SweepWorkspace {
+  SweepGroup* groups;
+  int *n_raw, *raw_off, *n_clean;   // (L + 1) each
+  double *raw, *clean;              // (raw_rows, 2) each
+  SweepJob* jobs;
+  int *n_merged, *counts;           // (M + 1) each
+  double* scratch;                  // (job_rows, 2)
+  uint32_t *tile_map, *state_in, *events;   // the batch
   int *chunk_cnt, *chunk_off;
 };
-
-static SweepBatch sweep_batch(char* p, int T, int groups) {
+static SweepWorkspace sweep_layout(Carver& c, int T, int groups, int per, int L, int M, long raw_rows, long job_rows) {
   const size_t ntiles = cdiv(T, RG_TILE), nchunks = cdiv(T, RG_CHUNK);
-  SweepBatch b;
-  b.tile_map = (uint32_t*)p;  p += groups * sw_up(4 * ntiles);
-  b.state_in = (uint32_t*)p;  p += groups * sw_up(4 * ntiles);
-  b.events = (uint32_t*)p;    p += groups * sw_up(4 * (size_t)T);
-  b.chunk_cnt = (int*)p;      p += groups * sw_up(4 * RG_MAXK * nchunks);
-  b.chunk_off = (int*)p;
-  return b;
+  SweepWorkspace w;
+  w.groups = c.take<SweepGroup>(groups);
+  w.n_raw = c.take<int>((size_t)L + 1);
+  w.raw_off = c.take<int>((size_t)L + 1);
+  w.n_clean = c.take<int>((size_t)L + 1);
+  w.raw = c.take<double>(2 * (size_t)raw_rows);
+  w.clean = c.take<double>(2 * (size_t)raw_rows);
+  w.jobs = c.take<SweepJob>(M);
+  w.n_merged = c.take<int>((size_t)M + 1);
+  w.counts = c.take<int>((size_t)M + 1);
+  w.scratch = c.take<double>(2 * (size_t)job_rows);
+  w.tile_map = c.take<uint32_t>(per * align_up(4 * ntiles) / 4);
+  w.state_in = c.take<uint32_t>(per * align_up(4 * ntiles) / 4);
+  w.events = c.take<uint32_t>(per * align_up(4 * (size_t)T) / 4);
+  w.chunk_cnt = c.take<int>(per * align_up(4 * RG_MAXK * nchunks) / 4);
+  w.chunk_off = c.take<int>(per * align_up(4 * RG_MAXK * nchunks) / 4);
+  return w;
+}
+static size_t sweep_bytes(int T, int groups, int per, int L, int M, long raw_rows, long job_rows) {
+  return carved_bytes([&](Carver& c) { sweep_layout(c, T, groups, per, L, M, raw_rows, job_rows); }, 256);
 }
 
 // lanes of one class, in lane order, sixteen to a group; classes in ascending order.  false: a class out of range
@@ -374,23 +381,22 @@ static int sweep_check_lanes(const char* who, int T, int K, int L, const int32_t
   return 0;
 }
 
-// the launches of one batch of `n` groups starting at group `g0`; `raw` NULL: counting only
-static void sweep_launch_batch(hipStream_t s, const float* scores, int T, int K, const SweepGroup* d_groups, int g0,
-                               int n, const SweepBatch& b, int* d_n_raw, double start, double duration, double step,
-                               const int* d_raw_off, double* raw, double* clean, int* d_n_clean) {
+// the launches of one batch of `n` groups starting at group `g0`; `emit` false: counting only
+static void sweep_launch_batch(hipStream_t s, const float* scores, int T, int K, const SweepWorkspace& w, int g0,
+                               int n, bool emit, double start, double duration, double step) {
   const int ntiles = cdiv(T, RG_TILE), nchunks = cdiv(T, RG_CHUNK);
-  const SweepGroup* g = d_groups + g0;
-  hipLaunchKernelGGL(k_sweep_reduce, dim3(ntiles, n), dim3(RG_THREADS), 0, s, scores, T, K, g, ntiles, b.tile_map);
-  hipLaunchKernelGGL(k_sweep_scan, dim3(n), dim3(64), 0, s, b.tile_map, ntiles, b.state_in);
-  hipLaunchKernelGGL(k_sweep_apply, dim3(ntiles, n), dim3(RG_THREADS), 0, s, scores, T, K, g, ntiles, b.state_in,
-                     raw ? b.events : nullptr, b.chunk_cnt, nchunks);
-  hipLaunchKernelGGL(k_sweep_offsets, dim3(n), dim3(64 * RG_MAXK), 0, s, g, b.chunk_cnt, nchunks, b.chunk_off,
-                     d_n_raw);
-  if (!raw) return;
-  hipLaunchKernelGGL(k_sweep_emit, dim3(cdiv(T, RG_THREADS), n), dim3(RG_THREADS), 0, s, b.events, T, g, start,
-                     duration, step, b.chunk_off, nchunks, d_raw_off, raw);
-  hipLaunchKernelGGL(k_sweep_clean, dim3(n * RG_MAXK), dim3(RG_THREADS), 0, s, g, d_n_raw, d_raw_off, raw, clean,
-                     d_n_clean);
+  const SweepGroup* g = w.groups + g0;
+  hipLaunchKernelGGL(k_sweep_reduce, dim3(ntiles, n), dim3(RG_THREADS), 0, s, scores, T, K, g, ntiles, w.tile_map);
+  hipLaunchKernelGGL(k_sweep_scan, dim3(n), dim3(64), 0, s, w.tile_map, ntiles, w.state_in);
+  hipLaunchKernelGGL(k_sweep_apply, dim3(ntiles, n), dim3(RG_THREADS), 0, s, scores, T, K, g, ntiles, w.state_in,
+                     emit ? w.events : nullptr, w.chunk_cnt, nchunks);
+  hipLaunchKernelGGL(k_sweep_offsets, dim3(n), dim3(64 * RG_MAXK), 0, s, g, w.chunk_cnt, nchunks, w.chunk_off,
+                     w.n_raw);
+  if (!emit) return;
+  hipLaunchKernelGGL(k_sweep_emit, dim3(cdiv(T, RG_THREADS), n), dim3(RG_THREADS), 0, s, w.events, T, g, start,
+                     duration, step, w.chunk_off, nchunks, w.raw_off, w.raw);
+  hipLaunchKernelGGL(k_sweep_clean, dim3(n * RG_MAXK), dim3(RG_THREADS), 0, s, g, w.n_raw, w.raw_off, w.raw, w.clean,
+                     w.n_clean);
 }
 
 }  // namespace pa
@@ -412,8 +418,7 @@ int pa_regions_sweep_groups(int K, int L, const int32_t* lane_class) {
 size_t pa_regions_sweep_workspace_bytes(int T, int groups, int groups_per_launch, int L, int M, long raw_rows,
                                         long job_rows) {
   if (T < 2 || groups < 0 || groups_per_launch < 0 || L < 0 || M < 0 || raw_rows < 0 || job_rows < 0) return 0;
-  return pa::sweep_fixed_bytes(groups, L, M, raw_rows, job_rows) +
-         (size_t)groups_per_launch * pa::sweep_group_bytes(T);
+  return pa::sweep_bytes(T, groups, groups_per_launch, L, M, raw_rows, job_rows);
 }
 
 int pa_regions_sweep_count(const float* scores, int T, int K, int L, const int32_t* lane_class, const float* onset,
@@ -429,16 +434,16 @@ int pa_regions_sweep_count(const float* scores, int T, int K, int L, const int32
   std::vector<pa::SweepGroup> groups;
   pa::sweep_plan(K, L, lane_class, onset, offset, &groups);
   const int G = (int)groups.size();
-  const size_t fixed = pa::sweep_fixed_bytes(G, L, 0, 0, 0), each = pa::sweep_group_bytes(T);
+  const size_t fixed = pa::sweep_bytes(T, G, 0, L, 0, 0, 0), each = pa::sweep_bytes(T, G, 1, L, 0, 0, 0) - fixed;
   PA_REQUIRE(workspace && workspace_bytes >= fixed + each, "%s: workspace of %zu bytes, at least %zu needed", who,
              workspace_bytes, fixed + each);
   const int per = (int)std::min<size_t>(std::min(G, 65535), (workspace_bytes - fixed) / each);   // (grid.y)
   hipStream_t s = (hipStream_t)stream;
-  char* p = (char*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
-  pa::SweepGroup* d_groups = (pa::SweepGroup*)p;  p += pa::sw_up(sizeof(pa::SweepGroup) * (size_t)G);
-  int* d_n_raw = (int*)p;                         p += 3 * pa::sw_up(4 * ((size_t)L + 1));
-  const pa::SweepBatch b = pa::sweep_batch(p, T, per);
-  if (hipMemcpyAsync(d_groups, groups.data(), sizeof(pa::SweepGroup) * (size_t)G, hipMemcpyHostToDevice, s) !=
+  pa::Carver carver(workspace, 256);
+  const pa::SweepWorkspace w = pa::sweep_layout(carver, T, G, per, L, 0, 0, 0);
+  PA_REQUIRE(workspace_bytes >= carver.bytes(), "%s: workspace of %zu bytes, %zu needed", who, workspace_bytes,
+             carver.bytes());
+  if (hipMemcpyAsync(w.groups, groups.data(), sizeof(pa::SweepGroup) * (size_t)G, hipMemcpyHostToDevice, s) !=
       hipSuccess) {
     pa::set_error("%s: uploading the lane tables failed", who);
     return 1;
@@ -446,14 +451,13 @@ int pa_regions_sweep_count(const float* scores, int T, int K, int L, const int32
   {
     pa::ProfScope prof("k_regions_sweep_count", stream, 4.0 * T * G * 16, 12.0 * T * G);
     for (int g0 = 0; g0 < G; g0 += per) {
-      pa::sweep_launch_batch(s, scores, T, K, d_groups, g0, std::min(per, G - g0), b, d_n_raw, 0.0, 0.0, 0.0, nullptr,
-                             nullptr, nullptr, nullptr);
+      pa::sweep_launch_batch(s, scores, T, K, w, g0, std::min(per, G - g0), false, 0.0, 0.0, 0.0);
       PA_CHECK_LAUNCH(who);
       if (launches) ++*launches;
     }
   }
   // the one read-back the row buffers are sized from (it also keeps `groups` alive until the upload has happened)
-  if (hipMemcpyAsync(n_raw, d_n_raw, sizeof(int32_t) * (size_t)L, hipMemcpyDeviceToHost, s) != hipSuccess ||
+  if (hipMemcpyAsync(n_raw, w.n_raw, sizeof(int32_t) * (size_t)L, hipMemcpyDeviceToHost, s) != hipSuccess ||
       hipStreamSynchronize(s) != hipSuccess) {
     pa::set_error("%s: reading the region counts back failed: %s", who, hipGetErrorString(hipGetLastError()));
     return 1;
@@ -507,41 +511,33 @@ int pa_regions_sweep_emit(const float* scores, int T, int K, int L, const int32_
   std::vector<pa::SweepGroup> groups;
   pa::sweep_plan(K, L, lane_class, onset, offset, &groups);
   const int G = (int)groups.size();
-  const size_t fixed = pa::sweep_fixed_bytes(G, L, M, raw_rows, job_rows), each = pa::sweep_group_bytes(T);
+  const size_t fixed = pa::sweep_bytes(T, G, 0, L, M, raw_rows, job_rows),
+               each = pa::sweep_bytes(T, G, 1, L, M, raw_rows, job_rows) - fixed;
   PA_REQUIRE(workspace && workspace_bytes >= fixed + each, "%s: workspace of %zu bytes, at least %zu needed", who,
              workspace_bytes, fixed + each);
   const int per = (int)std::min<size_t>(std::min(G, 65535), (workspace_bytes - fixed) / each);   // (grid.y)
-  char* p = (char*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
-  pa::SweepGroup* d_groups = (pa::SweepGroup*)p;  p += pa::sw_up(sizeof(pa::SweepGroup) * (size_t)G);
-  int* d_n_raw = (int*)p;                         p += pa::sw_up(4 * ((size_t)L + 1));
-  int* d_raw_off = (int*)p;                       p += pa::sw_up(4 * ((size_t)L + 1));
-  int* d_n_clean = (int*)p;                       p += pa::sw_up(4 * ((size_t)L + 1));
-  double* raw = (double*)p;                       p += pa::sw_up(16 * (size_t)raw_rows);
-  double* clean = (double*)p;                     p += pa::sw_up(16 * (size_t)raw_rows);
-  pa::SweepJob* d_jobs = (pa::SweepJob*)p;        p += pa::sw_up(sizeof(pa::SweepJob) * (size_t)M);
-  int* d_n_merged = (int*)p;                      p += pa::sw_up(4 * ((size_t)M + 1));
-  int* d_counts = (int*)p;                        p += pa::sw_up(4 * ((size_t)M + 1));
-  double* scratch = (double*)p;                   p += pa::sw_up(16 * (size_t)job_rows);
-  const pa::SweepBatch b = pa::sweep_batch(p, T, per);
-  if (hipMemcpyAsync(d_groups, groups.data(), sizeof(pa::SweepGroup) * (size_t)G, hipMemcpyHostToDevice, s) !=
+  pa::Carver carver(workspace, 256);
+  const pa::SweepWorkspace w = pa::sweep_layout(carver, T, G, per, L, M, raw_rows, job_rows);
+  PA_REQUIRE(workspace_bytes >= carver.bytes(), "%s: workspace of %zu bytes, %zu needed", who, workspace_bytes,
+             carver.bytes());
+  if (hipMemcpyAsync(w.groups, groups.data(), sizeof(pa::SweepGroup) * (size_t)G, hipMemcpyHostToDevice, s) !=
           hipSuccess ||
-      hipMemcpyAsync(d_raw_off, raw_off.data(), 4 * ((size_t)L + 1), hipMemcpyHostToDevice, s) != hipSuccess ||
-      hipMemcpyAsync(d_jobs, jobs.data(), sizeof(pa::SweepJob) * (size_t)M, hipMemcpyHostToDevice, s) != hipSuccess) {
+      hipMemcpyAsync(w.raw_off, raw_off.data(), 4 * ((size_t)L + 1), hipMemcpyHostToDevice, s) != hipSuccess ||
+      hipMemcpyAsync(w.jobs, jobs.data(), sizeof(pa::SweepJob) * (size_t)M, hipMemcpyHostToDevice, s) != hipSuccess) {
     pa::set_error("%s: uploading the lane and job tables failed", who);
     return 1;
   }
   {
     pa::ProfScope prof("k_regions_sweep_emit", stream, 4.0 * T * G * 16, 16.0 * T * G + 48.0 * job_rows);
     for (int g0 = 0; g0 < G; g0 += per) {
-      pa::sweep_launch_batch(s, scores, T, K, d_groups, g0, std::min(per, G - g0), b, d_n_raw, start, duration, step,
-                             d_raw_off, raw, clean, d_n_clean);
+      pa::sweep_launch_batch(s, scores, T, K, w, g0, std::min(per, G - g0), true, start, duration, step);
       PA_CHECK_LAUNCH(who);
       if (launches) ++*launches;
     }
-    hipLaunchKernelGGL(pa::k_sweep_merge, dim3(M), dim3(pa::RG_THREADS), 0, s, d_jobs, d_n_clean, d_raw_off, clean,
-                       scratch, d_n_merged, d_counts);
-    hipLaunchKernelGGL(pa::k_sweep_job_offsets, dim3(1), dim3(64), 0, s, d_counts, M, job_off);
-    hipLaunchKernelGGL(pa::k_sweep_remove, dim3(M), dim3(pa::RG_THREADS), 0, s, d_jobs, scratch, d_n_merged, job_off,
+    hipLaunchKernelGGL(pa::k_sweep_merge, dim3(M), dim3(pa::RG_THREADS), 0, s, w.jobs, w.n_clean, w.raw_off, w.clean,
+                       w.scratch, w.n_merged, w.counts);
+    hipLaunchKernelGGL(pa::k_sweep_job_offsets, dim3(1), dim3(64), 0, s, w.counts, M, job_off);
+    hipLaunchKernelGGL(pa::k_sweep_remove, dim3(M), dim3(pa::RG_THREADS), 0, s, w.jobs, w.scratch, w.n_merged, job_off,
                        (int)std::min<long>(rows, 0x7fffffffL), regions, tracks);
     PA_CHECK_LAUNCH(who);
   }

@@ -320,6 +320,41 @@ __global__ __launch_bounds__(VB_T) void k_vbx_batch_elbo(VbxBatch b, int it, dou
   }
 }
 
+// The workspace of pa_vbx_iteration: the arrays back to back and 64 spare bytes
+struct VbxFile {
+  double *rho, *G, *logpx, *alpha, *invL, *Nk, *cterm, *eterm;   // (n, d), (n), (n), (s, d) x 2, (s) x 3
+};
+static VbxFile vbx_file_layout(Carver& c, int n, int s, int d) {
+  const size_t N = n, S = s, D = d, packed = sizeof(double);
+  VbxFile f;
+  f.rho = c.take<double>(N * D, packed);
+  f.G = c.take<double>(N, packed);
+  f.logpx = c.take<double>(N, packed);
+  f.alpha = c.take<double>(S * D, packed);
+  f.invL = c.take<double>(S * D, packed);
+  f.Nk = c.take<double>(S, packed);
+  f.cterm = c.take<double>(S, packed);
+  f.eterm = c.take<double>(S, packed);
+  c.take<char>(64, packed);
+  return f;
+}
+
+// The workspace of pa_vbx_run_batch in 256-byte-aligned blocks: rho and G, shared by the jobs, in one block; then per
+// array the slabs of all jobs, at the common stride of the largest S of the call; the `done` flags last.  Fills the
+// workspace pointers of `b` and returns rho; G follows its n x d doubles.
+static double* vbx_batch_layout(Carver& c, int jobs, int n, int smax, int d, VbxBatch& b) {
+  const size_t J = jobs, N = n, S = smax, D = d;
+  double* rho = c.take<double>(N * D + N);
+  b.logpx = c.take<double>(J * N);
+  b.alpha = c.take<double>(J * S * D);
+  b.invL = c.take<double>(J * S * D);
+  b.Nk = c.take<double>(J * S);
+  b.cterm = c.take<double>(J * S);
+  b.eterm = c.take<double>(J * S);
+  b.done = c.take<int>(J);
+  return rho;
+}
+
 }  // namespace pa
 
 extern "C" {
@@ -338,8 +373,7 @@ int pa_plda_transform(const float* X, int n, int din, int dmid, int dout, const 
 }
 
 size_t pa_vbx_workspace_bytes(int n, int s, int d) {
-  // rho (n d) + G (n) + logpx (n) + alpha, invL (s d each) + Nk, cterm, eterm (s each)
-  return 8 * ((size_t)n * d + 2 * (size_t)n + 2 * (size_t)s * d + 3 * (size_t)s) + 64;
+  return pa::carved_bytes([&](pa::Carver& c) { pa::vbx_file_layout(c, n, s, d); });
 }
 
 // One VB iteration (utils/vbx.py:106-133) on device buffers.  `gamma` (n, s) is read by the M step and
@@ -349,39 +383,26 @@ int pa_vbx_iteration(const double* fea, const double* Phi, int n, int s, int d, 
                      int first, double* gamma, double* elbo_out, void* workspace, size_t workspace_bytes,
                      void* stream) {
   if (n <= 0 || s <= 0) return 0;
-  PA_REQUIRE(workspace_bytes >= pa_vbx_workspace_bytes(n, s, d), "pa_vbx_iteration: workspace too small");
+  pa::Carver carver(workspace);
+  const pa::VbxFile f = pa::vbx_file_layout(carver, n, s, d);
+  PA_REQUIRE(workspace_bytes >= carver.bytes(), "pa_vbx_iteration: workspace too small");
   PA_REQUIRE((size_t)(d + s) * 8 <= 64 * 1024, "pa_vbx_iteration: too many clusters for one workgroup");
-  double* w = (double*)workspace;
-  double* rho = w;
-  double* G = rho + (size_t)n * d;
-  double* logpx = G + n;
-  double* alpha = logpx + n;
-  double* invL = alpha + (size_t)s * d;
-  double* Nk = invL + (size_t)s * d;
-  double* cterm = Nk + s;
-  double* eterm = cterm + s;
   hipStream_t st = (hipStream_t)stream;
   pa::ProfScope prof("k_vbx_iteration", stream, 4.0 * n * (double)s * d, 8.0 * (2.0 * n * s + 2.0 * n * d));
-  if (first) hipLaunchKernelGGL(pa::k_vbx_prepare, dim3(n), dim3(pa::VB_T), 0, st, fea, n, d, Phi, rho, G);
-  hipLaunchKernelGGL(pa::k_vbx_mstep, dim3(s), dim3(pa::VB_T), (size_t)(pa::VB_T / 128) * d * 8, st, gamma, rho, n,
-                     s, d, Phi, Fa / Fb, alpha,
-                     invL, Nk, cterm, eterm);
-  hipLaunchKernelGGL(pa::k_vbx_estep, dim3(n), dim3(pa::VB_T), (size_t)(d + s) * 8, st, rho, alpha, cterm, G, Nk,
-                     first, n, s, d, Fa, gamma, logpx);
-  hipLaunchKernelGGL(pa::k_vbx_elbo, dim3(1), dim3(pa::VB_T), 0, st, logpx, n, eterm, s, Fb, elbo_out);
+  if (first) hipLaunchKernelGGL(pa::k_vbx_prepare, dim3(n), dim3(pa::VB_T), 0, st, fea, n, d, Phi, f.rho, f.G);
+  hipLaunchKernelGGL(pa::k_vbx_mstep, dim3(s), dim3(pa::VB_T), (size_t)(pa::VB_T / 128) * d * 8, st, gamma, f.rho, n,
+                     s, d, Phi, Fa / Fb, f.alpha, f.invL, f.Nk, f.cterm, f.eterm);
+  hipLaunchKernelGGL(pa::k_vbx_estep, dim3(n), dim3(pa::VB_T), (size_t)(d + s) * 8, st, f.rho, f.alpha, f.cterm, f.G,
+                     f.Nk, first, n, s, d, Fa, gamma, f.logpx);
+  hipLaunchKernelGGL(pa::k_vbx_elbo, dim3(1), dim3(pa::VB_T), 0, st, f.logpx, n, f.eterm, s, Fb, elbo_out);
   PA_CHECK_LAUNCH("pa_vbx_iteration");
   return 0;
 }
 
-static size_t vbx_align(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
-
 size_t pa_vbx_batch_workspace_bytes(int jobs, int n, int smax, int d) {
   if (jobs <= 0 || n <= 0 || smax <= 0 || d <= 0) return 0;
-  const size_t J = (size_t)jobs;
-  // shared: rho (n d) + G (n); per job: logpx (n) + alpha, invL (smax d each) + Nk, cterm, eterm (smax each)
-  // + its `done` flag
-  return vbx_align(8 * ((size_t)n * d + n)) + vbx_align(8 * J * n) + 2 * vbx_align(8 * J * smax * d) +
-         3 * vbx_align(8 * J * smax) + vbx_align(J * sizeof(int));
+  pa::VbxBatch b;
+  return pa::carved_bytes([&](pa::Carver& c) { pa::vbx_batch_layout(c, jobs, n, smax, d, b); });
 }
 
 // Whole VB inferences of `jobs` jobs over the same features `fea` (n, d), no read-back and no host
@@ -401,25 +422,11 @@ int pa_vbx_run_batch(const double* fea, const double* Phi, int n, int d, int job
   PA_REQUIRE(jobs <= 65535 && max_iterations >= 1, "pa_vbx_run_batch: bad job or iteration count");
   PA_REQUIRE(smax >= 1 && (size_t)(d + smax) * 8 <= 64 * 1024,
              "pa_vbx_run_batch: too many clusters for one workgroup");
-  PA_REQUIRE(workspace_bytes >= pa_vbx_batch_workspace_bytes(jobs, n, smax, d),
-             "pa_vbx_run_batch: workspace too small");
-  const size_t J = (size_t)jobs;
-  char* w = (char*)workspace;
-  auto take = [&](size_t bytes) {
-    char* p = w;
-    w += vbx_align(bytes);
-    return p;
-  };
-  double* rho = (double*)take(8 * ((size_t)n * d + n));
-  double* G = rho + (size_t)n * d;
+  pa::Carver carver(workspace);
   pa::VbxBatch b;
-  b.logpx = (double*)take(8 * J * n);
-  b.alpha = (double*)take(8 * J * smax * d);
-  b.invL = (double*)take(8 * J * smax * d);
-  b.Nk = (double*)take(8 * J * smax);
-  b.cterm = (double*)take(8 * J * smax);
-  b.eterm = (double*)take(8 * J * smax);
-  b.done = (int*)take(J * sizeof(int));
+  double* rho = pa::vbx_batch_layout(carver, jobs, n, smax, d, b);
+  double* G = rho + (size_t)n * d;
+  PA_REQUIRE(workspace_bytes >= carver.bytes(), "pa_vbx_run_batch: workspace too small");
   b.job_init = job_init;
   b.job_f = job_f;
   b.gamma0_len = gamma0_len;

@@ -321,12 +321,6 @@ __global__ void k_det_finish(const DetHeader* __restrict__ head, long T, const i
   status[6] = pair_hi(head->totals);
 }
 
-__global__ __launch_bounds__(128) void k_trial_norms_f64(const double* __restrict__ E, int N, int D,
-                                                         double* __restrict__ nrm) {
-  const int i = blockIdx.x * 128 + threadIdx.x;
-  if (i < N) nrm[i] = row_norm_f64(E + (long)i * D, D);
-}
-
 // one thread per trial: the whole dot product in dot2way's order
 __global__ __launch_bounds__(128) void k_trial_cosine_f64(const double* __restrict__ E, int D,
                                                           const double* __restrict__ nrm,
@@ -339,36 +333,30 @@ __global__ __launch_bounds__(128) void k_trial_cosine_f64(const double* __restri
   out[t] = cosine_distance_f64(dot2way(E + (long)i * D, E + (long)j * D, D), nrm[i], nrm[j]);
 }
 
+// The workspace of pa_det_curve_f64 in 256-byte-aligned blocks
 struct DetLayout {
   int nb, nc;
-  size_t head, block_sums, chunk_sums, group_end, group_tps, bytes;
+  DetHeader* head;
+  pair64 *block_sums, *chunk_sums;   // (nb), (nc)
+  uint32_t *group_end, *group_tps;   // (T) each
 };
-static DetLayout det_layout(long T) {
+static DetLayout det_layout(Carver& c, long T) {
   DetLayout l;
   l.nb = cdiv(T, DET_BLOCK);
   l.nc = cdiv(l.nb, DET_CHUNK);
-  size_t at = 0;
-  auto take = [&](size_t n) {
-    const size_t here = at;
-    at += (n + 255) / 256 * 256;
-    return here;
-  };
-  l.head = take(sizeof(DetHeader));
-  l.block_sums = take(sizeof(pair64) * (size_t)l.nb);
-  l.chunk_sums = take(sizeof(pair64) * (size_t)l.nc);
-  l.group_end = take(sizeof(uint32_t) * (size_t)T);
-  l.group_tps = take(sizeof(uint32_t) * (size_t)T);
-  l.bytes = at;
+  l.head = c.take<DetHeader>(1);
+  l.block_sums = c.take<pair64>(l.nb);
+  l.chunk_sums = c.take<pair64>(l.nc);
+  l.group_end = c.take<uint32_t>(T);
+  l.group_tps = c.take<uint32_t>(T);
   return l;
 }
 
 // exclusive scan of ws.block_sums in place (launch 2 of the header comment); the grand total goes to *total_out
-static void det_scan(const DetLayout& l, char* ws, pair64* total_out, hipStream_t s) {
-  pair64* block_sums = (pair64*)(ws + l.block_sums);
-  pair64* chunk_sums = (pair64*)(ws + l.chunk_sums);
-  hipLaunchKernelGGL(k_det_chunk_sums, dim3(l.nc), dim3(DET_THREADS), 0, s, block_sums, l.nb, chunk_sums);
-  hipLaunchKernelGGL(k_det_scan_top, dim3(1), dim3(DET_THREADS), 0, s, chunk_sums, l.nc, total_out);
-  hipLaunchKernelGGL(k_det_scan_chunks, dim3(l.nc), dim3(DET_THREADS), 0, s, block_sums, l.nb, chunk_sums);
+static void det_scan(const DetLayout& l, pair64* total_out, hipStream_t s) {
+  hipLaunchKernelGGL(k_det_chunk_sums, dim3(l.nc), dim3(DET_THREADS), 0, s, l.block_sums, l.nb, l.chunk_sums);
+  hipLaunchKernelGGL(k_det_scan_top, dim3(1), dim3(DET_THREADS), 0, s, l.chunk_sums, l.nc, total_out);
+  hipLaunchKernelGGL(k_det_scan_chunks, dim3(l.nc), dim3(DET_THREADS), 0, s, l.block_sums, l.nb, l.chunk_sums);
 }
 
 }  // namespace pa
@@ -384,7 +372,7 @@ int pa_trial_cosine_f64(const double* E, int N, int D, const int32_t* idx1, cons
   hipStream_t s = (hipStream_t)stream;
   pa::ProfScope prof("k_trial_cosine_f64", stream, 2.0 * D * ((double)T + N),
                      8.0 * (double)N * D + 8.0 * N + 16.0 * (double)T);
-  hipLaunchKernelGGL(pa::k_trial_norms_f64, dim3(pa::cdiv(N, 128)), dim3(128), 0, s, E, N, D, norms_scratch);
+  pa_row_norms_f64(E, N, D, norms_scratch, stream);
   hipLaunchKernelGGL(pa::k_trial_cosine_f64, dim3(pa::cdiv(T, 128)), dim3(128), 0, s, E, D, norms_scratch, idx1,
                      idx2, T, out);
   PA_CHECK_LAUNCH("pa_trial_cosine_f64");
@@ -396,7 +384,7 @@ int pa_det_scan_chunk(void) { return pa::DET_CHUNK; }
 
 size_t pa_det_workspace_bytes(long T) {
   if (T < 1 || T > pa::DET_MAX_T) return 0;
-  return pa::det_layout(T).bytes;
+  return pa::carved_bytes([&](pa::Carver& c) { pa::det_layout(c, T); });
 }
 
 int pa_det_curve_f64(const double* sorted_keys, const uint8_t* labels, long T, int negate, int32_t* fps,
@@ -406,15 +394,12 @@ int pa_det_curve_f64(const double* sorted_keys, const uint8_t* labels, long T, i
   PA_REQUIRE(sorted_keys && labels && fps && tps && status && workspace, "pa_det_curve_f64: null array");
   PA_REQUIRE((thresholds != nullptr) == (fpr != nullptr) && (fpr != nullptr) == (fnr != nullptr),
              "pa_det_curve_f64: thresholds, fpr and fnr are given together or not at all");
-  const pa::DetLayout l = pa::det_layout(T);
-  PA_REQUIRE(workspace_bytes >= l.bytes, "pa_det_curve_f64: workspace of %zu bytes, %zu needed", workspace_bytes,
-             l.bytes);
+  pa::Carver carver(workspace);
+  const pa::DetLayout l = pa::det_layout(carver, T);
+  PA_REQUIRE(workspace_bytes >= carver.bytes(), "pa_det_curve_f64: workspace of %zu bytes, %zu needed",
+             workspace_bytes, carver.bytes());
   hipStream_t s = (hipStream_t)stream;
-  char* ws = (char*)workspace;
-  pa::DetHeader* head = (pa::DetHeader*)(ws + l.head);
-  pa::pair64* block_sums = (pa::pair64*)(ws + l.block_sums);
-  uint32_t* group_end = (uint32_t*)(ws + l.group_end);
-  uint32_t* group_tps = (uint32_t*)(ws + l.group_tps);
+  pa::DetHeader* head = l.head;
   // header: counts 0, first_cross (and its padding) all ones; status: all 0
   if (hipMemsetAsync(head, 0, offsetof(pa::DetHeader, first_cross), s) != hipSuccess ||
       hipMemsetAsync(&head->first_cross, 0xff, 8, s) != hipSuccess ||
@@ -424,14 +409,15 @@ int pa_det_curve_f64(const double* sorted_keys, const uint8_t* labels, long T, i
   }
   pa::ProfScope prof("k_det_curve_f64", stream, 0.0, 2.0 * 9.0 * (double)T + 16.0 * (double)T);
   const dim3 grid(l.nb), block(pa::DET_THREADS);
-  hipLaunchKernelGGL(pa::k_det_block_counts, grid, block, 0, s, sorted_keys, labels, T, block_sums,
+  hipLaunchKernelGGL(pa::k_det_block_counts, grid, block, 0, s, sorted_keys, labels, T, l.block_sums,
                      (unsigned long long*)status);
-  pa::det_scan(l, ws, &head->totals, s);
-  hipLaunchKernelGGL(pa::k_det_groups, grid, block, 0, s, sorted_keys, labels, T, block_sums, group_end, group_tps);
-  hipLaunchKernelGGL(pa::k_det_corner_counts, grid, block, 0, s, head, group_end, group_tps, T, block_sums);
-  pa::det_scan(l, ws, &head->kept, s);
-  hipLaunchKernelGGL(pa::k_det_compact, grid, block, 0, s, sorted_keys, T, negate, head, group_end, group_tps,
-                     block_sums, fps, tps, thresholds, fpr, fnr);
+  pa::det_scan(l, &head->totals, s);
+  hipLaunchKernelGGL(pa::k_det_groups, grid, block, 0, s, sorted_keys, labels, T, l.block_sums, l.group_end,
+                     l.group_tps);
+  hipLaunchKernelGGL(pa::k_det_corner_counts, grid, block, 0, s, head, l.group_end, l.group_tps, T, l.block_sums);
+  pa::det_scan(l, &head->kept, s);
+  hipLaunchKernelGGL(pa::k_det_compact, grid, block, 0, s, sorted_keys, T, negate, head, l.group_end, l.group_tps,
+                     l.block_sums, fps, tps, thresholds, fpr, fnr);
   hipLaunchKernelGGL(pa::k_det_finish, dim3(1), dim3(64), 0, s, head, T, fps, tps, status);
   PA_CHECK_LAUNCH("pa_det_curve_f64");
   return 0;

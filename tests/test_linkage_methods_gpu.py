@@ -80,7 +80,9 @@ def test_pdist_cosine_equals_scipy(gpu_device, n, d):
 CASES = {
     "n2": lambda: clustered(2, 16, 2),                      # the degenerate chain
     "n3": lambda: clustered(3, 16, 3),
-    "n65": lambda: clustered(65, 16, 65, dup=6),            # crosses a wave
+    "n63": lambda: clustered(63, 16, 63, dup=6),            # one short of a 64 x 64 tile of the square copy
+    "n65": lambda: clustered(65, 16, 65, dup=6),            # crosses a wave, and a tile edge of the square copy
+    "n129": lambda: clustered(129, 16, 129, dup=12),        # 3 x 3 tiles, the last one a single row and column
     "n1025": lambda: clustered(1025, 32, 1025, dup=40),     # one element more than the workgroup
     "n2500": lambda: clustered(2500, 32, 2500, dup=25),     # several elements per thread, ties across threads and waves
     "identical70": lambda: identical(70, 16, 70),           # every distance equal: only the tie rules decide

@@ -142,10 +142,12 @@ def test_silence_returns_empty(pipeline_dir, gpu_device):
 
 
 @pytest.mark.parametrize("n,d,dup,seed", [(2, 8, 0, 0), (3, 8, 0, 1), (50, 16, 0, 2), (257, 256, 0, 3),
-                                          (200, 16, 60, 4), (1500, 256, 25, 5), (4000, 64, 0, 6)])
+                                          (200, 16, 60, 4), (1500, 256, 25, 5), (4000, 64, 0, 6),
+                                          (63, 16, 0, 7), (65, 16, 0, 8), (129, 16, 0, 9)])
 def test_linkage_centroid_bit_exact_vs_scipy(gpu_device, n, d, dup, seed):
     """pa_pdist_f64 + pa_linkage_centroid_f64 == scipy linkage(pdist(X), "centroid"), including exact
-    ties produced by duplicated rows (same merge order, same float64 heights)."""
+    ties produced by duplicated rows (same merge order, same float64 heights); 63, 65 and 129 points sit on both
+    sides of an edge of the 64 x 64 tiles of the square copy the heap-free merge works on."""
     from scipy.cluster.hierarchy import linkage
     from scipy.spatial.distance import pdist
     from pyannote_audio_amd import distance

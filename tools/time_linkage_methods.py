@@ -3,7 +3,8 @@
 device + download + scipy.cluster.hierarchy.linkage for the Euclidean and "geometric" cases, SciPy alone (pdist
 included) for cosine with a non-geometric method.  n = 7 176 (one audio-hour), d = 256, clustered unit vectors; median
 of 5 after one warm-up; every device result is compared with the host's.
-usage (GPU box): python tools/time_linkage_methods.py [n]      -> profiles/linkage_methods_timing.txt"""
+usage (GPU box): python tools/time_linkage_methods.py [n]      -> profiles/linkage_methods_timing.txt
+LM_DEVICE_ONLY=1 times the device path alone and writes no file (comparing two builds of the library: PA_LIB)."""
 import os, statistics, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
@@ -14,6 +15,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 dev = torch.device("cuda:0")
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 7176
 repeats = int(os.environ.get("LM_REPEATS", "5"))
+device_only = os.environ.get("LM_DEVICE_ONLY") == "1"
 rng = np.random.default_rng(0)
 c = rng.standard_normal((4, 256))
 X = (c[rng.integers(0, 4, n)] + 0.6 * rng.standard_normal((n, 256))).astype(np.float32)
@@ -50,10 +52,15 @@ lines = [f"linkage methods, n = {n}, d = 256, clustered unit vectors; wall time 
 for method, metric in [("single", "cosine"), ("complete", "cosine"), ("average", "cosine"), ("weighted", "cosine"),
                        ("ward", "euclidean"), ("single", "euclidean"), ("average", "euclidean")]:
     t_dev, Z = median_seconds(device_path, method, metric)
+    if device_only:
+        print(f"{method:10s} {metric:10s} {1e3 * t_dev:10.1f}", flush=True)
+        continue
     t_par, Z_ref = median_seconds(parent_path, method, metric)
     lines.append(f"{method:10s} {metric:10s} {1e3 * t_dev:10.1f} {1e3 * t_par:15.1f} {t_par / t_dev:8.1f}x  "
                  f"{np.array_equal(Z, Z_ref)}")
     print(lines[-1], flush=True)
+if device_only:
+    sys.exit(0)
 out = os.path.join(ROOT, "profiles", "linkage_methods_timing.txt")
 with open(out, "w") as fp:
     fp.write("\n".join(lines) + "\n")
