@@ -619,8 +619,12 @@ int pa_topk_binarize(const int32_t* act, const uint8_t* count, int T, int K, int
 /* Soft-score (non-powerset segmentation) forms of the same stages:
  * hysteresis thresholding = `binarize` (utils/signal.py:78-140; pipelines/speaker_diarization.py:599-606):
  * scores (C,F,K) fp32 -> out (C,F,K) uint8; on where score > onset, off where score < offset, unchanged in
- * between, NaN = 0; initial_state 0 / 1, or -1 for `scores[:, 0] >= (onset + offset) / 2`. */
-int pa_binarize_hysteresis(const float* scores, int C, int F, int K, float onset, float offset,
+ * between, NaN = 0; initial_state 0 / 1, or -1 for `scores[:, 0] >= midpoint`.  `midpoint` is the reference's
+ * threshold for that comparison: 0.5 * (onset + offset) formed in double precision from the caller's double
+ * thresholds and rounded once to fp32 (numpy compares fp32 scores with the Python float that way).  It is an argument
+ * because the two fp32 thresholds cannot carry it: 0.5f * (onset + offset) in fp32 is one ulp off for some pairs,
+ * (0.4, 0.3) among them.  Read only when initial_state is -1. */
+int pa_binarize_hysteresis(const float* scores, int C, int F, int K, float onset, float offset, float midpoint,
                            int initial_state, uint8_t* out, void* stream);
 /* out (C,F,K) fp32 = max_{s: hard[c][s]==k} scores[c][f][s], NaN when chunk c has no speaker in cluster k
  * (pipelines/speaker_diarization.py:506-522); overlap-add it with pa_aggregate(skip_average = 1). */

@@ -189,9 +189,13 @@ __global__ __launch_bounds__(256) void k_topk_binarize(const VT* __restrict__ ac
 // Hysteresis thresholding, replaces `binarize` (utils/signal.py:78-140) for non-powerset segmentation
 // models (pipelines/speaker_diarization.py:599-606): per (chunk, class) a state machine over the frames --
 // on where score > onset, off where score < offset, unchanged in between; NaN counts as 0 (nan_to_num).
-// initial: 0 / 1 = given state, -1 = `scores[0] >= (onset + offset) / 2`.  One thread per (chunk, class).
+// initial: 0 / 1 = given state, -1 = `scores[0] >= midpoint`.  The reference forms 0.5 * (onset + offset) on Python
+// doubles and numpy compares the float32 scores with that value rounded ONCE to float32 (utils/signal.py:111);
+// 0.5f * (onset + offset) on the two float32 thresholds is one ulp off for some pairs ((0.4, 0.3) among them), so
+// the caller passes the reference's float32 midpoint in and the kernel only compares.
+// One thread per (chunk, class).
 __global__ __launch_bounds__(256) void k_hysteresis(const float* __restrict__ scores, long rows, int F, int K,
-                                                     float onset, float offset, int initial,
+                                                     float onset, float offset, float midpoint, int initial,
                                                      uint8_t* __restrict__ out) {
   const long r = (long)blockIdx.x * 256 + threadIdx.x;  // r = c * K + k
   if (r >= rows) return;
@@ -201,7 +205,7 @@ __global__ __launch_bounds__(256) void k_hysteresis(const float* __restrict__ sc
   uint8_t* q = out + c * F * K + k;
   float s0 = p[0];
   s0 = s0 != s0 ? 0.f : s0;
-  bool state = initial < 0 ? (s0 >= 0.5f * (onset + offset)) : (initial != 0);
+  bool state = initial < 0 ? (s0 >= midpoint) : (initial != 0);
   for (int f = 0; f < F; ++f) {
     float s = p[(long)f * K];
     s = s != s ? 0.f : s;
@@ -241,13 +245,13 @@ __global__ __launch_bounds__(256) void k_cluster_max(const float* __restrict__ s
 
 extern "C" {
 
-int pa_binarize_hysteresis(const float* scores, int C, int F, int K, float onset, float offset,
+int pa_binarize_hysteresis(const float* scores, int C, int F, int K, float onset, float offset, float midpoint,
                            int initial_state, uint8_t* out, void* stream) {
   if (C <= 0 || F <= 0 || K <= 0) return 0;
   const long rows = (long)C * K;
   pa::ProfScope prof("k_hysteresis", stream, 2.0 * rows * F, 5.0 * rows * F);
   hipLaunchKernelGGL(pa::k_hysteresis, dim3(pa::cdiv(rows, 256)), dim3(256), 0, (hipStream_t)stream, scores,
-                     rows, F, K, onset, offset, initial_state, out);
+                     rows, F, K, onset, offset, midpoint, initial_state, out);
   PA_CHECK_LAUNCH("pa_binarize_hysteresis");
   return 0;
 }

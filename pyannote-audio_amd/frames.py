@@ -419,7 +419,10 @@ def binarize(scores: torch.Tensor, onset: float = 0.5, offset: float | None = No
     C, F, K = x.shape
     out = torch.empty((C, F, K), dtype=torch.uint8, device=x.device)
     init = -1 if initial_state is None else int(bool(initial_state))
-    ffi.check(ffi.load().pa_binarize_hysteresis(ffi.ptr(x), C, F, K, float(onset), float(offset), init,
+    # the reference compares the float32 scores of frame 0 with 0.5 * (onset + offset), a Python float that numpy
+    # rounds once to float32 (utils/signal.py:111); the same product of the float32 thresholds can be one ulp off
+    midpoint = float(np.float32(0.5 * (float(onset) + float(offset))))
+    ffi.check(ffi.load().pa_binarize_hysteresis(ffi.ptr(x), C, F, K, float(onset), float(offset), midpoint, init,
                                                 ffi.ptr(out), ffi.stream()), "pa_binarize_hysteresis")
     return out
 

@@ -34,11 +34,14 @@ def ratio(got, want, rtol=1e-4, atol=1e-5) -> float:
 
 
 class Guarded:
-    """`n` elements of device memory between two guard blocks, everything NaN (0xA5 for uint8) before the kernel runs"""
+    """`n` elements of device memory between two guard blocks, everything NaN (0xA5 for integers) before the kernel
+    runs.  `fill`: another value for "untouched", for outputs whose correct values include the default one (an int32
+    count may be 0xA5, a max over no speaker is NaN); it must be exact in `dtype` and a value no correct result takes."""
 
-    def __init__(self, n: int, device, dtype=torch.float32):
-        self.n, self.dtype = int(n), dtype
-        fill = float("nan") if dtype.is_floating_point else U8_UNTOUCHED
+    def __init__(self, n: int, device, dtype=torch.float32, fill=None):
+        self.n, self.dtype, self.fill = int(n), dtype, fill
+        if fill is None:
+            fill = float("nan") if dtype.is_floating_point else U8_UNTOUCHED
         self.buf = torch.full((self.n + 2 * GUARD,), fill, dtype=dtype, device=device)
 
     @property
@@ -46,6 +49,8 @@ class Guarded:
         return C.c_void_p(self.buf.data_ptr() + GUARD * self.buf.element_size())
 
     def _untouched(self, t):
+        if self.fill is not None:
+            return t == self.fill
         return torch.isnan(t) if self.dtype.is_floating_point else t == U8_UNTOUCHED
 
     def check(self, written=None, what=""):

@@ -6,7 +6,7 @@ import math
 import torch
 
 GUARD = 256            # elements in front of and behind every output
-PATTERN = {torch.float32: 1234.5, torch.uint8: 0xA5}
+PATTERN = {torch.float32: 1234.5, torch.uint8: 0xA5, torch.int32: -0x5A5A5A5A}
 
 
 def altered(struct, **fields):
