@@ -838,6 +838,33 @@ int pa_annot_counts(const double* ref_seg, const int32_t* ref_label, int Nr, int
                     const int32_t* hyp_label, int Nh, int Kh, const double* uem_seg, int Nu, double collar,
                     int skip_overlap, double* out, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- the same sums for W windows of one file in one call (the reference's SlidingDiarizationErrorRate,
+ *      utils/metric.py:245-286, crops and scores every window by itself) ---- */
+
+/* bytes of `ws` below (0: a negative count, or more cuts than the quadratic sort accepts, the 2 W window cuts
+ * included) */
+size_t pa_annot_window_counts_workspace_bytes(int Nr, int Nh, int Nu, int W);
+/* The arrays of pa_annot_counts, and win_seg (W, 2) fp64 start / end on the device.  Windows come in any order; they
+ * may overlap, touch, lie partly or wholly outside the uem, or have zero length.
+ * out, (W, Kr*Kh + Kr + Kh + 7) fp64, overwritten: row w holds, in exact arithmetic, the values pa_annot_counts
+ * defines for (ref, hyp, uem intersected with [win_start, win_end], collar, skip_overlap), labels indexed file-wide
+ * (a label that is silent in the window has zeros).  COLLARS ARE THOSE OF THE FILE: around the reference boundaries
+ * as given, not around the edges a crop of the reference to the window would create.
+ * The cut list of pa_annot_counts is extended by the 2 W window boundaries (cuts only: nothing starts or ends
+ * there); rank sort and interval sweep run once, window w is the rank range [rank of its start, rank of its end) of
+ * the sorted intervals, and one workgroup per (window, value) sums that range in a fixed order: no floating-point
+ * atomics, no workgroup waits for another, the same input gives the same bits, and inputs whose boundaries (the
+ * windows' included) are multiples of one power of two give exact sums.  The sort is quadratic in
+ * 2 (Nr + Nh + Nu + W) [+ 4 Nr] cuts.
+ * Refused before any launch (3): a negative count, a K above 64, more cuts than the sort accepts, a workspace that
+ * is too small, collar negative or NaN.  W == 0 launches nothing and returns 0.  The caller refuses NaN and
+ * end < start: the kernels stay in bounds for them but the result is meaningless.  Four launches on `stream`;
+ * nothing is copied back. */
+int pa_annot_window_counts(const double* ref_seg, const int32_t* ref_label, int Nr, int Kr, const double* hyp_seg,
+                           const int32_t* hyp_label, int Nh, int Kh, const double* uem_seg, int Nu,
+                           const double* win_seg, int W, double collar, int skip_overlap, double* out, void* ws,
+                           size_t ws_bytes, void* stream);
+
 /* ---- a corpus of files at once, with the within-speaker gaps of every hypothesis filled on the device (the
  *      reference's MinDurationOffOptimizer, __main__.py:430-510, evaluates all files again for every candidate gap:
  *      the turns are uploaded once and only `fill` changes between calls) ---- */

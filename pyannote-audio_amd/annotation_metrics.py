@@ -17,7 +17,9 @@ counts of all files of a corpus in one device call and hands them to `add_counts
 
 `annotation_counts` is the one place the integrals are taken: on a `cuda` device by the kernels of
 csrc/annot_metrics.hip, otherwise (or with more than 64 labels on a side) by a numpy sweep over the same elementary
-intervals.  The names here are this module's own: `metrics.DiarizationErrorRate` is the torchmetrics class."""
+intervals.  `window_counts` takes them for many windows of one file from ONE sweep (`pa_annot_window_counts`, DESIGN.md
+section 29); `SlidingDiarizationErrorRate`, the reference's own class (utils/metric.py:245-286), is built on it.
+The names here are this module's own: `metrics.DiarizationErrorRate` is the torchmetrics class."""
 from __future__ import annotations
 
 import warnings
@@ -28,8 +30,8 @@ import torch
 from scipy.optimize import linear_sum_assignment
 
 from . import ffi
-from .core import Annotation
-from .metrics import BaseMetric
+from .core import Annotation, SlidingWindow
+from .metrics import BaseMetric, _as_timeline
 
 MAX_LABELS = 64          # a side's labels travel as one 64-bit mask on the device
 
@@ -83,16 +85,18 @@ def _device(device) -> Optional[torch.device]:
 
 
 # -------------------------------------------------------------------------------------------------- counts
-def _host_counts(ref_seg, ref_lab, Kr, hyp_seg, hyp_lab, Kh, uem_seg, collar, skip_overlap) -> np.ndarray:
-    """The kernel's sums by a numpy sweep: cut the axis at every boundary, mark per elementary interval which
-    labels are on and whether it is evaluated, sum the lengths."""
+def _host_sweep(ref_seg, ref_lab, Kr, hyp_seg, hyp_lab, Kh, uem_seg, collar, skip_overlap, extra=None):
+    """The kernel's sweep in numpy: cut the axis at every boundary (and at the `extra` values, which are cuts
+    only), mark per elementary interval which labels are on and whether it is evaluated.  -> the sorted distinct
+    cuts (n + 1), bool R (n, Kr) and H (n, Kh), the label counts nr, nh (n) and the evaluated lengths d (n); None
+    without an interval."""
     half = 0.5 * collar
     bounds = np.concatenate([ref_seg.ravel(), ref_seg.ravel() - half, ref_seg.ravel() + half])
-    cuts = np.unique(np.concatenate([bounds if collar > 0 else ref_seg.ravel(), hyp_seg.ravel(), uem_seg.ravel()]))
+    cuts = np.unique(np.concatenate([bounds if collar > 0 else ref_seg.ravel(), hyp_seg.ravel(), uem_seg.ravel()] +
+                                    ([] if extra is None else [extra])))
     n = max(len(cuts) - 1, 0)
-    out = np.zeros(Kr * Kh + Kr + Kh + len(_SCALARS))
     if n == 0:
-        return out
+        return None
 
     def coverage(seg, columns, width):
         """(n, width) number of segments of every column that cover every interval"""
@@ -111,14 +115,59 @@ def _host_counts(ref_seg, ref_lab, Kr, hyp_seg, hyp_lab, Kh, uem_seg, collar, sk
         evaluated &= coverage(around, np.zeros(len(b), dtype=np.int64), 1)[:, 0] == 0
     if skip_overlap:
         evaluated &= nr < 2
-    d = np.where(evaluated, np.diff(cuts), 0.0)
+    return cuts, R, H, nr, nh, np.where(evaluated, np.diff(cuts), 0.0)
+
+
+def _scalar_weights(nr, nh) -> tuple:
+    """per interval, what multiplies its length in each of the seven scalars, in `_SCALARS` order"""
+    return (nr, np.maximum(0, nh - nr), np.maximum(0, nr - nh), np.minimum(nr, nh), nr > 0, nh > 0,
+            (nr > 0) & (nh > 0))
+
+
+def _host_counts(ref_seg, ref_lab, Kr, hyp_seg, hyp_lab, Kh, uem_seg, collar, skip_overlap) -> np.ndarray:
+    """The kernel's sums by the numpy sweep: sum the lengths of the evaluated elementary intervals."""
+    out = np.zeros(Kr * Kh + Kr + Kh + len(_SCALARS))
+    sweep = _host_sweep(ref_seg, ref_lab, Kr, hyp_seg, hyp_lab, Kh, uem_seg, collar, skip_overlap)
+    if sweep is None:
+        return out
+    _, R, H, nr, nh, d = sweep
     Rd = R * d[:, None]
     n0 = Kr * Kh
     out[:n0] = (Rd.T @ H.astype(np.float64)).ravel()
     out[n0:n0 + Kr] = Rd.sum(axis=0)
     out[n0 + Kr:n0 + Kr + Kh] = (H * d[:, None]).sum(axis=0)
-    out[n0 + Kr + Kh:] = [np.sum(w * d) for w in (nr, np.maximum(0, nh - nr), np.maximum(0, nr - nh),
-                                                 np.minimum(nr, nh), nr > 0, nh > 0, (nr > 0) & (nh > 0))]
+    out[n0 + Kr + Kh:] = [np.sum(w * d) for w in _scalar_weights(nr, nh)]
+    return out
+
+
+def _host_window_counts(ref_seg, ref_lab, Kr, hyp_seg, hyp_lab, Kh, uem_seg, win_seg, collar,
+                        skip_overlap) -> np.ndarray:
+    """`pa_annot_window_counts` in numpy, (W, Kr*Kh + Kr + Kh + 7): the sweep of `_host_counts` with the window
+    boundaries among the cuts, then per window the sum over its range of intervals (`searchsorted` of its
+    boundaries; `np.add.reduceat` sums every range by itself, in order -- differences of running sums would carry
+    the rounding of everything in front of the window)."""
+    W, n0 = len(win_seg), Kr * Kh
+    out = np.zeros((W, n0 + Kr + Kh + len(_SCALARS)))
+    sweep = _host_sweep(ref_seg, ref_lab, Kr, hyp_seg, hyp_lab, Kh, uem_seg, collar, skip_overlap,
+                        extra=win_seg.ravel()) if W else None
+    if sweep is None:
+        return out
+    cuts, R, H, nr, nh, d = sweep
+    first, last = np.searchsorted(cuts, win_seg[:, 0]), np.searchsorted(cuts, win_seg[:, 1])
+    empty = last <= first
+    pairs = np.stack([first, last], axis=1).ravel()       # reduceat sums [pairs[i], pairs[i + 1]): the even ones
+
+    def ranges(terms):
+        """(n, C) terms -> (W, C) sums over every window's intervals (a row of zeros behind: index n is valid)"""
+        sums = np.add.reduceat(np.concatenate([terms, np.zeros((1, terms.shape[1]))]), pairs, axis=0)[0::2]
+        sums[empty] = 0.0                                 # (reduceat gives one row, not none, for an empty range)
+        return sums
+
+    Rd, Hf = R * d[:, None], H.astype(np.float64)
+    for i in range(Kr):                                   # (labels, not windows: (n, Kr * Kh) at once is too much)
+        out[:, i * Kh:(i + 1) * Kh] = ranges(Rd[:, i:i + 1] * Hf)
+    out[:, n0:] = ranges(np.concatenate([Rd, Hf * d[:, None], np.stack(_scalar_weights(nr, nh), axis=1) * d[:, None]],
+                                        axis=1))
     return out
 
 
@@ -152,14 +201,9 @@ def device_counts(ref_seg, ref_lab, Kr, hyp_seg, hyp_lab, Kh, uem_seg, collar, s
     return out
 
 
-def annotation_counts(reference: Annotation, hypothesis: Annotation, uem=None, collar: float = 0.0,
-                      skip_overlap: bool = False, device=None, _warn: bool = True) -> dict:
-    """The integrals every class below is made of (include/pyannote_amd.h, `pa_annot_counts`).  Labels are indexed
-    in `labels()` order on each side.  `uem`: a `Timeline`, a list of `Segment`s, or None -- then the evaluated
-    region is the one segment from the earliest start to the latest end over both annotations, with a warning, as
-    pyannote.metrics does.  A `cuda` device runs the kernels; None, `cpu`, or more than 64 labels on a side the
-    numpy sweep.  -> `ref_labels`, `hyp_labels`, float64 numpy `cooc` (Kr, Kh), `ref_dur`, `hyp_dur`, and floats
-    `total`, `false_alarm`, `missed`, `both`, `ref_speech`, `hyp_speech`, `both_speech`."""
+def _inputs(reference, hypothesis, uem, collar, warn: bool) -> tuple:
+    """what `annotation_counts` and `window_counts` check and flatten, called from them directly (the warning
+    names their caller): -> ref_labels, ref_seg, ref_lab, hyp_labels, hyp_seg, hyp_lab, uem_seg"""
     reference, uem = _split(reference, uem)
     ref_labels, ref_seg, ref_lab = _rows(reference)
     hyp_labels, hyp_seg, hyp_lab = _rows(hypothesis)
@@ -168,14 +212,27 @@ def annotation_counts(reference: Annotation, hypothesis: Annotation, uem=None, c
     if not collar >= 0.0:
         raise ValueError(f"collar must be >= 0, got {collar}")
     if uem is None:
-        if _warn:       # (`diarization.cooccurrence` means the whole extent)
+        if warn:       # (`diarization.cooccurrence` means the whole extent)
             warnings.warn("'uem' was approximated by the union of 'reference' and 'hypothesis' extents.",
-                          UserWarning, stacklevel=2)
+                          UserWarning, stacklevel=3)
         both = np.concatenate([ref_seg, hyp_seg])
         uem_seg = np.array([[both[:, 0].min(), both[:, 1].max()]]) if len(both) else np.zeros((0, 2))
     else:
         uem_seg = _uem_rows(uem)
         _check("uem", uem_seg)
+    return ref_labels, ref_seg, ref_lab, hyp_labels, hyp_seg, hyp_lab, uem_seg
+
+
+def annotation_counts(reference: Annotation, hypothesis: Annotation, uem=None, collar: float = 0.0,
+                      skip_overlap: bool = False, device=None, _warn: bool = True) -> dict:
+    """The integrals every class below is made of (include/pyannote_amd.h, `pa_annot_counts`).  Labels are indexed
+    in `labels()` order on each side.  `uem`: a `Timeline`, a list of `Segment`s, or None -- then the evaluated
+    region is the one segment from the earliest start to the latest end over both annotations, with a warning, as
+    pyannote.metrics does.  A `cuda` device runs the kernels; None, `cpu`, or more than 64 labels on a side the
+    numpy sweep.  -> `ref_labels`, `hyp_labels`, float64 numpy `cooc` (Kr, Kh), `ref_dur`, `hyp_dur`, and floats
+    `total`, `false_alarm`, `missed`, `both`, `ref_speech`, `hyp_speech`, `both_speech`."""
+    ref_labels, ref_seg, ref_lab, hyp_labels, hyp_seg, hyp_lab, uem_seg = _inputs(reference, hypothesis, uem, collar,
+                                                                                  _warn)
     Kr, Kh = len(ref_labels), len(hyp_labels)
     dev = _device(device) if Kr <= MAX_LABELS and Kh <= MAX_LABELS else None
     if dev is not None:
@@ -193,6 +250,79 @@ def counts_dict(ref_labels: list, hyp_labels: list, flat: np.ndarray) -> dict:
     counts = {"ref_labels": ref_labels, "hyp_labels": hyp_labels, "cooc": flat[:n0].reshape(Kr, Kh),
               "ref_dur": flat[n0:n0 + Kr], "hyp_dur": flat[n0 + Kr:n0 + Kr + Kh]}
     counts.update({name: float(v) for name, v in zip(_SCALARS, flat[n0 + Kr + Kh:])})
+    return counts
+
+
+# -------------------------------------------------------------------------------------------------- windows
+def device_window_counts(ref_seg, ref_lab, Kr, hyp_seg, hyp_lab, Kh, uem_seg, win_seg, collar, skip_overlap,
+                         device: torch.device) -> torch.Tensor:
+    """`pa_annot_window_counts` on host arrays: one upload, four launches; -> the (W, Kr*Kh + Kr + Kh + 7) float64
+    device tensor (nothing is copied back here)."""
+    Nr, Nh, Nu, W = len(ref_seg), len(hyp_seg), len(uem_seg), len(win_seg)
+    out = torch.empty((W, Kr * Kh + Kr + Kh + len(_SCALARS)), dtype=torch.float64, device=device)
+    if W == 0:
+        return out
+    f64 = np.concatenate([ref_seg.ravel(), hyp_seg.ravel(), uem_seg.ravel(), win_seg.ravel()]).astype(np.float64)
+    i32 = np.concatenate([ref_lab, hyp_lab]).astype(np.int32)
+    if len(i32) % 2:
+        i32 = np.concatenate([i32, np.zeros(1, dtype=np.int32)])
+    packed = torch.from_numpy(np.concatenate([f64, i32.view(np.float64)])).to(device)
+    segs, labs = packed[:len(f64)], packed[len(f64):].view(torch.int32)
+    lib = ffi.load()
+    ws_bytes = int(lib.pa_annot_window_counts_workspace_bytes(Nr, Nh, Nu, W))
+    if ws_bytes == 0:
+        raise ValueError(f"{Nr} + {Nh} + {Nu} segments and {W} windows are more than the device sort accepts")
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=device)
+
+    def at(t, offset, n):
+        return ffi.ptr(t[offset:offset + n]) if n else None
+
+    with torch.cuda.device(device):
+        ffi.check(lib.pa_annot_window_counts(at(segs, 0, 2 * Nr), at(labs, 0, Nr), Nr, Kr,
+                                             at(segs, 2 * Nr, 2 * Nh), at(labs, Nr, Nh), Nh, Kh,
+                                             at(segs, 2 * (Nr + Nh), 2 * Nu), Nu,
+                                             at(segs, 2 * (Nr + Nh + Nu), 2 * W), W, float(collar),
+                                             int(bool(skip_overlap)), ffi.ptr(out), ffi.ptr(ws), ws_bytes,
+                                             ffi.stream()), "pa_annot_window_counts")
+    return out
+
+
+def _window_rows(windows) -> np.ndarray:
+    """a list of `Segment`s (or pairs) or a (W, 2) array -> (W, 2) float64 start / end"""
+    if isinstance(windows, np.ndarray):
+        rows = np.asarray(windows, dtype=np.float64)
+    else:
+        rows = np.array([tuple(w) for w in windows], dtype=np.float64)
+    if rows.size and (rows.ndim != 2 or rows.shape[1] != 2):
+        raise ValueError(f"windows: expected (W, 2) start / end, got shape {rows.shape}")
+    return np.ascontiguousarray(rows.reshape(-1, 2))
+
+
+def window_counts(reference: Annotation, hypothesis: Annotation, windows, uem=None, collar: float = 0.0,
+                  skip_overlap: bool = False, device=None) -> dict:
+    """`annotation_counts` for every window of one file at once (include/pyannote_amd.h, `pa_annot_window_counts`):
+    the counts of window w are those of (reference, hypothesis, uem intersected with the window), labels indexed
+    file-wide, collars around the reference boundaries of the FILE (a crop would put new ones at the window's
+    edges).  `windows`: a list of `Segment`s or a (W, 2) array, in any order, overlapping or not.  A `cuda` device
+    does one upload, one call and one download; None, `cpu`, or more than 64 labels on a side the numpy form of the
+    same sweep.  -> `ref_labels`, `hyp_labels`, float64 numpy `cooc` (W, Kr, Kh), `ref_dur` (W, Kr), `hyp_dur`
+    (W, Kh) and (W,) arrays `total`, `false_alarm`, `missed`, `both`, `ref_speech`, `hyp_speech`, `both_speech`."""
+    ref_labels, ref_seg, ref_lab, hyp_labels, hyp_seg, hyp_lab, uem_seg = _inputs(reference, hypothesis, uem, collar,
+                                                                                  True)
+    win_seg = _window_rows(windows)
+    _check("windows", win_seg)
+    Kr, Kh = len(ref_labels), len(hyp_labels)
+    dev = _device(device) if Kr <= MAX_LABELS and Kh <= MAX_LABELS else None
+    if dev is not None:
+        flat = device_window_counts(ref_seg, ref_lab, Kr, hyp_seg, hyp_lab, Kh, uem_seg, win_seg, collar,
+                                    skip_overlap, dev).cpu().numpy()
+    else:
+        flat = _host_window_counts(ref_seg, ref_lab, Kr, hyp_seg, hyp_lab, Kh, uem_seg, win_seg, float(collar),
+                                   bool(skip_overlap))
+    W, n0 = len(win_seg), Kr * Kh
+    counts = {"ref_labels": ref_labels, "hyp_labels": hyp_labels, "cooc": flat[:, :n0].reshape(W, Kr, Kh),
+              "ref_dur": flat[:, n0:n0 + Kr], "hyp_dur": flat[:, n0 + Kr:n0 + Kr + Kh]}
+    counts.update({name: flat[:, n0 + Kr + Kh + s] for s, name in enumerate(_SCALARS)})
     return counts
 
 
@@ -314,6 +444,77 @@ class GreedyDiarizationErrorRate(DiarizationErrorRate):
     def greedy_mapping(self, reference, hypothesis, uem=None) -> dict:
         """{hypothesis label: reference label}"""
         return self._mapping(reference, hypothesis, uem=uem, mapper=greedy_mapping)
+
+
+_WINDOW_COMPONENTS = ("total", "correct", "false alarm", "missed detection", "confusion")
+
+
+def window_rates_from_counts(counts: dict) -> dict:
+    """`window_counts` -> per window what `DiarizationErrorRate` makes of a file: (W,) float64 arrays `total`,
+    `correct`, `false alarm`, `missed detection`, `confusion` and `diarization error rate`.  Every window has its
+    own optimal mapping, found on the window's own matrix: the labels are compacted to those with a positive
+    duration in the window (the labels a crop to the window would keep), and `optimal_mapping` -- SciPy on the
+    host, W small matrices -- sees exactly the matrix it would see for the cropped file."""
+    der = DiarizationErrorRate()
+    W = len(counts["total"])
+    table = {name: np.zeros(W) for name in _WINDOW_COMPONENTS + (der.metric_name(),)}
+    for w in range(W):
+        rows, columns = counts["ref_dur"][w] > 0, counts["hyp_dur"][w] > 0
+        one = der.components_from_counts({"cooc": counts["cooc"][w][rows][:, columns],
+                                          **{name: float(counts[name][w])
+                                             for name in ("total", "false_alarm", "missed", "both")}})
+        one[der.metric_name()] = der.compute_metric(one)
+        for name, value in one.items():
+            table[name][w] = value
+    return table
+
+
+def window_error_rates(reference: Annotation, hypothesis: Annotation, windows, uem=None, collar: float = 0.0,
+                       skip_overlap: bool = False, device=None) -> dict:
+    """The diarization error rate of every window of one file (`window_rates_from_counts` of `window_counts`)."""
+    return window_rates_from_counts(window_counts(reference, hypothesis, windows, uem=uem, collar=collar,
+                                                  skip_overlap=skip_overlap, device=device))
+
+
+class SlidingDiarizationErrorRate(BaseMetric):
+    """The reference's `SlidingDiarizationErrorRate` (utils/metric.py:245-286): a window of `window` seconds slides
+    over the `uem` with a step of half a window; every window is scored by a complete `DiarizationErrorRate` with
+    its own optimal mapping, and the components are summed.  `metric(reference, hypothesis, uem=uem)`; `uem` is
+    required.  All windows are counted in one call (`window_counts`; on `device` when it is a `cuda` device).
+    Intervals are taken exactly (no 1e-6 rule), as everywhere in this module.  `windows(...)` returns the per-window
+    table, which says WHERE in a file the errors are."""
+
+    @classmethod
+    def metric_name(cls):
+        return "window diarization error rate"
+
+    @classmethod
+    def metric_components(cls):
+        return ["total", "false alarm", "missed detection", "confusion"]
+
+    def __init__(self, window: float = 10.0, device=None):
+        super().__init__()
+        self.window = window
+        self.device = device
+
+    def windows(self, reference, hypothesis, uem=None) -> dict:
+        """-> `windows`, the list of `Segment`s, and per window the (W,) arrays of `window_error_rates`"""
+        reference, uem = _split(reference, uem)
+        if uem is None:
+            raise ValueError("SlidingDiarizationErrorRate expects `uem` to be provided.")
+        uem = _as_timeline(uem)
+        chunks = list(SlidingWindow(duration=self.window, step=0.5 * self.window)(uem))
+        table = window_error_rates(reference, hypothesis, chunks, uem=uem, device=self.device)
+        return {"windows": chunks, **table}
+
+    def compute_components(self, reference, hypothesis, uem=None, **kwargs) -> dict:
+        table = self.windows(reference, hypothesis, uem=uem)
+        # (added window after window from 0, as an accumulating `DiarizationErrorRate` adds them)
+        return {name: sum(table[name].tolist()) for name in _WINDOW_COMPONENTS}
+
+    def compute_metric(self, components):
+        return (components["false alarm"] + components["missed detection"] + components["confusion"]) / \
+            components["total"]
 
 
 class JaccardErrorRate(_AnnotationMetric):

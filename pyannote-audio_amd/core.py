@@ -4,8 +4,8 @@ The reference returns `pyannote.core.Annotation` / `SlidingWindowFeature` object
 package is importable we re-export it (true drop-in); otherwise these restatements of its published
 semantics are used (pyannote-core 6.0.1 is not installed in the build / GPU containers).  Only the
 subset the diarization path touches is provided: Segment, SlidingWindow (closest_frame, indexing,
-crop, range_to_segment), SlidingWindowFeature (iteration, extent, crop, numpy protocol), Annotation
-(track insertion, itertracks, labels, rename_labels, support, RTTM).  `load_rttm` / `load_uem` at the end read RTTM and
+iteration, sliding over a support, crop, range_to_segment), SlidingWindowFeature (iteration, extent, crop,
+numpy protocol), Annotation (track insertion, itertracks, labels, rename_labels, crop, support, RTTM).  `load_rttm` / `load_uem` at the end read RTTM and
 UEM files back, with either package's classes."""
 from __future__ import annotations
 
@@ -114,6 +114,33 @@ if not HAVE_PYANNOTE_CORE:
             if start >= self.end:
                 return None
             return Segment(start=start, end=start + self.duration)
+
+        def __iter__(self) -> Iterator[Segment]:
+            """the windows start + i * step, i = 0, 1, .., while they start before `end` (endless without one)"""
+            i = 0
+            while True:
+                window = self[i]
+                if window is None:
+                    return
+                yield window
+                i += 1
+
+        def __call__(self, support, align_last: bool = False) -> Iterator[Segment]:
+            """Slide over a `Segment` or a `Timeline`: for every segment of the support that is at least `duration`
+            long, the windows segment.start + i * step that lie inside the segment; with `align_last`, when the
+            last of them ends before the segment does, one more window flush with the segment's end."""
+            segments = [support] if isinstance(support, Segment) else list(support)
+            for segment in segments:
+                if segment.duration < self.duration:
+                    continue
+                last = None
+                for window in SlidingWindow(duration=self.duration, step=self.step, start=segment.start,
+                                            end=segment.end):
+                    if segment.start <= window.start and window.end <= segment.end:
+                        yield window
+                        last = window
+                if align_last and last is not None and last.end < segment.end:
+                    yield Segment(start=segment.end - self.duration, end=segment.end)
 
         def range_to_segment(self, i0: int, n: int) -> Segment:
             start = self.start + (i0 - 0.5) * self.step + 0.5 * self.duration
@@ -388,6 +415,27 @@ if not HAVE_PYANNOTE_CORE:
             for s, t, l in annotation.itertracks(yield_label=True):
                 result[s, t] = l
             return result
+
+        def crop(self, support, mode: str = "intersection") -> "Annotation":
+            """The part of the annotation inside `support`, a `Segment` or a `Timeline` (Annotation.crop, mode
+            "intersection"): every segment is replaced by its intersections with the segments of the support, empty
+            ones dropped; a track keeps its name unless the intersection already carries it, then it gets the
+            smallest unused integer."""
+            if mode != "intersection":
+                raise NotImplementedError("Annotation.crop: only mode='intersection' is provided")
+            pieces = [support] if isinstance(support, Segment) else list(support)
+            out = Annotation(uri=self.uri, modality=self.modality)
+            for segment, track, label in self.itertracks(yield_label=True):
+                for piece in pieces:
+                    inside = segment & piece
+                    if not inside:
+                        continue
+                    taken = out._tracks.get(inside, {})
+                    name = track
+                    if name in taken:
+                        name = next(n for n in itertools.count() if n not in taken)
+                    out[inside, name] = label
+            return out
 
         def support(self, collar: float = 0.0):
             """merge same-label segments closer than `collar` (Annotation.support)."""

@@ -20,6 +20,8 @@
 //
 // pa_annot_corpus_counts (second half of this file) runs the same four steps for all files of a corpus in one call,
 // after filling the within-label gaps of every hypothesis on the device (k_annot_support).
+// pa_annot_window_counts takes the sums of many windows of one file from one sweep: the window boundaries are cuts
+// too, a window is a contiguous range of the sorted intervals, and only the reduction runs per window.
 //
 // Every rank lies in 0..M-1 whatever the values are (NaN included: its rank is then meaningless, not out of
 // range), a label outside 0..K-1 is ignored, a segment with end < start covers nothing: bad VALUES cannot make a
@@ -36,12 +38,14 @@ constexpr int ANN_SCALARS = 7;
 
 struct AnnotShape {
   int Nr, Nh, Nu, collar;  // collar: 0 / 1
-  __host__ __device__ int cuts() const { return 2 * (Nr + Nh + Nu) + (collar ? 4 * Nr : 0); }
+  int W = 0;               // windows (pa_annot_window_counts): their boundaries are cuts, not items of the sweep
+  __host__ __device__ int cuts() const { return 2 * (Nr + Nh + Nu) + (collar ? 4 * Nr : 0) + 2 * W; }
   __host__ __device__ int items() const { return Nr + Nh + Nu + (collar ? 2 * Nr : 0); }
 };
 
 // cut layout: [ref start Nr][ref end Nr][hyp start Nh][hyp end Nh][uem start Nu][uem end Nu]
 //             [collar lo 2 Nr][collar hi 2 Nr]   (collar u < Nr: around ref start u; u >= Nr: around ref end u - Nr)
+//             [window start W][window end W]     (pa_annot_window_counts only, written by k_annot_window_cuts)
 // (the four steps are device functions of the workgroup index `blk`: the one-file kernels below and the corpus
 // kernels further down run the same instructions on a file's arrays, which is what makes their bits equal)
 __device__ __forceinline__ void annot_cuts(int blk, const double* __restrict__ ref_seg,
@@ -217,9 +221,48 @@ __global__ __launch_bounds__(ANN_THREADS) void k_annot_reduce(const unsigned lon
   annot_reduce(blockIdx.x, rec_r, rec_h, rec_d, nint, Kr, Kh, out);
 }
 
-static bool annot_cut_count(int Nr, int Nh, int Nu, bool collar, long* M) {
-  if (Nr < 0 || Nh < 0 || Nu < 0) return false;
-  *M = 2 * ((long)Nr + Nh + Nu) + (collar ? 4 * (long)Nr : 0);
+// ------------------------------------------------------------------------------------------------ windows
+// pa_annot_window_counts: the sums of W windows of one file from ONE sweep.  The 2 W window boundaries join the cut
+// list behind the file's own cuts; they are cuts only (no item of the sweep starts or ends there), so the label masks
+// and the evaluated flag of every elementary interval are the file's.  Rank sort and sweep are the device functions
+// above, run once; what is left per window is the reduction over its intervals.
+__global__ __launch_bounds__(ANN_THREADS) void k_annot_window_cuts(const double* __restrict__ ref_seg,
+                                                                   const double* __restrict__ hyp_seg,
+                                                                   const double* __restrict__ uem_seg,
+                                                                   const double* __restrict__ win_seg, AnnotShape sh,
+                                                                   double half_collar, double* __restrict__ cuts) {
+  AnnotShape file = sh;
+  file.W = 0;
+  annot_cuts(blockIdx.x, ref_seg, hyp_seg, uem_seg, file, half_collar, cuts);
+  const int u = blockIdx.x * ANN_THREADS + threadIdx.x - file.cuts();
+  if (u >= 0 && u < 2 * sh.W) cuts[file.cuts() + u] = u < sh.W ? win_seg[2 * u] : win_seg[2 * (u - sh.W) + 1];
+}
+
+// Window w is the rank range [a, b) of the interval list, a = rank of its start cut, b = rank of its end cut:
+// sorted[a] is the window's start and sorted[b] its end, and `sorted` ascends, so an interval k < a ends at
+// sorted[k + 1] <= start, an interval k >= b starts at sorted[k] >= end, and an interval a <= k < b lies inside
+// [start, end].  An interval of non-zero length inside the window therefore has a <= k < b, and one of non-zero
+// length outside it does not.  With tied cuts (a window edge on a segment boundary, the end of window w on the start
+// of window w + 2) which of the equal cuts gets the lower rank is decided by the cut index, but the intervals that
+// this moves across a or b lie between two equal cuts: length 0, contribution 0.  A window with end < start or a
+// NaN boundary has an empty or meaningless range that still lies inside 0 .. cuts - 1.
+// One workgroup per (window, output value): annot_reduce on the range, so the order of additions is fixed by the
+// range alone -- no floating-point atomics, no workgroup waits for another.
+__global__ __launch_bounds__(ANN_THREADS) void k_annot_window_reduce(const unsigned long long* __restrict__ rec_r,
+                                                                     const unsigned long long* __restrict__ rec_h,
+                                                                     const double* __restrict__ rec_d,
+                                                                     const int* __restrict__ rank, AnnotShape sh,
+                                                                     int Kr, int Kh, double* __restrict__ out) {
+  const int w = blockIdx.x, first = sh.cuts() - 2 * sh.W;
+  const int a = rank[first + w], b = rank[first + sh.W + w];
+  const long nout = Kr * Kh + Kr + Kh + ANN_SCALARS;
+  annot_reduce(blockIdx.y, rec_r + a, rec_h + a, rec_d + a, b > a ? b - a : 0, Kr, Kh, out + w * nout);
+}
+
+// the cuts of a file and of W windows over it (W = 0: pa_annot_counts' own count)
+static bool annot_cut_count(int Nr, int Nh, int Nu, bool collar, long* M, int W = 0) {
+  if (Nr < 0 || Nh < 0 || Nu < 0 || W < 0) return false;
+  *M = 2 * ((long)Nr + Nh + Nu + W) + (collar ? 4 * (long)Nr : 0);
   return *M <= ANN_MAX_CUTS;
 }
 
@@ -456,6 +499,52 @@ int pa_annot_counts(const double* ref_seg, const int32_t* ref_label, int Nr, int
   hipLaunchKernelGGL(pa::k_annot_reduce, dim3(nout), dim3(pa::ANN_THREADS), 0, s, a.rec_r, a.rec_h, a.rec_d, nint, Kr,
                      Kh, out);
   PA_CHECK_LAUNCH("pa_annot_counts");
+  return 0;
+}
+
+size_t pa_annot_window_counts_workspace_bytes(int Nr, int Nh, int Nu, int W) {
+  long M;
+  if (!pa::annot_cut_count(Nr, Nh, Nu, true, &M, W)) return 0;
+  return pa::carved_bytes([&](pa::Carver& c) { pa::annot_layout(c, 0, M); }, pa::ANN_SLACK);
+}
+
+int pa_annot_window_counts(const double* ref_seg, const int32_t* ref_label, int Nr, int Kr, const double* hyp_seg,
+                           const int32_t* hyp_label, int Nh, int Kh, const double* uem_seg, int Nu,
+                           const double* win_seg, int W, double collar, int skip_overlap, double* out, void* ws,
+                           size_t ws_bytes, void* stream) {
+  PA_REQUIRE(Kr >= 0 && Kr <= pa::ANN_MAXK && Kh >= 0 && Kh <= pa::ANN_MAXK,
+             "pa_annot_window_counts: %d reference and %d hypothesis labels, 0..%d each supported", Kr, Kh,
+             pa::ANN_MAXK);
+  PA_REQUIRE(Nr >= 0 && Nh >= 0 && Nu >= 0 && W >= 0,
+             "pa_annot_window_counts: negative segment or window count (%d, %d, %d, %d)", Nr, Nh, Nu, W);
+  PA_REQUIRE(collar >= 0.0, "pa_annot_window_counts: collar %g is negative or NaN", collar);
+  const bool with_collar = collar > 0.0;
+  long M;
+  PA_REQUIRE(pa::annot_cut_count(Nr, Nh, Nu, with_collar, &M, W), "pa_annot_window_counts: more than %ld cuts",
+             pa::ANN_MAX_CUTS);
+  PA_REQUIRE((W == 0 || (out && win_seg)) && (Nr == 0 || (ref_seg && ref_label)) &&
+                 (Nh == 0 || (hyp_seg && hyp_label)) && (Nu == 0 || uem_seg),
+             "pa_annot_window_counts: null array");
+  pa::Carver carver(ws, pa::ANN_SLACK);
+  const pa::AnnotBufs a = pa::annot_layout(carver, 0, M);
+  PA_REQUIRE(ws && ws_bytes >= carver.bytes(), "pa_annot_window_counts: workspace of %zu bytes, %zu needed", ws_bytes,
+             carver.bytes());
+  if (W == 0) return 0;
+  hipStream_t s = (hipStream_t)stream;
+  const pa::AnnotShape sh{Nr, Nh, Nu, with_collar ? 1 : 0, W};
+  const int m = (int)M;                                       // >= 2: the windows' own cuts
+  const int nout = Kr * Kh + Kr + Kh + pa::ANN_SCALARS;
+  pa::ProfScope prof("k_annot_window_counts", stream, 0.0, 44.0 * m + 8.0 * nout * W);
+  const int grid = pa::cdiv(m, pa::ANN_THREADS);
+  hipLaunchKernelGGL(pa::k_annot_window_cuts, dim3(grid), dim3(pa::ANN_THREADS), 0, s, ref_seg, hyp_seg, uem_seg,
+                     win_seg, sh, 0.5 * collar, a.cuts);
+  hipLaunchKernelGGL(pa::k_annot_rank, dim3(grid), dim3(pa::ANN_THREADS), 0, s, a.cuts, m, a.sorted, a.rank);
+  hipLaunchKernelGGL(pa::k_annot_intervals, dim3(pa::cdiv(m - 1, pa::ANN_THREADS)), dim3(pa::ANN_THREADS), 0, s,
+                     a.sorted, a.rank, ref_label, hyp_label, sh, Kr, Kh, skip_overlap ? 1 : 0, a.rec_r, a.rec_h,
+                     a.rec_d);
+  hipLaunchKernelGGL(pa::k_annot_window_reduce, dim3(W, nout), dim3(pa::ANN_THREADS), 0, s, a.rec_r, a.rec_h, a.rec_d,
+                     a.rank, sh, Kr, Kh, out);
+  PA_CHECK_LAUNCH("pa_annot_window_counts");
   return 0;
 }
 

@@ -317,6 +317,9 @@ _OPTIONAL: list[tuple] = [
     ("pa_annot_counts_workspace_bytes", [C.c_int, C.c_int, C.c_int], C.c_size_t),
     ("pa_annot_counts", [c_fp, c_fp, C.c_int, C.c_int, c_fp, c_fp, C.c_int, C.c_int, c_fp, C.c_int, C.c_double,
                          C.c_int, c_fp, c_fp, C.c_size_t, c_fp], C.c_int),
+    ("pa_annot_window_counts_workspace_bytes", [C.c_int, C.c_int, C.c_int, C.c_int], C.c_size_t),
+    ("pa_annot_window_counts", [c_fp, c_fp, C.c_int, C.c_int, c_fp, c_fp, C.c_int, C.c_int, c_fp, C.c_int, c_fp,
+                                C.c_int, C.c_double, C.c_int, c_fp, c_fp, C.c_size_t, c_fp], C.c_int),
     ("pa_annot_corpus_workspace_bytes", [C.POINTER(AnnotCorpus)], C.c_size_t),
     ("pa_annot_corpus_counts", [C.POINTER(AnnotCorpus), C.c_double, C.c_double, C.c_int, c_fp, c_fp, c_fp, C.c_size_t,
                                 c_fp], C.c_int),
