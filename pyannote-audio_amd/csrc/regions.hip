@@ -1,24 +1,12 @@
 // hipcc-flags: -ffp-contract=off
 // Hysteresis thresholding of an aggregated (T, K) score array into per-class region lists, on the device
 // (what utils/signal.py:254-318 `Binarize.__call__` does to every class of a multi-label model, followed by
-// `Annotation.support(collar)` and the min_duration_on deletion).
+// `Annotation.support(collar)` and the min_duration_on deletion).  One detector per class: slot k of the map word is
+// class k.  The rule and every step of it are in regions.h; the kernels here say where a step's data lies.
 //
-// The reference's rule is state dependent: inactive -> active iff y > onset, active -> inactive iff y < offset.
-// Every frame is therefore one of four maps on {inactive, active} (identity, set, clear, swap; swap needs
-// offset > onset), and the state sequence is a prefix scan under map composition, which is associative.  A map
-// is two bits (image of "inactive", image of "active"); the maps of all K <= 16 classes of one frame travel in
-// one 32-bit word (low half: images of "inactive", high half: images of "active") and compose bitwise, so one
-// scan serves every class.
-//
-// Launch sequence (each kernel ends before the next starts; NO workgroup ever waits for another one):
-//   k_regions_reduce   one workgroup per tile of 1024 frames: composed map of the tile
-//   k_regions_scan     one wave: exclusive scan of the tile maps -> state on entry of every tile
-//   k_regions_apply    per tile: states, on / off events per frame, number of on-events per 64-frame chunk
-//   k_regions_offsets  one wave per class: exclusive scan of the chunk counts
-//   k_regions_emit     per chunk: the n-th on-event and the n-th off-event of a class are region n
+// Launch sequence (each kernel ends before the next starts):
+//   k_regions_reduce, k_regions_scan, k_regions_apply, k_regions_offsets, k_regions_emit   the steps of regions.h
 //   k_regions_finish   one workgroup per class: drop empty regions, merge across short gaps, drop short regions
-// Times are float64 and bit-identical to the host's `0.5 * (s + (s + duration))`, `s = start + i * step`: this
-// file is compiled without FMA contraction and the products / sums are the _rn intrinsics.
 #include "common.h"
 #include "pyannote_amd.h"
 #include "regions.h"
@@ -27,35 +15,12 @@ namespace pa {
 
 __global__ __launch_bounds__(RG_THREADS) void k_regions_reduce(const float* __restrict__ scores, int T, int K,
                                                                RegionParams p, uint32_t* __restrict__ tile_map) {
-  __shared__ uint32_t part[RG_PASSES * 4];
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const long t0 = (long)blockIdx.x * RG_TILE;
-#pragma unroll
-  for (int q = 0; q < RG_PASSES; ++q) {
-    const uint32_t m = rg_wave_scan(rg_frame_map(scores, t0 + q * RG_THREADS + threadIdx.x, T, K, p), lane);
-    if (lane == 63) part[q * 4 + w] = m;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    uint32_t m = part[0];
-    for (int j = 1; j < RG_PASSES * 4; ++j) m = rg_compose(m, part[j]);
-    tile_map[blockIdx.x] = m;
-  }
+  rg_reduce_tile(scores, T, K, p, tile_map);
 }
 
 __global__ __launch_bounds__(64) void k_regions_scan(const uint32_t* __restrict__ tile_map, int ntiles,
                                                      uint32_t* __restrict__ state_in) {
-  const int lane = threadIdx.x;
-  uint32_t carry = RG_IDENTITY;
-  for (int base = 0; base < ntiles; base += 64) {
-    const int t = base + lane;
-    const uint32_t inc = rg_wave_scan(t < ntiles ? tile_map[t] : RG_IDENTITY, lane);
-    uint32_t exc = __shfl_up(inc, 1, 64);
-    if (lane == 0) exc = RG_IDENTITY;
-    // frame 0 is a constant map, so the image of "inactive" is the state whatever came before
-    if (t < ntiles) state_in[t] = rg_compose(carry, exc) & 0xffffu;
-    carry = rg_compose(carry, __shfl(inc, 63, 64));
-  }
+  rg_scan_tiles(tile_map, ntiles, state_in);
 }
 
 __global__ __launch_bounds__(RG_THREADS) void k_regions_apply(const float* __restrict__ scores, int T, int K,
@@ -63,152 +28,42 @@ __global__ __launch_bounds__(RG_THREADS) void k_regions_apply(const float* __res
                                                               const uint32_t* __restrict__ state_in,
                                                               uint32_t* __restrict__ events,
                                                               int* __restrict__ chunk_cnt, int nchunks) {
-  __shared__ uint32_t part[4];
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const long t0 = (long)blockIdx.x * RG_TILE;
-  uint32_t state = state_in[blockIdx.x];            // state of every class before the pass's first frame
-  for (int q = 0; q < RG_PASSES; ++q) {
-    const long i = t0 + q * RG_THREADS + threadIdx.x;
-    const uint32_t m = rg_frame_map(scores, i, T, K, p);
-    const uint32_t inc = rg_wave_scan(m, lane);
-    __syncthreads();                                // `part` of the previous pass has been read
-    if (lane == 63) part[w] = inc;
-    __syncthreads();
-    uint32_t exc = __shfl_up(inc, 1, 64);
-    if (lane == 0) exc = RG_IDENTITY;
-    uint32_t pre = RG_IDENTITY, total = part[0];
-    for (int j = 1; j < 4; ++j) {
-      if (j == w) pre = total;
-      total = rg_compose(total, part[j]);
-    }
-    if (w == 0) pre = RG_IDENTITY;
-    exc = rg_compose(pre, exc);
-    const uint32_t before = ((state & (exc >> 16)) | (~state & exc)) & 0xffffu;
-    const uint32_t after = ((before & (m >> 16)) | (~before & m)) & 0xffffu;
-    uint32_t on = ~before & after & 0xffffu, off = before & ~after;
-    if (i == T - 1) {   // a region still open closes on the last frame; one that would open there is empty
-      off = before;
-      on = 0;
-    }
-    if (i >= T) on = off = 0;
-    if (i < T) events[i] = on | (off << 16);
-    const int chunk = blockIdx.x * (RG_TILE / RG_CHUNK) + q * 4 + w;
-#pragma unroll
-    for (int k = 0; k < RG_MAXK; ++k)
-      if (k < K) {
-        const unsigned long long b = __ballot((on >> k) & 1u);
-        if (lane == k && chunk < nchunks) chunk_cnt[(long)k * nchunks + chunk] = __popcll(b);
-      }
-    state = ((state & (total >> 16)) | (~state & total)) & 0xffffu;
-  }
+  rg_apply_tile(scores, T, K, p, K, state_in[blockIdx.x], events, chunk_cnt, nchunks);
 }
 
-// wave k: exclusive scan of class k's chunk counts; the total is the number of regions before any clean-up
-__global__ __launch_bounds__(64 * RG_MAXK) void k_regions_offsets(const int* __restrict__ chunk_cnt, int nchunks, int* __restrict__ chunk_off,
-                                  int* __restrict__ n_raw) {
-  const int lane = threadIdx.x & 63, k = threadIdx.x >> 6;
-  const int* cnt = chunk_cnt + (long)k * nchunks;
-  int* out = chunk_off + (long)k * nchunks;
-  int carry = 0;
-  for (int base = 0; base < nchunks; base += 64) {
-    const int c = base + lane;
-    const int v = c < nchunks ? cnt[c] : 0;
-    const int inc = rg_wave_scan_int(v, lane);
-    if (c < nchunks) out[c] = carry + inc - v;
-    carry += __shfl(inc, 63, 64);
-  }
-  if (lane == 0) n_raw[k] = carry;
+// wave k: class k's chunk counts; the total is the number of regions before any clean-up
+__global__ __launch_bounds__(64 * RG_MAXK) void k_regions_offsets(const int* __restrict__ chunk_cnt, int nchunks,
+                                                                  int* __restrict__ chunk_off,
+                                                                  int* __restrict__ n_raw) {
+  const int k = threadIdx.x >> 6;
+  const int total = rg_scan_counts(chunk_cnt + (long)k * nchunks, nchunks, chunk_off + (long)k * nchunks);
+  if ((threadIdx.x & 63) == 0) n_raw[k] = total;
 }
 
-// On- and off-events of a class alternate, starting with an on-event: region n runs from the n-th on-event to the
-// n-th off-event, and the off-event's n is (number of on-events up to and including its frame) - 1.
 __global__ __launch_bounds__(RG_THREADS) void k_regions_emit(const uint32_t* __restrict__ events, int T, int K,
                                                              RegionParams p, const int* __restrict__ chunk_off,
                                                              int nchunks, int capacity,
                                                              double* __restrict__ raw) {
-  const int lane = threadIdx.x & 63;
-  const long i = (long)blockIdx.x * RG_THREADS + threadIdx.x;
-  const int chunk = (int)(i >> 6);
-  const uint32_t ev = i < T ? events[i] : 0u;
-  if (__ballot(ev != 0u) == 0ull) return;
-  const double t = rg_time(i, p);
-  const unsigned long long upto = ~0ull >> (63 - lane);   // lanes 0..lane
-#pragma unroll
-  for (int k = 0; k < RG_MAXK; ++k)
-    if (k < K) {
-      const unsigned long long b = __ballot((ev >> k) & 1u);
-      if ((ev >> k) & 0x10001u) {
-        const int n = chunk_off[(long)k * nchunks + chunk] + __popcll(b & upto) - 1;
-        if (n >= 0 && n < capacity) {
-          double* r = raw + ((long)k * capacity + n) * 2;
-          if ((ev >> k) & 1u) r[0] = t;
-          if ((ev >> (16 + k)) & 1u) r[1] = t;
-        }
-      }
-    }
+  rg_emit_events(events, T, K, p.start, p.duration, p.step, chunk_off, nchunks,
+                 [=](int k) { return RegionRows{(long)k * capacity, capacity}; }, raw);
 }
 
-// One workgroup per class over its (few) regions, three order-preserving compactions: raw -> out drops regions the
-// reference's Annotation refuses on insertion (duration <= 1e-6); out -> raw merges neighbours whose gap has
-// Segment.duration < min_duration_off (Annotation.support(collar)); raw -> out drops regions with
-// duration < min_duration_on and records every survivor's index among the merged regions (its track name).
+// One workgroup per class over its (few) regions: the three compactions of regions.h, raw -> out -> raw -> out
 __global__ __launch_bounds__(RG_THREADS) void k_regions_finish(int K, RegionParams p, const int* __restrict__ n_raw,
                                                                int capacity, double* raw_all, double* out_all,
                                                                int* __restrict__ tracks_all,
                                                                int* __restrict__ counts) {
   __shared__ int red[4];
-  const int k = blockIdx.x, tid = threadIdx.x;
+  const int k = blockIdx.x;
   double* raw = raw_all + (long)k * capacity * 2;
   double* out = out_all + (long)k * capacity * 2;
   int* tracks = tracks_all ? tracks_all + (long)k * capacity : nullptr;
-  const double min_on = p.min_on[k], min_off = p.min_off[k];
-  const int n0 = min(n_raw[k], capacity);
-  int total;
-
-  int n1 = 0;
-  for (int base = 0; base < n0; base += RG_THREADS) {
-    const int i = base + tid;
-    double s = 0.0, e = 0.0;
-    if (i < n0) { s = raw[2 * i]; e = raw[2 * i + 1]; }
-    const int keep = i < n0 && (e - s) > RG_PRECISION;
-    const int pos = n1 + rg_block_scan_int(keep, red, total) - 1;
-    if (keep) { out[2 * pos] = s; out[2 * pos + 1] = e; }
-    n1 += total;
-  }
+  const int n1 = rg_drop_empty(raw, min(n_raw[k], capacity), out, red);
   __syncthreads();
-
-  int n2 = 0;
-  for (int base = 0; base < n1; base += RG_THREADS) {
-    const int i = base + tid;
-    int head = 0, tail = 0;
-    double s = 0.0, e = 0.0;
-    if (i < n1) {
-      s = out[2 * i]; e = out[2 * i + 1];
-      head = i == 0 || !(min_off > 0.0 && rg_duration(out[2 * i - 1], s) < min_off);
-      tail = i == n1 - 1 || !(min_off > 0.0 && rg_duration(e, out[2 * i + 2]) < min_off);
-    }
-    const int run = n2 + rg_block_scan_int(head, red, total) - 1;
-    if (head) raw[2 * run] = s;
-    if (tail) raw[2 * run + 1] = e;
-    n2 += total;
-  }
+  const int n2 = rg_merge_gaps(out, n1, p.min_off[k], raw, red);
   __syncthreads();
-
-  int n3 = 0;
-  for (int base = 0; base < n2; base += RG_THREADS) {
-    const int i = base + tid;
-    double s = 0.0, e = 0.0;
-    if (i < n2) { s = raw[2 * i]; e = raw[2 * i + 1]; }
-    const int keep = i < n2 && !(min_on > 0.0 && rg_duration(s, e) < min_on);
-    const int pos = n3 + rg_block_scan_int(keep, red, total) - 1;
-    if (keep) {
-      out[2 * pos] = s;
-      out[2 * pos + 1] = e;
-      if (tracks) tracks[pos] = min_off > 0.0 ? i : 0;   // support() renames tracks; without it all are the first name
-    }
-    n3 += total;
-  }
-  if (tid == 0) counts[k] = n3;
+  const int n3 = rg_drop_short(raw, n2, p.min_on[k], p.min_off[k], capacity, out, tracks, red);
+  if (threadIdx.x == 0) counts[k] = n3;
 }
 
 // The workspace of pa_binarize_regions in 256-byte-aligned blocks

@@ -1,7 +1,7 @@
 // hipcc-flags: -ffp-contract=off
 // The regions of MANY hysteresis detectors from one pass over an aggregated (T, K) score array: what tuning the
 // thresholds of VoiceActivityDetection / MultiLabelSegmentation on a corpus asks for (every candidate's region lists;
-// DESIGN.md section 24).  The rule is pa_binarize_regions' (regions.hip), bit for bit.
+// DESIGN.md section 24).  The rule is pa_binarize_regions', bit for bit: both run the steps of regions.h.
 //
 // A LANE is (class, onset, offset); a JOB is (lane, min_duration_on, min_duration_off).  Lanes of one class travel
 // sixteen to a map word -- the role the K classes play in regions.hip -- so a GROUP of up to 16 lanes reads its
@@ -9,7 +9,7 @@
 //
 // Per launch batch of groups (blockIdx.y = group; as many groups at a time as the workspace holds, results do not
 // depend on the split; NO workgroup ever waits for another one):
-//   k_sweep_reduce / k_sweep_scan / k_sweep_apply / k_sweep_offsets   as in regions.hip -> raw regions per lane
+//   k_sweep_reduce / k_sweep_scan / k_sweep_apply / k_sweep_offsets   the steps of regions.h -> raw count per lane
 //   (counting phase stops here: pa_regions_sweep_count reads the raw counts back, the caller sizes the row buffers)
 //   k_sweep_emit       region n of a lane runs from its n-th on-event to its n-th off-event
 //   k_sweep_clean      one workgroup per lane: drops the empty regions into a list that is only read from then on
@@ -29,65 +29,35 @@ namespace pa {
 struct SweepGroup {
   float onset[RG_MAXK], offset[RG_MAXK];   // unused slots: +inf / -inf, the identity map, never an event
   int32_t lane[RG_MAXK];                   // lane id of every slot, -1: unused
-  int32_t cls;
+  int32_t cls;                             // the column every slot reads
+
+  __device__ __forceinline__ uint32_t frame_map(const float* __restrict__ scores, long i, int T, int K) const {
+    if (i >= T) return RG_IDENTITY;
+    const float y = scores[i * K + cls];              // NaN: both comparisons false -> identity
+    uint32_t f0 = 0, f1 = 0;
+#pragma unroll
+    for (int s = 0; s < RG_MAXK; ++s) {
+      f0 |= (uint32_t)(y > onset[s]) << s;
+      f1 |= (uint32_t)(!(y < offset[s])) << s;
+    }
+    if (i == 0) f1 = f0;
+    return f0 | (f1 << 16);
+  }
 };
 
-__device__ __forceinline__ uint32_t sw_frame_map(const float* __restrict__ scores, long i, int T, int K,
-                                                 const SweepGroup& g) {
-  if (i >= T) return RG_IDENTITY;
-  const float y = scores[i * K + g.cls];            // NaN: both comparisons false -> identity
-  uint32_t f0 = 0, f1 = 0;
-#pragma unroll
-  for (int s = 0; s < RG_MAXK; ++s) {
-    f0 |= (uint32_t)(y > g.onset[s]) << s;
-    f1 |= (uint32_t)(!(y < g.offset[s])) << s;
-  }
-  if (i == 0) f1 = f0;
-  return f0 | (f1 << 16);
-}
-
-// rg_time with the grid as plain arguments (same operations, same order)
-__device__ __forceinline__ double sw_time(long i, double start, double duration, double step) {
-  const double s = __dadd_rn(start, __dmul_rn((double)i, step));
-  return __dmul_rn(0.5, __dadd_rn(s, __dadd_rn(s, duration)));
-}
-
+// grid (tile, group); a group's thresholds are read from LDS
 __global__ __launch_bounds__(RG_THREADS) void k_sweep_reduce(const float* __restrict__ scores, int T, int K,
                                                              const SweepGroup* __restrict__ groups, int ntiles,
                                                              uint32_t* __restrict__ tile_map) {
-  __shared__ uint32_t part[RG_PASSES * 4];
   __shared__ SweepGroup g;
   if (threadIdx.x == 0) g = groups[blockIdx.y];
   __syncthreads();
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const long t0 = (long)blockIdx.x * RG_TILE;
-#pragma unroll
-  for (int q = 0; q < RG_PASSES; ++q) {
-    const uint32_t m = rg_wave_scan(sw_frame_map(scores, t0 + q * RG_THREADS + threadIdx.x, T, K, g), lane);
-    if (lane == 63) part[q * 4 + w] = m;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    uint32_t m = part[0];
-    for (int j = 1; j < RG_PASSES * 4; ++j) m = rg_compose(m, part[j]);
-    tile_map[(long)blockIdx.y * ntiles + blockIdx.x] = m;
-  }
+  rg_reduce_tile(scores, T, K, g, tile_map + (long)blockIdx.y * ntiles);
 }
 
-__global__ __launch_bounds__(64) void k_sweep_scan(const uint32_t* __restrict__ tile_map_all, int ntiles,
-                                                   uint32_t* __restrict__ state_in_all) {
-  const int lane = threadIdx.x;
-  const uint32_t* tile_map = tile_map_all + (long)blockIdx.x * ntiles;
-  uint32_t* state_in = state_in_all + (long)blockIdx.x * ntiles;
-  uint32_t carry = RG_IDENTITY;
-  for (int base = 0; base < ntiles; base += 64) {
-    const int t = base + lane;
-    const uint32_t inc = rg_wave_scan(t < ntiles ? tile_map[t] : RG_IDENTITY, lane);
-    uint32_t exc = __shfl_up(inc, 1, 64);
-    if (lane == 0) exc = RG_IDENTITY;
-    if (t < ntiles) state_in[t] = rg_compose(carry, exc) & 0xffffu;
-    carry = rg_compose(carry, __shfl(inc, 63, 64));
-  }
+__global__ __launch_bounds__(64) void k_sweep_scan(const uint32_t* __restrict__ tile_map, int ntiles,
+                                                   uint32_t* __restrict__ state_in) {
+  rg_scan_tiles(tile_map + (long)blockIdx.x * ntiles, ntiles, state_in + (long)blockIdx.x * ntiles);
 }
 
 // `events`: NULL in the counting phase (only the chunk counts are wanted)
@@ -96,66 +66,24 @@ __global__ __launch_bounds__(RG_THREADS) void k_sweep_apply(const float* __restr
                                                             const uint32_t* __restrict__ state_in,
                                                             uint32_t* __restrict__ events,
                                                             int* __restrict__ chunk_cnt, int nchunks) {
-  __shared__ uint32_t part[4];
   __shared__ SweepGroup g;
   if (threadIdx.x == 0) g = groups[blockIdx.y];
   __syncthreads();
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const long t0 = (long)blockIdx.x * RG_TILE;
-  uint32_t state = state_in[(long)blockIdx.y * ntiles + blockIdx.x];
-  for (int q = 0; q < RG_PASSES; ++q) {
-    const long i = t0 + q * RG_THREADS + threadIdx.x;
-    const uint32_t m = sw_frame_map(scores, i, T, K, g);
-    const uint32_t inc = rg_wave_scan(m, lane);
-    __syncthreads();                                // `part` of the previous pass has been read
-    if (lane == 63) part[w] = inc;
-    __syncthreads();
-    uint32_t exc = __shfl_up(inc, 1, 64);
-    if (lane == 0) exc = RG_IDENTITY;
-    uint32_t pre = RG_IDENTITY, total = part[0];
-    for (int j = 1; j < 4; ++j) {
-      if (j == w) pre = total;
-      total = rg_compose(total, part[j]);
-    }
-    if (w == 0) pre = RG_IDENTITY;
-    exc = rg_compose(pre, exc);
-    const uint32_t before = ((state & (exc >> 16)) | (~state & exc)) & 0xffffu;
-    const uint32_t after = ((before & (m >> 16)) | (~before & m)) & 0xffffu;
-    uint32_t on = ~before & after & 0xffffu, off = before & ~after;
-    if (i == T - 1) {   // a region still open closes on the last frame; one that would open there is empty
-      off = before;
-      on = 0;
-    }
-    if (i >= T) on = off = 0;
-    if (events && i < T) events[(long)blockIdx.y * T + i] = on | (off << 16);
-    const int chunk = blockIdx.x * (RG_TILE / RG_CHUNK) + q * 4 + w;
-#pragma unroll
-    for (int s = 0; s < RG_MAXK; ++s) {
-      const unsigned long long b = __ballot((on >> s) & 1u);
-      if (lane == s && chunk < nchunks) chunk_cnt[((long)blockIdx.y * RG_MAXK + s) * nchunks + chunk] = __popcll(b);
-    }
-    state = ((state & (total >> 16)) | (~state & total)) & 0xffffu;
-  }
+  rg_apply_tile(scores, T, K, g, RG_MAXK, state_in[(long)blockIdx.y * ntiles + blockIdx.x],
+                events ? events + (long)blockIdx.y * T : nullptr, chunk_cnt + (long)blockIdx.y * RG_MAXK * nchunks,
+                nchunks);
 }
 
-// workgroup = group, wave s = its slot s: exclusive scan of the slot's chunk counts; the total is the lane's raw count
+// workgroup = group, wave s = its slot s; the total of the slot's chunk counts is the lane's raw count
 __global__ __launch_bounds__(64 * RG_MAXK) void k_sweep_offsets(const SweepGroup* __restrict__ groups,
                                                                 const int* __restrict__ chunk_cnt, int nchunks,
                                                                 int* __restrict__ chunk_off,
                                                                 int* __restrict__ n_raw) {
-  const int lane = threadIdx.x & 63, s = threadIdx.x >> 6;
-  const int* cnt = chunk_cnt + ((long)blockIdx.x * RG_MAXK + s) * nchunks;
-  int* out = chunk_off + ((long)blockIdx.x * RG_MAXK + s) * nchunks;
-  int carry = 0;
-  for (int base = 0; base < nchunks; base += 64) {
-    const int c = base + lane;
-    const int v = c < nchunks ? cnt[c] : 0;
-    const int inc = rg_wave_scan_int(v, lane);
-    if (c < nchunks) out[c] = carry + inc - v;
-    carry += __shfl(inc, 63, 64);
-  }
+  const int s = threadIdx.x >> 6;
+  const long row = ((long)blockIdx.x * RG_MAXK + s) * nchunks;
+  const int total = rg_scan_counts(chunk_cnt + row, nchunks, chunk_off + row);
   const int id = groups[blockIdx.x].lane[s];
-  if (lane == 0 && id >= 0) n_raw[id] = carry;
+  if ((threadIdx.x & 63) == 0 && id >= 0) n_raw[id] = total;
 }
 
 // raw rows of lane l: raw + 2 raw_off[l], raw_off[l + 1] - raw_off[l] of them (the counting phase's counts)
@@ -165,31 +93,18 @@ __global__ __launch_bounds__(RG_THREADS) void k_sweep_emit(const uint32_t* __res
                                                            const int* __restrict__ chunk_off, int nchunks,
                                                            const int* __restrict__ raw_off,
                                                            double* __restrict__ raw) {
-  const int lane = threadIdx.x & 63;
-  const long i = (long)blockIdx.x * RG_THREADS + threadIdx.x;
-  const int chunk = (int)(i >> 6);
-  const uint32_t ev = i < T ? events[(long)blockIdx.y * T + i] : 0u;
-  if (__ballot(ev != 0u) == 0ull) return;
-  const SweepGroup& g = groups[blockIdx.y];
-  const double t = sw_time(i, start, duration, step);
-  const unsigned long long upto = ~0ull >> (63 - lane);   // lanes 0..lane
-#pragma unroll
-  for (int s = 0; s < RG_MAXK; ++s) {
-    const unsigned long long b = __ballot((ev >> s) & 1u);
-    if ((ev >> s) & 0x10001u) {
-      const int id = g.lane[s];
-      const int n = chunk_off[((long)blockIdx.y * RG_MAXK + s) * nchunks + chunk] + __popcll(b & upto) - 1;
-      if (id >= 0 && n >= 0 && n < raw_off[id + 1] - raw_off[id]) {
-        double* r = raw + ((long)raw_off[id] + n) * 2;
-        if ((ev >> s) & 1u) r[0] = t;
-        if ((ev >> (16 + s)) & 1u) r[1] = t;
-      }
-    }
-  }
+  const int32_t* lane_of = groups[blockIdx.y].lane;
+  rg_emit_events(events + (long)blockIdx.y * T, T, RG_MAXK, start, duration, step,
+                 chunk_off + (long)blockIdx.y * RG_MAXK * nchunks, nchunks,
+                 [=](int s) {
+                   const int id = lane_of[s];
+                   return id < 0 ? RegionRows{0, 0} : RegionRows{raw_off[id], raw_off[id + 1] - raw_off[id]};
+                 },
+                 raw);
 }
 
-// one workgroup per slot of the batch's groups: raw -> clean drops the regions the reference's Annotation refuses on
-// insertion (duration <= 1e-6).  `clean` has the layout of `raw` and is only read afterwards.
+// one workgroup per slot of the batch's groups: raw -> clean without the empty regions.  `clean` has the layout of
+// `raw` and is only read afterwards.
 __global__ __launch_bounds__(RG_THREADS) void k_sweep_clean(const SweepGroup* __restrict__ groups,
                                                             const int* __restrict__ n_raw,
                                                             const int* __restrict__ raw_off,
@@ -197,22 +112,11 @@ __global__ __launch_bounds__(RG_THREADS) void k_sweep_clean(const SweepGroup* __
                                                             double* __restrict__ clean_all,
                                                             int* __restrict__ n_clean) {
   __shared__ int red[4];
-  const int id = groups[blockIdx.x / RG_MAXK].lane[blockIdx.x % RG_MAXK], tid = threadIdx.x;
+  const int id = groups[blockIdx.x / RG_MAXK].lane[blockIdx.x % RG_MAXK];
   if (id < 0) return;                                   // (the whole workgroup)
-  const double* raw = raw_all + (long)raw_off[id] * 2;
-  double* clean = clean_all + (long)raw_off[id] * 2;
-  const int n0 = min(n_raw[id], raw_off[id + 1] - raw_off[id]);
-  int total, n1 = 0;
-  for (int base = 0; base < n0; base += RG_THREADS) {
-    const int i = base + tid;
-    double s = 0.0, e = 0.0;
-    if (i < n0) { s = raw[2 * i]; e = raw[2 * i + 1]; }
-    const int keep = i < n0 && (e - s) > RG_PRECISION;
-    const int pos = n1 + rg_block_scan_int(keep, red, total) - 1;
-    if (keep) { clean[2 * pos] = s; clean[2 * pos + 1] = e; }
-    n1 += total;
-  }
-  if (tid == 0) n_clean[id] = n1;
+  const int n1 = rg_drop_empty(raw_all + (long)raw_off[id] * 2, min(n_raw[id], raw_off[id + 1] - raw_off[id]),
+                               clean_all + (long)raw_off[id] * 2, red);
+  if (threadIdx.x == 0) n_clean[id] = n1;
 }
 
 struct SweepJob {
@@ -220,8 +124,8 @@ struct SweepJob {
   int32_t lane, scratch_off;    // the job's merged rows: scratch + 2 scratch_off, room for the lane's raw count
 };
 
-// one workgroup per job: clean (read only) -> the job's scratch merges neighbours whose gap has
-// Segment.duration < min_duration_off; then the survivors of the min_duration_on removal are counted
+// one workgroup per job: clean (read only) -> the job's scratch, merged across short gaps; then the survivors of the
+// min_duration_on removal are counted
 __global__ __launch_bounds__(RG_THREADS) void k_sweep_merge(const SweepJob* __restrict__ jobs,
                                                             const int* __restrict__ n_clean,
                                                             const int* __restrict__ raw_off,
@@ -231,27 +135,12 @@ __global__ __launch_bounds__(RG_THREADS) void k_sweep_merge(const SweepJob* __re
   __shared__ int red[4];
   const SweepJob job = jobs[blockIdx.x];
   const int tid = threadIdx.x;
-  const double* in = clean_all + (long)raw_off[job.lane] * 2;
   double* out = scratch_all + (long)job.scratch_off * 2;
-  const double min_on = job.min_on, min_off = job.min_off;
+  const double min_on = job.min_on;
   const int n1 = min(n_clean[job.lane], raw_off[job.lane + 1] - raw_off[job.lane]);
-  int total, n2 = 0;
-  for (int base = 0; base < n1; base += RG_THREADS) {
-    const int i = base + tid;
-    int head = 0, tail = 0;
-    double s = 0.0, e = 0.0;
-    if (i < n1) {
-      s = in[2 * i]; e = in[2 * i + 1];
-      head = i == 0 || !(min_off > 0.0 && rg_duration(in[2 * i - 1], s) < min_off);
-      tail = i == n1 - 1 || !(min_off > 0.0 && rg_duration(e, in[2 * i + 2]) < min_off);
-    }
-    const int run = n2 + rg_block_scan_int(head, red, total) - 1;
-    if (head) out[2 * run] = s;
-    if (tail) out[2 * run + 1] = e;
-    n2 += total;
-  }
+  const int n2 = rg_merge_gaps(clean_all + (long)raw_off[job.lane] * 2, n1, job.min_off, out, red);
   __syncthreads();                                      // the merged rows are read by other threads below
-  int n3 = 0;
+  int total, n3 = 0;
   for (int base = 0; base < n2; base += RG_THREADS) {
     const int i = base + tid;
     const int keep = i < n2 && !(min_on > 0.0 && rg_duration(out[2 * i], out[2 * i + 1]) < min_on);
@@ -261,22 +150,14 @@ __global__ __launch_bounds__(RG_THREADS) void k_sweep_merge(const SweepJob* __re
   if (tid == 0) { n_merged[blockIdx.x] = n2; counts[blockIdx.x] = n3; }
 }
 
+// one wave: the jobs' counts -> the (M + 1) offset table
 __global__ __launch_bounds__(64) void k_sweep_job_offsets(const int* __restrict__ counts, int M,
                                                           int* __restrict__ job_off) {
-  const int lane = threadIdx.x;
-  int carry = 0;
-  for (int base = 0; base < M; base += 64) {
-    const int j = base + lane;
-    const int v = j < M ? counts[j] : 0;
-    const int inc = rg_wave_scan_int(v, lane);
-    if (j < M) job_off[j] = carry + inc - v;
-    carry += __shfl(inc, 63, 64);
-  }
-  if (lane == 0) job_off[M] = carry;
+  const int total = rg_scan_counts(counts, M, job_off);
+  if (threadIdx.x == 0) job_off[M] = total;
 }
 
-// one workgroup per job: scratch -> the job's rows of the packed output drops regions with duration < min_duration_on
-// and records every survivor's index among the merged regions (its track name)
+// one workgroup per job: scratch -> the job's rows of the packed output (`rows` in all) without the short regions
 __global__ __launch_bounds__(RG_THREADS) void k_sweep_remove(const SweepJob* __restrict__ jobs,
                                                              const double* __restrict__ scratch_all,
                                                              const int* __restrict__ n_merged,
@@ -285,24 +166,9 @@ __global__ __launch_bounds__(RG_THREADS) void k_sweep_remove(const SweepJob* __r
                                                              int* __restrict__ tracks) {
   __shared__ int red[4];
   const SweepJob job = jobs[blockIdx.x];
-  const int tid = threadIdx.x;
-  const double* in = scratch_all + (long)job.scratch_off * 2;
-  const double min_on = job.min_on, min_off = job.min_off;
-  const int n2 = n_merged[blockIdx.x], o = job_off[blockIdx.x];
-  int total, n3 = 0;
-  for (int base = 0; base < n2; base += RG_THREADS) {
-    const int i = base + tid;
-    double s = 0.0, e = 0.0;
-    if (i < n2) { s = in[2 * i]; e = in[2 * i + 1]; }
-    const int keep = i < n2 && !(min_on > 0.0 && rg_duration(s, e) < min_on);
-    const long pos = (long)o + n3 + rg_block_scan_int(keep, red, total) - 1;
-    if (keep && pos < rows) {
-      regions[2 * pos] = s;
-      regions[2 * pos + 1] = e;
-      if (tracks) tracks[pos] = min_off > 0.0 ? i : 0;   // support() renames tracks; without it all are the first name
-    }
-    n3 += total;
-  }
+  const int o = job_off[blockIdx.x];
+  rg_drop_short(scratch_all + (long)job.scratch_off * 2, n_merged[blockIdx.x], job.min_on, job.min_off, rows - o,
+                regions + (long)o * 2, tracks ? tracks + o : nullptr, red);
 }
 
 // ------------------------------------------------------------------------------------------------ host side
@@ -381,6 +247,36 @@ static int sweep_check_lanes(const char* who, int T, int K, int L, const int32_t
   return 0;
 }
 
+// What either phase does between its argument checks and its first launch: the plan of the lanes, how many groups a
+// launch sequence takes (as many as the workspace holds), the carve and the upload of the plan.  Nothing is launched,
+// and nothing written, before the last refusal here.
+struct SweepSetup {
+  std::vector<SweepGroup> groups;   // handed to an asynchronous copy: the phase waits for the stream before it returns
+  int G, per;                       // groups in all and per launch sequence
+  SweepWorkspace w;
+};
+static int sweep_setup(const char* who, int T, int K, int L, const int32_t* lane_class, const float* onset,
+                       const float* offset, int M, long raw_rows, long job_rows, void* workspace,
+                       size_t workspace_bytes, hipStream_t s, SweepSetup* u) {
+  sweep_plan(K, L, lane_class, onset, offset, &u->groups);
+  const int G = u->G = (int)u->groups.size();
+  const size_t fixed = sweep_bytes(T, G, 0, L, M, raw_rows, job_rows),
+               each = sweep_bytes(T, G, 1, L, M, raw_rows, job_rows) - fixed;
+  PA_REQUIRE(workspace && workspace_bytes >= fixed + each, "%s: workspace of %zu bytes, at least %zu needed", who,
+             workspace_bytes, fixed + each);
+  u->per = (int)std::min<size_t>(std::min(G, 65535), (workspace_bytes - fixed) / each);   // (grid.y)
+  Carver carver(workspace, 256);
+  u->w = sweep_layout(carver, T, G, u->per, L, M, raw_rows, job_rows);
+  PA_REQUIRE(workspace_bytes >= carver.bytes(), "%s: workspace of %zu bytes, %zu needed", who, workspace_bytes,
+             carver.bytes());
+  if (hipMemcpyAsync(u->w.groups, u->groups.data(), sizeof(SweepGroup) * (size_t)G, hipMemcpyHostToDevice, s) !=
+      hipSuccess) {
+    set_error("%s: uploading the lane tables failed", who);
+    return 1;
+  }
+  return 0;
+}
+
 // the launches of one batch of `n` groups starting at group `g0`; `emit` false: counting only
 static void sweep_launch_batch(hipStream_t s, const float* scores, int T, int K, const SweepWorkspace& w, int g0,
                                int n, bool emit, double start, double duration, double step) {
@@ -431,23 +327,12 @@ int pa_regions_sweep_count(const float* scores, int T, int K, int L, const int32
   for (int l = 0; l < L; ++l) n_raw[l] = 0;
   if (T < 2 || L == 0) return 0;      // the reference has no defined result for fewer than two frames
   PA_REQUIRE(scores, "%s: null scores", who);
-  std::vector<pa::SweepGroup> groups;
-  pa::sweep_plan(K, L, lane_class, onset, offset, &groups);
-  const int G = (int)groups.size();
-  const size_t fixed = pa::sweep_bytes(T, G, 0, L, 0, 0, 0), each = pa::sweep_bytes(T, G, 1, L, 0, 0, 0) - fixed;
-  PA_REQUIRE(workspace && workspace_bytes >= fixed + each, "%s: workspace of %zu bytes, at least %zu needed", who,
-             workspace_bytes, fixed + each);
-  const int per = (int)std::min<size_t>(std::min(G, 65535), (workspace_bytes - fixed) / each);   // (grid.y)
   hipStream_t s = (hipStream_t)stream;
-  pa::Carver carver(workspace, 256);
-  const pa::SweepWorkspace w = pa::sweep_layout(carver, T, G, per, L, 0, 0, 0);
-  PA_REQUIRE(workspace_bytes >= carver.bytes(), "%s: workspace of %zu bytes, %zu needed", who, workspace_bytes,
-             carver.bytes());
-  if (hipMemcpyAsync(w.groups, groups.data(), sizeof(pa::SweepGroup) * (size_t)G, hipMemcpyHostToDevice, s) !=
-      hipSuccess) {
-    pa::set_error("%s: uploading the lane tables failed", who);
-    return 1;
-  }
+  pa::SweepSetup u;
+  if (int rc = pa::sweep_setup(who, T, K, L, lane_class, onset, offset, 0, 0, 0, workspace, workspace_bytes, s, &u))
+    return rc;
+  const int G = u.G, per = u.per;
+  const pa::SweepWorkspace& w = u.w;
   {
     pa::ProfScope prof("k_regions_sweep_count", stream, 4.0 * T * G * 16, 12.0 * T * G);
     for (int g0 = 0; g0 < G; g0 += per) {
@@ -508,21 +393,13 @@ int pa_regions_sweep_emit(const float* scores, int T, int K, int L, const int32_
     PA_REQUIRE(job_rows <= 0x7fffffffL, "%s: more than 2^31 - 1 job rows: sweep fewer jobs per call", who);
   }
   PA_REQUIRE(rows >= job_rows && (regions || job_rows == 0), "%s: room for %ld rows, %ld needed", who, rows, job_rows);
-  std::vector<pa::SweepGroup> groups;
-  pa::sweep_plan(K, L, lane_class, onset, offset, &groups);
-  const int G = (int)groups.size();
-  const size_t fixed = pa::sweep_bytes(T, G, 0, L, M, raw_rows, job_rows),
-               each = pa::sweep_bytes(T, G, 1, L, M, raw_rows, job_rows) - fixed;
-  PA_REQUIRE(workspace && workspace_bytes >= fixed + each, "%s: workspace of %zu bytes, at least %zu needed", who,
-             workspace_bytes, fixed + each);
-  const int per = (int)std::min<size_t>(std::min(G, 65535), (workspace_bytes - fixed) / each);   // (grid.y)
-  pa::Carver carver(workspace, 256);
-  const pa::SweepWorkspace w = pa::sweep_layout(carver, T, G, per, L, M, raw_rows, job_rows);
-  PA_REQUIRE(workspace_bytes >= carver.bytes(), "%s: workspace of %zu bytes, %zu needed", who, workspace_bytes,
-             carver.bytes());
-  if (hipMemcpyAsync(w.groups, groups.data(), sizeof(pa::SweepGroup) * (size_t)G, hipMemcpyHostToDevice, s) !=
-          hipSuccess ||
-      hipMemcpyAsync(w.raw_off, raw_off.data(), 4 * ((size_t)L + 1), hipMemcpyHostToDevice, s) != hipSuccess ||
+  pa::SweepSetup u;
+  if (int rc = pa::sweep_setup(who, T, K, L, lane_class, onset, offset, M, raw_rows, job_rows, workspace,
+                               workspace_bytes, s, &u))
+    return rc;
+  const int G = u.G, per = u.per;
+  const pa::SweepWorkspace& w = u.w;
+  if (hipMemcpyAsync(w.raw_off, raw_off.data(), 4 * ((size_t)L + 1), hipMemcpyHostToDevice, s) != hipSuccess ||
       hipMemcpyAsync(w.jobs, jobs.data(), sizeof(pa::SweepJob) * (size_t)M, hipMemcpyHostToDevice, s) != hipSuccess) {
     pa::set_error("%s: uploading the lane and job tables failed", who);
     return 1;
