@@ -738,6 +738,17 @@ def kaldi_mel_banks(num_bins: int = 80, padded: int = 512, sample_freq: float = 
     return torch.nn.functional.pad(bins, (0, 1)).contiguous()
 
 
+def fbank_tables():
+    """the float32 tables k_fbank reads (csrc/emb_fbank.hip), fp64 -> fp32: the Hamming window (400,),
+    tw256 (256, 2) = exp(-2 pi i m / 256) and tw512 (257, 2) = exp(-2 pi i k / 512) as (re, im)"""
+    window = torch.hamming_window(400, periodic=False, alpha=0.54, beta=0.46)
+    m = np.arange(256, dtype=np.float64)
+    tw256 = np.stack([np.cos(2 * np.pi * m / 256), -np.sin(2 * np.pi * m / 256)], -1)
+    k = np.arange(257, dtype=np.float64)
+    tw512 = np.stack([np.cos(2 * np.pi * k / 512), -np.sin(2 * np.pi * k / 512)], -1)
+    return window, torch.from_numpy(tw256.astype(np.float32)), torch.from_numpy(tw512.astype(np.float32))
+
+
 def winograd_weights(cw: torch.Tensor) -> torch.Tensor:
     """(cout, cin, 3, 3) -> [16][cout][cin] float32: U = G g G^T of Winograd F(2x2, 3x3), computed in
     float64 (xi = 4a + b indexes the 4x4 transform domain)."""
@@ -856,13 +867,8 @@ class EmbeddingPack:
             w.planes[l] = int(planes[l])
         w.embed_dim = int(sd["resnet.seg_1.weight"].shape[0])
         # fbank tables (fp64 -> fp32)
-        w.fb_window = self._up(torch.hamming_window(400, periodic=False, alpha=0.54, beta=0.46))
-        m = np.arange(256, dtype=np.float64)
-        tw256 = np.stack([np.cos(2 * np.pi * m / 256), -np.sin(2 * np.pi * m / 256)], -1)
-        k = np.arange(257, dtype=np.float64)
-        tw512 = np.stack([np.cos(2 * np.pi * k / 512), -np.sin(2 * np.pi * k / 512)], -1)
-        w.fb_tw256 = self._up(torch.from_numpy(tw256.astype(np.float32)))
-        w.fb_tw512 = self._up(torch.from_numpy(tw512.astype(np.float32)))
+        window, tw256, tw512 = fbank_tables()
+        w.fb_window, w.fb_tw256, w.fb_tw512 = self._up(window), self._up(tw256), self._up(tw512)
         mel = kaldi_mel_banks(num_mel, 512, float(sample_rate))
         self.mel = mel
         nz = mel > 0
