@@ -972,6 +972,45 @@ int pa_kmeans_f64(const double* X, int N, int D, int K, int n_init, const int32_
                   int max_iter, double tol, int round_iterations, int32_t* labels, double* centers, double* inertia,
                   int32_t* picks, int32_t* status, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- batched linear sum assignment (scipy.optimize.linear_sum_assignment; csrc/lsap.hip) ---- */
+
+/* the largest number of rows and of columns pa_lsap_batch takes (64) */
+int pa_lsap_max_size(void);
+/* `batch` assignment problems in one launch, each with the result of scipy.optimize.linear_sum_assignment(problem,
+ * maximize) -- the SAME optimum where there are several: the kernel does the additions, subtractions and comparisons
+ * of SciPy's shortest augmenting path solver in SciPy's order (tests/lsap_model.py restates them).
+ * cost: float64 on the device, element (b, r, c) at cost[b * batch_stride + r * row_stride + c * col_stride]; the
+ * strides are in elements and may describe a transposed view.  rows, cols <= pa_lsap_max_size().
+ * row_mask, col_mask: (batch) each on the device, or NULL = every row / column: problem b is the submatrix of the rows
+ * and columns whose bits are set, in ascending order (bits at or above rows / cols are ignored).
+ * col4row (batch, rows) int32: the column of every row, numbered as in `cost`; -1 for a row that is masked out, left
+ * unassigned (more rows than columns) or part of a problem that was not solved.
+ * total (batch), or NULL: cost[r][col4row[r]] added over the assigned rows in ascending r, starting from 0.0.
+ * status (batch): 0 solved; 1 invalid entry, what SciPy refuses with "matrix contains invalid numeric entries": a NaN,
+ * or -inf after the negation of `maximize`, anywhere in the problem; 2 infeasible: +inf (after the negation) forbids
+ * a pair, and no complete assignment avoids those.  With a status other than 0 the problem's col4row is -1 and its
+ * total 0.0.  A problem without a row or without a column is solved, with total 0.0.
+ * One 64-lane workgroup per problem; no workspace, no allocation, no synchronisation; every loop of the kernel has a
+ * bound known on entry.  batch == 0 returns at once.  Returns 3, before the launch, for more than 64 rows or columns. */
+int pa_lsap_batch(const double* cost, long batch_stride, long row_stride, long col_stride, int batch, int rows,
+                  int cols, const uint64_t* row_mask, const uint64_t* col_mask, int maximize, int32_t* col4row,
+                  double* total, uint8_t* status, void* stream);
+/* The cost matrices `permutate` (utils/permutation.py:99-196) hands to the solver, for y1 (batch, frames, C1) and
+ * y2 (batch, frames, C2) of one dtype (float32, or float64 with is_f64) on the device, given by their element strides
+ * (y2_batch_stride 0: one y2 for the whole batch): cost (batch, R, C2) float64, contiguous, R = max(C1, C2);
+ * rows < C1: the mean over the frames of (y1[.., i] - y2[.., j])^2, or of the absolute difference with `mae`, computed
+ * as numpy computes np.mean(.., axis=0) in the input dtype -- the frames added one after the other from frame 0, the
+ * product rounded before the sum, one division by `frames` -- and converted exactly; rows >= C1 (C2 > C1 only):
+ * the largest of those plus 1, both in the input dtype.  1 <= C1, C2 <= 64, frames >= 1. */
+int pa_pair_costs(const void* y1, long y1_batch_stride, long y1_frame_stride, long y1_class_stride, const void* y2,
+                  long y2_batch_stride, long y2_frame_stride, long y2_class_stride, int is_f64, int batch, int frames,
+                  int C1, int C2, int mae, double* cost, void* stream);
+/* out (batch, frames, C1), contiguous, of y2's dtype: out[b, f, i] = y2[b, f, perm[b * perm_stride + i]], 0 where that
+ * entry of perm is -1 (y2 by its element strides, as above) */
+int pa_permute_classes(const void* y2, long y2_batch_stride, long y2_frame_stride, long y2_class_stride, int is_f64,
+                       const int32_t* perm, long perm_stride, int batch, int frames, int C1, int C2, void* out,
+                       void* stream);
+
 #ifdef __cplusplus
 }
 #endif

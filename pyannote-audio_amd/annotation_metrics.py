@@ -471,9 +471,50 @@ def window_rates_from_counts(counts: dict) -> dict:
 
 def window_error_rates(reference: Annotation, hypothesis: Annotation, windows, uem=None, collar: float = 0.0,
                        skip_overlap: bool = False, device=None) -> dict:
-    """The diarization error rate of every window of one file (`window_rates_from_counts` of `window_counts`)."""
-    return window_rates_from_counts(window_counts(reference, hypothesis, windows, uem=uem, collar=collar,
-                                                  skip_overlap=skip_overlap, device=device))
+    """The diarization error rate of every window of one file (`window_rates_from_counts` of `window_counts`).  On a
+    `cuda` device the W mappings are found there as well (`device_window_rates`): the table is the same, value for
+    value, and W x 5 numbers come back instead of the counts."""
+    ref_labels, hyp_labels = _split(reference, uem)[0].labels(), hypothesis.labels()
+    dev = _device(device) if len(ref_labels) <= MAX_LABELS and len(hyp_labels) <= MAX_LABELS else None
+    if dev is None:
+        return window_rates_from_counts(window_counts(reference, hypothesis, windows, uem=uem, collar=collar,
+                                                      skip_overlap=skip_overlap, device=device))
+    ref_labels, ref_seg, ref_lab, hyp_labels, hyp_seg, hyp_lab, uem_seg = _inputs(reference, hypothesis, uem, collar,
+                                                                                  True)
+    win_seg = _window_rows(windows)
+    _check("windows", win_seg)
+    Kr, Kh = len(ref_labels), len(hyp_labels)
+    flat = device_window_counts(ref_seg, ref_lab, Kr, hyp_seg, hyp_lab, Kh, uem_seg, win_seg, collar, skip_overlap, dev)
+    return device_window_rates(flat, Kr, Kh)
+
+
+def device_window_rates(flat: torch.Tensor, Kr: int, Kh: int) -> dict:
+    """`window_rates_from_counts` for the (W, Kr*Kh + Kr + Kh + 7) device tensor of `device_window_counts`, the W
+    optimal mappings in ONE launch (`pa_lsap_batch`, csrc/lsap.hip): problem w is the (hypothesis, reference) view of
+    its co-occurrence matrix, read through the strides, restricted to the labels with a positive duration in the
+    window, maximised; its `total` -- the matched durations added in ascending hypothesis order, as the host adds
+    them -- is `correct`.  One download of W x 5 numbers: total, false alarm, missed, both, correct."""
+    from .distance import linear_sum_assignment_batch
+    W, n0 = flat.shape[0], Kr * Kh
+    scalars = flat[:, n0 + Kr + Kh:n0 + Kr + Kh + 4]
+    if W and Kr and Kh:
+        together = flat.as_strided((W, Kh, Kr), (flat.stride(0), 1, Kh))
+        _, correct, status = linear_sum_assignment_batch(
+            together, maximize=True, row_mask=flat[:, n0 + Kr:n0 + Kr + Kh] > 0, col_mask=flat[:, n0:n0 + Kr] > 0,
+            return_total=True, check=False)
+        correct = torch.where(status != 0, torch.full_like(correct, float("nan")), correct)
+    else:
+        correct = torch.zeros(W, dtype=torch.float64, device=flat.device)
+    host = torch.cat([scalars, correct[:, None]], dim=1).cpu().numpy()
+    total, false_alarm, missed, both, correct = (np.ascontiguousarray(host[:, k]) for k in range(5))
+    if np.isnan(correct).any():      # (durations are finite: a refused matrix means the counts are not counts)
+        raise ValueError(f"window {int(np.flatnonzero(np.isnan(correct))[0])}: the co-occurrence matrix is not finite")
+    confusion = both - correct
+    errors = false_alarm + missed + confusion
+    with np.errstate(divide="ignore", invalid="ignore"):
+        rate = np.where(total == 0, np.where(errors == 0, 0.0, 1.0), errors / total)
+    return dict(zip(_WINDOW_COMPONENTS + (DiarizationErrorRate.metric_name(),),
+                    (total, correct, false_alarm, missed, confusion, rate)))
 
 
 class SlidingDiarizationErrorRate(BaseMetric):

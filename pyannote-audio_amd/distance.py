@@ -240,6 +240,91 @@ def cdist(A, B: np.ndarray, metric: str = "cosine", device=None) -> np.ndarray:
     return out.cpu().numpy()
 
 
+#: what SciPy says when it refuses a matrix, by status of `pa_lsap_batch`
+LSAP_REFUSALS = {1: "matrix contains invalid numeric entries", 2: "cost matrix is infeasible"}
+
+
+def _bit_masks(mask, batch: int, size: int, device):
+    """None or a (batch, size) boolean table -> None or the (batch,) 64-bit masks of `pa_lsap_batch`, as an int64
+    device tensor"""
+    if mask is None:
+        return None
+    mask = torch.as_tensor(mask).to(device)
+    if mask.dtype != torch.bool or mask.shape != (batch, size):
+        raise ValueError(f"expected a boolean mask of shape {(batch, size)}, got {mask.dtype} {tuple(mask.shape)}")
+    weights = torch.ones(size, dtype=torch.int64, device=device) << torch.arange(size, device=device)
+    return (mask.to(torch.int64) * weights).sum(dim=1).contiguous()     # (bit 63 wraps to the sign: the same bits)
+
+
+def _lsap_host(cost: np.ndarray, maximize: bool, row_mask, col_mask):
+    """the SciPy loop with the outputs of `pa_lsap_batch`"""
+    from scipy.optimize import linear_sum_assignment
+    B, R, Cn = cost.shape
+    col4row = np.full((B, R), -1, dtype=np.int32)
+    total, status = np.zeros(B), np.zeros(B, dtype=np.uint8)
+    for b in range(B):
+        rows = np.flatnonzero(row_mask[b]) if row_mask is not None else np.arange(R)
+        cols = np.flatnonzero(col_mask[b]) if col_mask is not None else np.arange(Cn)
+        try:
+            r, c = linear_sum_assignment(cost[b][rows][:, cols], maximize=maximize)
+        except ValueError as error:
+            status[b] = 2 if "infeasible" in str(error) else 1
+            continue
+        col4row[b, rows[r]] = cols[c]
+        total[b] = sum((float(cost[b, i, j]) for i, j in zip(rows[r], cols[c])), 0.0)
+    return col4row, total, status
+
+
+@ffi.on_device(lambda cost, *args, **kwargs: getattr(cost, "device", None))
+def linear_sum_assignment_batch(cost, maximize: bool = False, row_mask=None, col_mask=None,
+                                return_total: bool = False, check: bool = True):
+    """`scipy.optimize.linear_sum_assignment(cost[b], maximize)` for every matrix of a (B, R, C) float64 batch, with
+    SciPy's own choice among equal optima (`pa_lsap_batch`, csrc/lsap.hip).
+    `cost`: a `cuda` tensor of any strides (a transposed view costs nothing) runs ONE launch and returns device tensors;
+    R, C <= 64 there.  `row_mask`, `col_mask`: (B, R) / (B, C) boolean tables: problem b is the submatrix of the
+    rows and columns that are set.  -> `col4row` (B, R) int32, the column of every row, -1 for a row that is
+    masked out or left unassigned; with `return_total` also `total` (B,) float64, cost[r][col4row[r]] added in
+    ascending r.  `check=True` downloads the B status bytes and raises SciPy's `ValueError` for the first problem it
+    would refuse; `check=False` appends the (B,) uint8 status (0 solved, 1 invalid entry, 2 infeasible) instead.
+    A host array or host tensor takes a SciPy loop and returns arrays of its own kind."""
+    on_device = isinstance(cost, torch.Tensor) and cost.is_cuda
+    if cost.ndim != 3:
+        raise ValueError(f"expected a (B, R, C) batch of matrices, got shape {tuple(cost.shape)}")
+    B, R, Cn = cost.shape
+    if on_device:
+        if cost.dtype != torch.float64:
+            raise ValueError(f"expected float64 costs, got {cost.dtype}")
+        lib = ffi.load()
+        limit = int(lib.pa_lsap_max_size())
+        if R > limit or Cn > limit:
+            raise ValueError(f"at most {limit} rows and columns on the device, got {R} x {Cn}")
+        dev = cost.device
+        rm, cm = _bit_masks(row_mask, B, R, dev), _bit_masks(col_mask, B, Cn, dev)
+        col4row = torch.empty((B, R), dtype=torch.int32, device=dev)
+        total = torch.empty(B, dtype=torch.float64, device=dev) if return_total else None
+        status = torch.empty(B, dtype=torch.uint8, device=dev)
+        sb, sr, sc = cost.stride()
+        ffi.check(lib.pa_lsap_batch(ffi.C.c_void_p(cost.data_ptr()), sb, sr, sc, B, R, Cn, ffi.ptr(rm), ffi.ptr(cm),
+                                    int(bool(maximize)), ffi.ptr(col4row), ffi.ptr(total), ffi.ptr(status),
+                                    ffi.stream()), "pa_lsap_batch")
+        host_status = status.cpu().numpy() if check else None
+    else:
+        as_torch = isinstance(cost, torch.Tensor)
+        array = cost.detach().numpy() if as_torch else np.asarray(cost)
+
+        tables = [None if mask is None else np.asarray(mask.cpu() if isinstance(mask, torch.Tensor) else mask, dtype=bool)
+                  for mask in (row_mask, col_mask)]
+        col4row, total, status = _lsap_host(array.astype(np.float64, copy=False), bool(maximize), *tables)
+        host_status = status
+        if as_torch:
+            col4row, total, status = (torch.from_numpy(x) for x in (col4row, total, status))
+    if check and host_status.any():
+        first = int(np.flatnonzero(host_status)[0])
+        raise ValueError(f"{LSAP_REFUSALS[int(host_status[first])]} (problem {first} of the batch)")
+    out = (col4row,) + ((total,) if return_total else ()) + (() if check else (status,))
+    return out[0] if len(out) == 1 else out
+
+
 #: Lloyd iterations enqueued between two reads of the done flags (`pa_kmeans_f64`; 0: all `max_iter` at once, no
 #: read-back).  The choice is measured in profiles/kmeans_timing.txt.
 KMEANS_ROUND_ITERATIONS = 8

@@ -333,6 +333,13 @@ _OPTIONAL: list[tuple] = [
     ("pa_kmeans_workspace_bytes", [C.c_int, C.c_int, C.c_int, C.c_int], C.c_size_t),
     ("pa_kmeans_f64", [c_fp, C.c_int, C.c_int, C.c_int, C.c_int, c_fp, c_fp, C.c_int, C.c_double, C.c_int, c_fp, c_fp,
                        c_fp, c_fp, c_fp, c_fp, C.c_size_t, c_fp], C.c_int),
+    ("pa_lsap_max_size", [], C.c_int),
+    ("pa_lsap_batch", [c_fp, C.c_long, C.c_long, C.c_long, C.c_int, C.c_int, C.c_int, c_fp, c_fp, C.c_int, c_fp, c_fp,
+                       c_fp, c_fp], C.c_int),
+    ("pa_pair_costs", [c_fp, C.c_long, C.c_long, C.c_long, c_fp, C.c_long, C.c_long, C.c_long, C.c_int, C.c_int,
+                       C.c_int, C.c_int, C.c_int, C.c_int, c_fp, c_fp], C.c_int),
+    ("pa_permute_classes", [c_fp, C.c_long, C.c_long, C.c_long, C.c_int, c_fp, C.c_long, C.c_int, C.c_int, C.c_int,
+                            C.c_int, c_fp, c_fp], C.c_int),
 ]
 
 

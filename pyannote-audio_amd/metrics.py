@@ -27,7 +27,7 @@ from scipy.optimize import linear_sum_assignment
 
 from . import ffi
 from .core import HAVE_PYANNOTE_CORE, SEGMENT_PRECISION, Annotation, Segment, SlidingWindowFeature
-from .permutation import permutate
+from .permutation import permutate, permutate_batch  # noqa: F401  (`permutate` stays importable from here)
 from .verification import EqualErrorRate  # noqa: F401  (the classification half of the reference's torchmetrics)
 
 MAX_SPEAKERS = 32        # a frame's speakers travel as one 32-bit mask
@@ -375,9 +375,9 @@ def _der_update(preds: torch.Tensor, target: torch.Tensor, threshold=0.5, reduce
 
     perm = None
     if S > AUTO_PERMUTATION and B > 0:
-        # larger speaker sets: the existing Hungarian `permutate` on the host (:90-92)
-        _, found = permutate(target.transpose(1, 2).to(torch.float32), preds.transpose(1, 2))
-        perm = torch.tensor([[-1 if j is None else j for j in row] for row in found], dtype=torch.int32).to(dev)
+        # larger speaker sets: the Hungarian `permutate` (:90-92), on the tensors as they lie (`permutate_batch`:
+        # the costs, SciPy's assignment and nothing downloaded)
+        _, perm = permutate_batch(target.to(torch.float32).transpose(1, 2), preds.transpose(1, 2))
 
     lib = ffi.load()
     is_f32 = int(target.dtype == torch.float32)
