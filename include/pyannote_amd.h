@@ -16,6 +16,19 @@
  *     convention of Inference.infer (core/inference.py:199-208).
  *   - all arithmetic is IEEE fp32 (f32-input MFMA; the reference disables TF32,
  *     utils/reproducibility.py:68-73); the clustering distance kernels are fp64 like SciPy.
+ *
+ * Workspaces (every `workspace` / `ws` argument with its `*_workspace_bytes` query)
+ *   - the contents on entry may be ANYTHING -- NaN, huge values, the left-over of another call or of a larger
+ *     batch -- and are unspecified on return.  Every block a call reads, it has written before on the same stream (a
+ *     kernel or a hipMemsetAsync), or the read cannot reach an output: DESIGN.md section 31 lists the blocks;
+ *   - nothing outside [workspace, workspace + workspace_bytes) is touched, and a call given the bytes its query
+ *     returned uses no more than those;
+ *   - no output depends on the contents: the same arguments give the same output BYTES whatever the workspace held
+ *     (tests/test_hostile_workspace_gpu.py).  One exception, by design: pa_vbx_iteration with first == 0 continues the
+ *     call before it and reads rho and G from the workspace that call left;
+ *   - the pointer must be 256-byte aligned, which every `tensor.data_ptr()` of a fresh torch allocation is: the blocks
+ *     are carved at multiples of 256 bytes from it and the kernels rely on 16-byte aligned rows.  The annotation-count
+ *     and regions-sweep entry points align the pointer themselves (their queries include the 256 bytes that may cost).
  */
 #ifndef PYANNOTE_AMD_H
 #define PYANNOTE_AMD_H

@@ -104,7 +104,9 @@ def test_capacity_too_small_is_reported_and_nothing_is_written_past_it(gpu_devic
     tracks = torch.full((K * cap + guard,), -7, dtype=torch.int32, device=gpu_device)
     counts = torch.full((K + guard,), -7, dtype=torch.int32, device=gpu_device)
     nbytes = int(lib.pa_binarize_regions_workspace_bytes(T, K, cap))
-    workspace = torch.zeros(nbytes + 8 * guard, dtype=torch.uint8, device=gpu_device)
+    # (0xFF bytes, the `ones` fill of tests/hostile_workspace.py: NaN / -1 wherever the kernels read before they write)
+    from hostile_workspace import fill_bytes
+    workspace = fill_bytes("ones", nbytes + 8 * guard, gpu_device)
     workspace[nbytes:] = 0xA5
     on = np.full(K, 0.5, dtype=np.float32)
     zero = np.zeros(K, dtype=np.float64)
