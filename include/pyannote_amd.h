@@ -655,6 +655,23 @@ int pa_aggregate(const float* scores, int C, int F, int K, const int32_t* start_
                  const double* window, const double* warm, float epsilon, float missing, int skip_average,
                  float* out, void* stream);
 
+/* pa_aggregate for a ragged list of files in ONE launch (detection pipelines on a list of files, DESIGN.md section
+ * 32).  scores (total_chunks, F, S) on the device: the chunks of all files in file order, as pa_seg_forward_files
+ * leaves them; fp32, or (scores_uint8) the uint8 hard multilabel output, whose values count as 0.f / 1.f.  DEVICE
+ * tables: chunk0 (num_files + 1) int32, file f owns chunks chunk0[f] .. chunk0[f + 1] - 1; row0 (num_files + 1) int32
+ * non-decreasing, file f owns rows row0[f] .. row0[f + 1] - 1 of `out`; T (num_files) int32 <= row0[f + 1] - row0[f],
+ * the frames kept for the file.  All files share the chunk grid: start_frame (max_chunks) int32 is indexed by a
+ * chunk's position in its file, max_chunks >= every file's chunk count.  window, warm, epsilon, missing,
+ * skip_average: as for pa_aggregate.  any = 0: K = S (fp32 scores only); any = 1: K = 1 and a chunk's value at a frame
+ * is the maximum of its S columns, NaN when one of them is (np.max).
+ * out (rows, K) fp32, rows = row0[num_files]: rows row0[f] .. row0[f] + T[f] - 1 equal, bit for bit, the first T[f]
+ * rows pa_aggregate gives for file f's chunks alone (collapsed first, with `any`); every other row is NaN.  A file
+ * without chunks owns no rows.  uint8 scores with any = 0 are refused (3). */
+int pa_aggregate_files(const void* scores, int scores_uint8, int total_chunks, int F, int S, int any, int num_files,
+                       const int32_t* chunk0, const int32_t* row0, const int32_t* T, const int32_t* start_frame,
+                       int max_chunks, const double* window, const double* warm, float epsilon, float missing,
+                       int skip_average, long rows, float* out, void* stream);
+
 /* Hysteresis thresholding of an aggregated score array into per-class region lists, replaces `Binarize.__call__`
  * (utils/signal.py:254-318) applied to every class, `Annotation.support(collar)` and the min_duration_on deletion:
  * scores (T,K) fp32 row-major on the device (as pa_aggregate leaves it), K <= 16.  onset / offset (K) fp32 and
@@ -709,6 +726,38 @@ int pa_regions_sweep_emit(const float* scores, int T, int K, int L, const int32_
                           const double* min_duration_on, const double* min_duration_off, double start, double duration,
                           double step, long rows, double* regions, int32_t* tracks, int32_t* job_off,
                           int32_t* launches, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- the regions of every (file, class) of a ragged list of files from one pass (csrc/regions_files.hip, DESIGN.md
+ *      section 32) ---- */
+
+/* scores (rows, K) fp32 on the device as pa_aggregate_files leaves it, K <= 16.  HOST arrays: row0 (num_files + 1)
+ * int32, row0[0] = 0, non-decreasing multiples of 64, rows = row0[num_files]; T (num_files) int32, 0 <= T[f] <=
+ * row0[f + 1] - row0[f]; onset / offset (K) fp32 and min_duration_on / min_duration_off (K) fp64, one set for all
+ * files.  For every file f and class k the region list and the track positions are, bit for bit, what
+ * pa_binarize_regions gives on rows row0[f] .. row0[f] + T[f] - 1 alone with the same parameters: times are counted
+ * from the file's own frame 0, nothing is merged across files, T[f] < 2 gives empty lists.  Two phases, because the
+ * row buffers are sized from counts:
+ *   pa_binarize_regions_files_count   n_raw (K) int32, HOST, overwritten: the regions of every class, over all files,
+ *                                     before any clean-up.
+ *   pa_binarize_regions_files_emit    takes those counts back (other counts than the scores have: 3); regions
+ *                                     (rows_out, 2) fp64 and tracks (rows_out) int32 (optional, NULL) on the device,
+ *                                     list after list in (file, class) order, each in time order; list_off
+ *                                     (num_files K + 1) int32 on the device: list f K + k owns rows list_off[f K + k]
+ *                                     .. list_off[f K + k + 1].  rows_out >= the sum of n_raw.
+ * `workspace` (device): pa_binarize_regions_files_workspace_bytes(rows, K, num_files, raw_rows), raw_rows = the sum of
+ * n_raw (0 for the counting phase).  K outside 1..16, NaN thresholds, durations or grid, row0 that decreases or is no
+ * multiple of 64, T[f] outside its file's rows, more than 65 535 files and a workspace below the stated size are
+ * refused before any launch (3, pa_last_error) with every output untouched.  No workgroup waits for another, no
+ * floating-point atomics, every loop is bounded by an argument.  Both calls wait for the stream. */
+size_t pa_binarize_regions_files_workspace_bytes(long rows, int K, int num_files, long raw_rows);
+int pa_binarize_regions_files_count(const float* scores, int K, int num_files, const int32_t* row0, const int32_t* T,
+                                    const float* onset, const float* offset, int32_t* n_raw, void* workspace,
+                                    size_t workspace_bytes, void* stream);
+int pa_binarize_regions_files_emit(const float* scores, int K, int num_files, const int32_t* row0, const int32_t* T,
+                                   const float* onset, const float* offset, const double* min_duration_on,
+                                   const double* min_duration_off, double start, double duration, double step,
+                                   const int32_t* n_raw, long rows_out, double* regions, int32_t* tracks,
+                                   int32_t* list_off, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- audio front door (core/io.py:223-265) ---- */
 

@@ -352,15 +352,13 @@ int pa_topk_binarize(const int32_t* act, const uint8_t* count, int T, int K, int
 // ---------------------------------------------------------------------------------------------
 namespace pa {
 
-__global__ __launch_bounds__(256) void k_aggregate(const float* __restrict__ scores, int C, int F, int K,
-                                                   const int* __restrict__ start, int T,
-                                                   const double* __restrict__ window,
-                                                   const double* __restrict__ warm, float epsilon,
-                                                   float missing, int skip_average,
-                                                   float* __restrict__ out) {
-  const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (idx >= (long)T * K) return;
-  const int t = (int)(idx / K), k = (int)(idx % K);
+// The walk of one (frame t, class) over the chunks that cover t, shared by k_aggregate and k_aggregate_files:
+// `score(c, f)` is the value of chunk c at its frame f; start (C) is non-decreasing.
+template <class Score>
+__device__ __forceinline__ float aggregate_gather(Score score, int C, int F, const int* __restrict__ start, int t,
+                                                  const double* __restrict__ window,
+                                                  const double* __restrict__ warm, float epsilon, float missing,
+                                                  int skip_average) {
   // first chunk c with start[c] + F > t (start is non-decreasing)
   int lo = 0, hi = C;
   while (lo < hi) {
@@ -371,7 +369,7 @@ __global__ __launch_bounds__(256) void k_aggregate(const float* __restrict__ sco
   float agg = 0.f, cnt = 0.f, msk = 0.f;
   for (int c = lo; c < C && start[c] <= t; ++c) {
     const int f = t - start[c];
-    const float x = scores[((long)c * F + f) * K + k];
+    const float x = score(c, f);
     const bool nan = x != x;
     const double m = nan ? 0.0 : 1.0;
     // ((score * mask) * hamming) * warm_up and ((mask * hamming) * warm_up), as numpy evaluates them
@@ -381,6 +379,71 @@ __global__ __launch_bounds__(256) void k_aggregate(const float* __restrict__ sco
   }
   float v = skip_average ? agg : agg / fmaxf(cnt, epsilon);
   if (msk == 0.f) v = missing;
+  return v;
+}
+
+__global__ __launch_bounds__(256) void k_aggregate(const float* __restrict__ scores, int C, int F, int K,
+                                                   const int* __restrict__ start, int T,
+                                                   const double* __restrict__ window,
+                                                   const double* __restrict__ warm, float epsilon,
+                                                   float missing, int skip_average,
+                                                   float* __restrict__ out) {
+  const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= (long)T * K) return;
+  const int t = (int)(idx / K), k = (int)(idx % K);
+  out[idx] = aggregate_gather([&](int c, int f) { return scores[((long)c * F + f) * K + k]; }, C, F, start, t, window,
+                              warm, epsilon, missing, skip_average);
+}
+
+// The overlap-add of a RAGGED LIST OF FILES in one launch.  scores (total_chunks, F, S), VT = float or uint8_t: the
+// chunks of all files in file order; file f owns chunks chunk0[f] .. chunk0[f + 1] - 1 and output rows row0[f] ..
+// row0[f + 1] - 1, of which the first T[f] are its frames and the rest is written as NaN.  All files share the chunk
+// grid: start (max_chunks) is indexed by a chunk's position in its file.  `any`: K = 1 and a chunk's value at a frame
+// is the maximum of its S columns, NaN if one of them is (np.max); otherwise K = S.  One thread per (row, class) walks
+// the chunks of ITS file like k_aggregate does: row row0[f] + t is bit for bit row t of pa_aggregate on file f alone.
+__device__ __forceinline__ float chunk_score(float v) { return v; }
+__device__ __forceinline__ float chunk_score(uint8_t v) { return v ? 1.f : 0.f; }   // a hard decision
+
+template <typename VT>
+__global__ __launch_bounds__(256) void k_aggregate_files(const VT* __restrict__ scores, int total_chunks, int F, int S,
+                                                         int any, int num_files, const int* __restrict__ chunk0,
+                                                         const int* __restrict__ row0, const int* __restrict__ T,
+                                                         const int* __restrict__ start, int max_chunks,
+                                                         const double* __restrict__ window,
+                                                         const double* __restrict__ warm, float epsilon,
+                                                         float missing, int skip_average, long rows,
+                                                         float* __restrict__ out) {
+  const int K = any ? 1 : S;
+  const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= rows * K) return;
+  const long row = idx / K;
+  const int k = (int)(idx % K);
+  int lo = 0, hi = num_files;   // first file with row0[file + 1] > row (row0 is non-decreasing)
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (row0[mid + 1] > row) hi = mid;
+    else lo = mid + 1;
+  }
+  float v = __builtin_nanf("");
+  if (lo < num_files && row >= row0[lo] && row - row0[lo] < T[lo]) {
+    const int first = max(chunk0[lo], 0);
+    const int C = min(min(chunk0[lo + 1], total_chunks) - first, max_chunks);   // (never past either table)
+    const VT* mine = scores + (long)first * F * S;
+    v = aggregate_gather(
+        [&](int c, int f) {
+          const VT* p = mine + ((long)c * F + f) * S;
+          if (!any) return chunk_score(p[k]);
+          float best = chunk_score(p[0]);
+          for (int s = 1; s < S; ++s) {
+            const float y = chunk_score(p[s]);
+            // np.max propagates NaN; otherwise the larger value
+            if (y != y || best != best) best = __builtin_nanf("");
+            else best = y > best ? y : best;
+          }
+          return best;
+        },
+        C, F, start, (int)(row - row0[lo]), window, warm, epsilon, missing, skip_average);
+  }
   out[idx] = v;
 }
 
@@ -396,6 +459,34 @@ int pa_aggregate(const float* scores, int C, int F, int K, const int32_t* start_
   hipLaunchKernelGGL(pa::k_aggregate, dim3(pa::cdiv((long)T * K, 256)), dim3(256), 0, (hipStream_t)stream,
                      scores, C, F, K, start_frame, T, window, warm, epsilon, missing, skip_average, out);
   PA_CHECK_LAUNCH("pa_aggregate");
+  return 0;
+}
+
+int pa_aggregate_files(const void* scores, int scores_uint8, int total_chunks, int F, int S, int any, int num_files,
+                       const int32_t* chunk0, const int32_t* row0, const int32_t* T, const int32_t* start_frame,
+                       int max_chunks, const double* window, const double* warm, float epsilon, float missing,
+                       int skip_average, long rows, float* out, void* stream) {
+  PA_REQUIRE(total_chunks >= 0 && F > 0 && S > 0 && num_files >= 0 && max_chunks >= 0 && rows >= 0,
+             "pa_aggregate_files: a negative size (or no frame, no class)");
+  PA_REQUIRE(any || !scores_uint8, "pa_aggregate_files: uint8 scores are the hard multilabel output, any = 1 only");
+  const int K = any ? 1 : S;
+  PA_REQUIRE(rows * K <= 0x7fffffffL * 256, "pa_aggregate_files: %ld rows are too many for one launch", rows);
+  if (rows == 0) return 0;
+  PA_REQUIRE(chunk0 && row0 && (T || num_files == 0) && window && warm && out && (scores || total_chunks == 0) &&
+                 (start_frame || max_chunks == 0),
+             "pa_aggregate_files: null array");
+  pa::ProfScope prof("k_aggregate_files", stream, 3.0 * total_chunks * (double)F * S,
+                     (scores_uint8 ? 1.0 : 4.0) * total_chunks * (double)F * S + 4.0 * rows * K);
+  const dim3 grid(pa::cdiv(rows * K, 256)), block(256);
+  if (scores_uint8)
+    hipLaunchKernelGGL(pa::k_aggregate_files<uint8_t>, grid, block, 0, (hipStream_t)stream, (const uint8_t*)scores,
+                       total_chunks, F, S, any, num_files, chunk0, row0, T, start_frame, max_chunks, window, warm,
+                       epsilon, missing, skip_average, rows, out);
+  else
+    hipLaunchKernelGGL(pa::k_aggregate_files<float>, grid, block, 0, (hipStream_t)stream, (const float*)scores,
+                       total_chunks, F, S, any, num_files, chunk0, row0, T, start_frame, max_chunks, window, warm,
+                       epsilon, missing, skip_average, rows, out);
+  PA_CHECK_LAUNCH("pa_aggregate_files");
   return 0;
 }
 

@@ -15,9 +15,11 @@
 //   rg_scan_counts     one wave per slot: exclusive scan of the chunk counts
 //   rg_emit_events     the n-th on-event and the n-th off-event of a slot are its region n
 //   rg_drop_empty, rg_merge_gaps, rg_drop_short   one workgroup per region list: order-preserving compactions
-// What a frame's map is made from is the one thing a step can be generic over: a MAP type provides
-// `frame_map(scores, i, T, K)` (RegionParams here, SweepGroup in regions_sweep.hip).  Everything else that differs
-// between the callers is an argument.
+// What a frame's map is made from, and where a frame lies in its file, are the things a step can be generic over: a
+// MAP type provides `frame_map(scores, i, T, K)` and the three questions of RegionOneFile below (RegionParams here,
+// SweepGroup in regions_sweep.hip: rows 0 .. T - 1 are one file; RegionFiles in regions_files.hip: the rows are the
+// concatenation of many files, each with a first frame, a last frame and times of its own).  Everything else that
+// differs between the callers is an argument.
 // Times are float64 and bit-identical to the host's `0.5 * (s + (s + duration))`, `s = start + i * step`: the files are
 // compiled without FMA contraction and the products / sums are the _rn intrinsics.
 #pragma once
@@ -33,16 +35,23 @@ constexpr int RG_MAXK = 16;
 constexpr uint32_t RG_IDENTITY = 0xffff0000u;     // inactive -> inactive, active -> active
 constexpr double RG_PRECISION = 1e-6;             // pyannote.core SEGMENT_PRECISION
 
+// where row i of the scores lies when rows 0 .. T - 1 are ONE file: the part of a MAP type that is the same for every
+// caller whose rows are one file
+struct RegionOneFile {
+  __device__ __forceinline__ bool first_frame(long i, int) const { return i == 0; }      // no state comes before it
+  __device__ __forceinline__ bool last_frame(long i, int T) const { return i == T - 1; } // closes what is open
+  __device__ __forceinline__ bool no_frame(long i, int T) const { return i >= T; }       // past the end: no event
+  __device__ __forceinline__ long time_frame(long i) const { return i; }                 // the index its time is of
+};
+
 // slot k = class k = column k of the scores
-struct RegionParams {
+struct RegionParams : RegionOneFile {
   float onset[RG_MAXK], offset[RG_MAXK];
   double min_on[RG_MAXK], min_off[RG_MAXK];
   double start, duration, step;
 
-  // the maps of frame i (identity past the end).  Frame 0 sets the state: `is_active = y > onset`, a constant map.
-  __device__ __forceinline__ uint32_t frame_map(const float* __restrict__ scores, long i, int T, int K) const {
-    if (i >= T) return RG_IDENTITY;
-    const float* row = scores + i * K;
+  // the maps of one frame, `row` its K scores.  A first frame sets the state: `is_active = y > onset`, a constant map.
+  __device__ __forceinline__ uint32_t row_map(const float* __restrict__ row, int K, bool first) const {
     uint32_t f0 = 0, f1 = 0;
 #pragma unroll
     for (int k = 0; k < RG_MAXK; ++k)
@@ -51,8 +60,14 @@ struct RegionParams {
         f0 |= (uint32_t)(y > onset[k]) << k;
         f1 |= (uint32_t)(!(y < offset[k])) << k;
       }
-    if (i == 0) f1 = f0;
+    if (first) f1 = f0;
     return f0 | (f1 << 16);
+  }
+
+  // the maps of frame i (identity past the end)
+  __device__ __forceinline__ uint32_t frame_map(const float* __restrict__ scores, long i, int T, int K) const {
+    if (i >= T) return RG_IDENTITY;
+    return row_map(scores + i * K, K, i == 0);
   }
 };
 
@@ -172,14 +187,15 @@ __device__ __forceinline__ void rg_apply_tile(const float* __restrict__ scores, 
     }
     if (w == 0) pre = RG_IDENTITY;
     exc = rg_compose(pre, exc);
-    const uint32_t before = ((state & (exc >> 16)) | (~state & exc)) & 0xffffu;
+    uint32_t before = ((state & (exc >> 16)) | (~state & exc)) & 0xffffu;
+    if (f.first_frame(i, T)) before = 0;   // (what frame 0 finds anyway; the state a previous file was left in)
     const uint32_t after = ((before & (m >> 16)) | (~before & m)) & 0xffffu;
     uint32_t on = ~before & after & 0xffffu, off = before & ~after;
-    if (i == T - 1) {   // a region still open closes on the last frame; one that would open there is empty
+    if (f.last_frame(i, T)) {   // a region still open closes on the last frame; one that would open there is empty
       off = before;
       on = 0;
     }
-    if (i >= T) on = off = 0;
+    if (f.no_frame(i, T)) on = off = 0;
     if (events && i < T) events[i] = on | (off << 16);
     const int chunk = blockIdx.x * (RG_TILE / RG_CHUNK) + q * 4 + w;
 #pragma unroll
@@ -214,18 +230,20 @@ struct RegionRows {
 
 // On- and off-events of a slot alternate, starting with an on-event: region n runs from the n-th on-event to the
 // n-th off-event, and the off-event's n is (number of on-events up to and including its frame) - 1.
-// `events`, `chunk_off`: as rg_apply_tile and rg_scan_counts left them.  `rows_of(k)`: the RegionRows of slot k, asked
-// for by the lanes that hold one of its events only.
-template <class RowsOf>
-__device__ __forceinline__ void rg_emit_events(const uint32_t* __restrict__ events, int T, int slots, double start,
-                                               double duration, double step, const int* __restrict__ chunk_off,
-                                               int nchunks, RowsOf rows_of, double* __restrict__ raw) {
+// `events`, `chunk_off`: as rg_apply_tile and rg_scan_counts left them (`nchunks`: the entries between two slots of
+// `chunk_off`).  `f.time_frame(i)`: the frame index the time of row i is computed from.  `rows_of(k)`: the RegionRows
+// of slot k, asked for by the lanes that hold one of its events only.
+template <class Map, class RowsOf>
+__device__ __forceinline__ void rg_emit_events(const uint32_t* __restrict__ events, int T, int slots, const Map& f,
+                                               double start, double duration, double step,
+                                               const int* __restrict__ chunk_off, int nchunks, RowsOf rows_of,
+                                               double* __restrict__ raw) {
   const int lane = threadIdx.x & 63;
   const long i = (long)blockIdx.x * RG_THREADS + threadIdx.x;
   const int chunk = (int)(i >> 6);
   const uint32_t ev = i < T ? events[i] : 0u;
   if (__ballot(ev != 0u) == 0ull) return;
-  const double t = rg_time(i, start, duration, step);
+  const double t = rg_time(f.time_frame(i), start, duration, step);
   const unsigned long long upto = ~0ull >> (63 - lane);   // lanes 0..lane
 #pragma unroll
   for (int k = 0; k < RG_MAXK; ++k)

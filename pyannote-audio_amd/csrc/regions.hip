@@ -44,7 +44,7 @@ __global__ __launch_bounds__(RG_THREADS) void k_regions_emit(const uint32_t* __r
                                                              RegionParams p, const int* __restrict__ chunk_off,
                                                              int nchunks, int capacity,
                                                              double* __restrict__ raw) {
-  rg_emit_events(events, T, K, p.start, p.duration, p.step, chunk_off, nchunks,
+  rg_emit_events(events, T, K, p, p.start, p.duration, p.step, chunk_off, nchunks,
                  [=](int k) { return RegionRows{(long)k * capacity, capacity}; }, raw);
 }
 

@@ -26,7 +26,7 @@
 
 namespace pa {
 
-struct SweepGroup {
+struct SweepGroup : RegionOneFile {
   float onset[RG_MAXK], offset[RG_MAXK];   // unused slots: +inf / -inf, the identity map, never an event
   int32_t lane[RG_MAXK];                   // lane id of every slot, -1: unused
   int32_t cls;                             // the column every slot reads
@@ -94,7 +94,7 @@ __global__ __launch_bounds__(RG_THREADS) void k_sweep_emit(const uint32_t* __res
                                                            const int* __restrict__ raw_off,
                                                            double* __restrict__ raw) {
   const int32_t* lane_of = groups[blockIdx.y].lane;
-  rg_emit_events(events + (long)blockIdx.y * T, T, RG_MAXK, start, duration, step,
+  rg_emit_events(events + (long)blockIdx.y * T, T, RG_MAXK, RegionOneFile{}, start, duration, step,
                  chunk_off + (long)blockIdx.y * RG_MAXK * nchunks, nchunks,
                  [=](int s) {
                    const int id = lane_of[s];

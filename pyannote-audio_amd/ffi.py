@@ -263,6 +263,14 @@ _OPTIONAL: list[tuple] = [
     ("pa_regions_sweep_emit", [c_fp, C.c_int, C.c_int, C.c_int, c_fp, c_fp, c_fp, c_fp, C.c_int, c_fp, c_fp, c_fp,
                                C.c_double, C.c_double, C.c_double, C.c_long, c_fp, c_fp, c_fp, c_fp, c_fp, C.c_size_t,
                                c_fp], C.c_int),
+    ("pa_aggregate_files", [c_fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_fp, c_fp, c_fp, c_fp, C.c_int,
+                            c_fp, c_fp, C.c_float, C.c_float, C.c_int, C.c_long, c_fp, c_fp], C.c_int),
+    ("pa_binarize_regions_files_workspace_bytes", [C.c_long, C.c_int, C.c_int, C.c_long], C.c_size_t),
+    ("pa_binarize_regions_files_count", [c_fp, C.c_int, C.c_int, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, C.c_size_t,
+                                         c_fp], C.c_int),
+    ("pa_binarize_regions_files_emit", [c_fp, C.c_int, C.c_int, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, C.c_double,
+                                        C.c_double, C.c_double, c_fp, C.c_long, c_fp, c_fp, c_fp, c_fp, C.c_size_t,
+                                        c_fp], C.c_int),
     ("pa_resample_poly", [c_fp, C.c_long, c_fp, C.c_int, C.c_int, C.c_int, C.c_int, c_fp, C.c_long, c_fp],
      C.c_int),
     ("pa_plda_transform", [c_fp, C.c_int, C.c_int, C.c_int, C.c_int, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp],

@@ -186,6 +186,185 @@ def binarize_regions(scores: torch.Tensor, frames: SlidingWindow, onset, offset,
     return out, [packed_tracks[bounds[k]:bounds[k + 1]] for k in range(K)]
 
 
+# ------------------------------------------------------------------------- a ragged list of files in shared launches
+#: rows of a file in the packed aggregate start at a multiple of this (RG_CHUNK of csrc/regions.h: a 64-frame count of
+#: the region kernels never straddles two files)
+FILES_ROW_ALIGN = 64
+
+
+def files_layout(num_samples_per_file, inference):
+    """Where the chunks and the aggregated rows of several files lie when they share launches (`forward_files`,
+    `aggregate_files`, `binarize_regions_files`) -> (chunks_per_file, chunk0, row0, T), int32 arrays of N, N + 1,
+    N + 1 and N entries: file f owns chunks chunk0[f]:chunk0[f + 1] and rows row0[f]:row0[f + 1] of the packed
+    aggregate, of which the first T[f] are its frames -- the rows `Inference.slide` / `slide_device` return for the
+    file (the padding of a zero-padded last chunk cut off by the loose crop).  row0[f] is a multiple of 64.  Host
+    arithmetic only, with `Inference.num_chunks`, `frame_geometry` and the crop of `slide_device`."""
+    from .core import Segment
+    from .inference import Inference
+    model = inference.model
+    sample_rate = model.audio.sample_rate
+    window_size = model.audio.get_num_samples(inference.duration)
+    step_size = round(inference.step * sample_rate)
+    chunks = SlidingWindow(start=0.0, duration=inference.duration, step=inference.step)
+    counts, kept = [], []
+    for num_samples in num_samples_per_file:
+        num_samples = int(num_samples)
+        n, has_last = Inference.num_chunks(num_samples, window_size, step_size)
+        _, num_frames, out_frames = frame_geometry(chunks, model.receptive_field, n + has_last)
+        if has_last:
+            (first, stop), = out_frames.crop(Segment(0.0, num_samples / sample_rate), mode="loose",
+                                             return_ranges=True)
+            num_frames = min(stop, num_frames) - max(first, 0)
+        counts.append(n + has_last)
+        kept.append(max(num_frames, 0))
+    counts = np.asarray(counts, dtype=np.int32).reshape(-1)
+    T = np.asarray(kept, dtype=np.int32).reshape(-1)
+    owned = (T.astype(np.int64) + FILES_ROW_ALIGN - 1) // FILES_ROW_ALIGN * FILES_ROW_ALIGN
+    chunk0 = np.concatenate([[0], np.cumsum(counts, dtype=np.int64)])
+    row0 = np.concatenate([[0], np.cumsum(owned)])
+    if chunk0[-1] > np.iinfo(np.int32).max or row0[-1] > np.iinfo(np.int32).max:
+        raise ValueError("files_layout: more than 2^31 - 1 chunks or rows in one group")
+    return counts, chunk0.astype(np.int32), row0.astype(np.int32), T
+
+
+def _files_tables(row0, T, what):
+    """the row tables of a group of files, checked as the kernels' entry points check them"""
+    row0 = np.ascontiguousarray(row0, dtype=np.int32).reshape(-1)
+    T = np.ascontiguousarray(T, dtype=np.int32).reshape(-1)
+    if len(row0) != len(T) + 1:
+        raise ValueError(f"{what}: row0 has one entry more than T")
+    if len(T) > 65535:
+        raise ValueError(f"{what}: {len(T)} files, at most 65535 share a call")
+    owned = np.diff(row0.astype(np.int64))
+    if row0[0] != 0 or (owned < 0).any() or (row0 % FILES_ROW_ALIGN).any():
+        raise ValueError(f"{what}: row0 starts at 0 and is a non-decreasing table of multiples of {FILES_ROW_ALIGN}")
+    if (T < 0).any() or (T > owned).any():
+        raise ValueError(f"{what}: a file keeps more frames than it owns rows")
+    return row0, T
+
+
+def aggregate_files(scores: torch.Tensor, chunk0, row0, T, chunks: SlidingWindow, frames: SlidingWindow,
+                    any: bool = False, warm_up: Tuple[float, float] = (0.0, 0.0), epsilon: float = 1e-12,
+                    hamming: bool = False, missing: float = np.nan, skip_average: bool = False,
+                    packed: bool = False):
+    """`aggregate_device` of several files in ONE launch (`pa_aggregate_files`).  scores: (sum of chunks, F, S) device
+    tensor, the files' chunks in file order as `forward_files` leaves them -- float32, or the uint8 hard multilabel
+    output (with `any` only); chunk0, row0, T: as `files_layout` returns them.  `any`: the chunks collapse to one
+    class first, the maximum over the S columns (VoiceActivityDetection's `any_speaker`).
+    -> ([(T[f], K) float32 device tensors, views of one buffer], frame grid); with `packed`, the buffer itself,
+    (row0[-1], K): file f's rows at row0[f], NaN in the padding rows.  Every file's rows are bit for bit those of
+    `aggregate_device` on its chunks alone."""
+    if not (isinstance(scores, torch.Tensor) and scores.is_cuda and scores.dim() == 3
+            and scores.dtype in (torch.float32, torch.uint8)):
+        raise ValueError("aggregate_files expects a (chunks, frames, classes) float32 or uint8 device tensor")
+    if scores.dtype == torch.uint8 and not any:
+        raise ValueError("aggregate_files: uint8 scores are hard decisions, aggregated with any=True only")
+    x = scores.contiguous()
+    total, F, S = x.shape
+    row0, T = _files_tables(row0, T, "aggregate_files")
+    chunk0 = np.ascontiguousarray(chunk0, dtype=np.int32).reshape(-1)
+    N = len(T)
+    counts = np.diff(chunk0.astype(np.int64))
+    if len(chunk0) != N + 1 or chunk0[0] != 0 or (counts < 0).any() or chunk0[-1] != total:
+        raise ValueError("aggregate_files: chunk0 is a non-decreasing table from 0 to the number of chunks, one entry "
+                         "more than there are files")
+    most = int(counts.max()) if N else 0
+    starts, _, out_frames = frame_geometry(chunks, frames, most)
+    covered = {int(c): frame_geometry(chunks, frames, int(c))[1] if c else 0 for c in np.unique(counts)}
+    for f in np.flatnonzero(T > 0):
+        if T[f] > covered[int(counts[f])]:
+            raise ValueError(f"aggregate_files: file {f} keeps {T[f]} frames, its {counts[f]} chunks cover fewer")
+    window = np.hamming(F) if hamming else np.ones(F)
+    warm = np.ones(F)
+    left = round(warm_up[0] / chunks.duration * F)
+    right = round(warm_up[1] / chunks.duration * F)
+    warm[:left] = epsilon
+    warm[F - right:] = epsilon
+    dev = x.device
+    K = 1 if any else S
+    rows = int(row0[-1])
+    with torch.cuda.device(dev):
+        # ONE upload: [window | warm-up] (8-byte entries), then [chunk0 | row0 | T | start frames]
+        table = np.concatenate([np.ascontiguousarray(window, dtype=np.float64), warm]).view(np.uint8)
+        ints = np.concatenate([chunk0, row0, T, starts.astype(np.int32)]).astype(np.int32)
+        table = torch.from_numpy(np.concatenate([table, ints.view(np.uint8)])).to(dev)
+        base = table.data_ptr()
+        at = base + 16 * F
+        out = torch.empty((rows, K), dtype=torch.float32, device=dev)
+        ffi.check(ffi.load().pa_aggregate_files(
+            ffi.ptr(x) if x.numel() else None, int(x.dtype == torch.uint8), total, F, S, int(bool(any)), N,
+            ffi.c_fp(at), ffi.c_fp(at + 4 * (N + 1)), ffi.c_fp(at + 8 * (N + 1)), ffi.c_fp(at + 8 * (N + 1) + 4 * N),
+            most, ffi.c_fp(base), ffi.c_fp(base + 8 * F), float(epsilon), float(missing), int(skip_average), rows,
+            ffi.ptr(out) if rows else None, ffi.stream()), "pa_aggregate_files")
+    if packed:
+        return out, out_frames
+    return [out[a:a + t] for a, t in zip(row0[:-1].tolist(), T.tolist())], out_frames
+
+
+def binarize_regions_files(scores: torch.Tensor, row0, T, frames: SlidingWindow, onset, offset, min_duration_on=0.0,
+                           min_duration_off=0.0, return_tracks: bool = False):
+    """`binarize_regions` of every file of a packed aggregate at once (`pa_binarize_regions_files_count` / `_emit`,
+    csrc/regions_files.hip).  scores: the (row0[-1], K) float32 device tensor `aggregate_files(..., packed=True)`
+    returns; row0, T: as `files_layout` returns them; one set of per-class parameters for all files (scalars are
+    shared).  -> per file the list of K float64 arrays (n, 2) `binarize_regions` returns for the file's rows alone
+    (times from the file's own frame 0), bit for bit; with `return_tracks`, also per file the K arrays of track
+    positions.  The whole group crosses to the host in one copy of the packed rows and one of the offset table."""
+    if not (isinstance(scores, torch.Tensor) and scores.is_cuda and scores.dim() == 2
+            and scores.dtype == torch.float32):
+        raise ValueError("binarize_regions_files expects a (rows, classes) float32 device tensor")
+    x = scores.contiguous()
+    rows, K = x.shape
+    row0, T = _files_tables(row0, T, "binarize_regions_files")
+    N = len(T)
+    if int(row0[-1]) != rows:
+        raise ValueError(f"binarize_regions_files: the files own {int(row0[-1])} rows, the scores have {rows}")
+    if not 1 <= K <= 16:
+        raise ValueError(f"binarize_regions_files: {K} classes, 1..16 supported")
+
+    def per_class(v, dtype):
+        return np.ascontiguousarray(np.broadcast_to(np.asarray(v, dtype=dtype), (K,)))
+
+    on, off = per_class(onset, np.float32), per_class(offset, np.float32)
+    d_on, d_off = per_class(min_duration_on, np.float64), per_class(min_duration_off, np.float64)
+    if np.isnan(on).any() or np.isnan(off).any() or np.isnan(d_on).any() or np.isnan(d_off).any():
+        raise ValueError("binarize_regions_files: a threshold or a duration is NaN")
+    lib = ffi.load()
+    dev = x.device
+    with torch.cuda.device(dev):
+        n_raw = np.zeros(K, dtype=np.int32)
+        nbytes = int(lib.pa_binarize_regions_files_workspace_bytes(rows, K, N, 0))
+        workspace = torch.empty(max(nbytes, 8), dtype=torch.uint8, device=dev)
+        ffi.check(lib.pa_binarize_regions_files_count(
+            ffi.ptr(x) if rows else None, K, N, row0.ctypes.data, T.ctypes.data, on.ctypes.data, off.ctypes.data,
+            n_raw.ctypes.data, ffi.ptr(workspace), nbytes, ffi.stream()), "pa_binarize_regions_files_count")
+        raw_rows = int(n_raw.sum(dtype=np.int64))
+        regions = torch.empty((raw_rows, 2), dtype=torch.float64, device=dev)
+        tracks = torch.empty(raw_rows, dtype=torch.int32, device=dev) if return_tracks else None
+        list_off = torch.empty(N * K + 1, dtype=torch.int32, device=dev)
+        nbytes = int(lib.pa_binarize_regions_files_workspace_bytes(rows, K, N, raw_rows))
+        if workspace.numel() < nbytes:
+            workspace = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        ffi.check(lib.pa_binarize_regions_files_emit(
+            ffi.ptr(x) if rows else None, K, N, row0.ctypes.data, T.ctypes.data, on.ctypes.data, off.ctypes.data,
+            d_on.ctypes.data, d_off.ctypes.data, float(frames.start), float(frames.duration), float(frames.step),
+            n_raw.ctypes.data, raw_rows, ffi.ptr(regions) if raw_rows else None,
+            ffi.ptr(tracks) if raw_rows and return_tracks else None, ffi.ptr(list_off), ffi.ptr(workspace), nbytes,
+            ffi.stream()), "pa_binarize_regions_files_emit")
+        offsets = list_off.cpu().numpy().astype(np.int64)
+        total = int(offsets[-1])
+        # one copy of the packed rows; the track positions ride along as a third float64 column (exact: they are
+        # small integers)
+        if return_tracks:
+            both = torch.cat([regions[:total], tracks[:total].to(torch.float64)[:, None]], dim=1).cpu().numpy()
+            host, host_tracks = np.ascontiguousarray(both[:, :2]), both[:, 2].astype(np.int32)
+        else:
+            host = regions[:total].cpu().numpy()
+    out = [[host[offsets[f * K + k]:offsets[f * K + k + 1]] for k in range(K)] for f in range(N)]
+    if not return_tracks:
+        return out
+    return out, [[host_tracks[offsets[f * K + k]:offsets[f * K + k + 1]] for k in range(K)] for f in range(N)]
+
+
 #: default budget of `binarize_regions_sweep`'s device workspace (event words, chunk tables and row buffers)
 SWEEP_WORKSPACE_BYTES = 1 << 30
 _SEGMENT_PRECISION = 1e-6

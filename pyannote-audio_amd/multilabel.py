@@ -18,6 +18,7 @@ import torch
 
 from .audio import Audio, AudioFile
 from .core import Annotation, SlidingWindowFeature, string_generator
+from .detection_batch import PackedDetection
 from .inference import Inference
 from .model import Problem, Resolution
 from .pipeline import ParamDict, Pipeline, Uniform
@@ -44,9 +45,12 @@ def regions_to_annotation(regions, positions, classes, uri) -> Annotation:
     return detection
 
 
-class MultiLabelSegmentation(Pipeline):
+class MultiLabelSegmentation(PackedDetection, Pipeline):
     """Hyper-parameters: `thresholds[label]` = onset, offset [, min_duration_on, min_duration_off]; the two
-    durations are top-level and shared between labels when `share_min_duration`."""
+    durations are top-level and shared between labels when `share_min_duration`.
+
+    A list of files goes through `apply_batch` (detection_batch.py): `pipeline(files, pack=True)` runs short files in
+    shared launches, with the Annotations of `apply`."""
 
     CACHED_SEGMENTATION = "cache/segmentation"
 
@@ -98,6 +102,17 @@ class MultiLabelSegmentation(Pipeline):
         else:
             self._min_duration_on = np.array([t["min_duration_on"] for t in per_label], dtype=np.float64)
             self._min_duration_off = np.array([t["min_duration_off"] for t in per_label], dtype=np.float64)
+
+    def _packed_detector(self) -> Optional[dict]:
+        """what `apply_batch(pack=...)` runs for a group of files, None: the per-file loop (a pre-aggregation hook is
+        host code between the network and the aggregation)"""
+        if self._segmentation.pre_aggregation_hook is not None:
+            return None
+        if not hasattr(self, "_onset"):
+            self.initialize()
+        return {"any": False, "hard": False, "onset": self._onset, "offset": self._offset,
+                "min_duration_on": self._min_duration_on, "min_duration_off": self._min_duration_off,
+                "classes": self._classes}
 
     def _aggregate(self, file: AudioFile, hook: Callable):
         """-> (frames, classes) float32 device tensor, frame grid"""

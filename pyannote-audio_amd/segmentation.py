@@ -85,14 +85,17 @@ class SegmentationEngine:
         """The chunks of several waveforms in shared launch groups (`pa_seg_forward_files`).  wavs: 1-D fp32 device
         tensors; file f contributes chunks_per_file[f] chunks, chunk c = wavs[f][c*stride : c*stride + num_samples]
         (zero padded past the end).  Returns what `forward_strided` returns, over the concatenation of all files'
-        chunks in file order; every file's rows equal, bit for bit, those of `forward_strided` on that file alone.
+        chunks in file order; every file's rows equal, bit for bit, those of `forward_strided` on that file alone (a
+        multi-label checkpoint returns its scores and no hard output, as there).
 
         A launch group holds at most `max_chunks` chunks: files are joined in order while they fit, and a file with
         more chunks than that is cut at the chunk boundaries `forward_strided` cuts it at."""
         lib = ffi.load()
         w = self.pack.struct
-        if not self.PACKS_FILES or not self.pack.powerset:
-            raise NotImplementedError("forward_files packs the powerset PyanNet model only")
+        if not self.PACKS_FILES:
+            raise NotImplementedError("forward_files packs the PyanNet model only")
+        if not self.pack.powerset:      # a multi-label checkpoint: scores only, as `forward_strided`
+            want_logp, want_multilabel = True, False
         counts = [int(c) for c in chunks_per_file]
         if len(counts) != len(wavs):
             raise ValueError("forward_files: one chunk count per waveform")

@@ -13,6 +13,7 @@ import numpy as np
 
 from .audio import AudioFile
 from .core import Annotation, SlidingWindowFeature
+from .detection_batch import PackedDetection
 from .diarization import Binarize
 from .inference import Inference
 from .pipeline import Pipeline, Uniform
@@ -24,9 +25,12 @@ def any_speaker(scores: np.ndarray) -> np.ndarray:
     return np.max(scores, axis=-1, keepdims=True)
 
 
-class VoiceActivityDetection(Pipeline):
+class VoiceActivityDetection(PackedDetection, Pipeline):
     """Hyper-parameters: onset / offset (fixed to 0.5 for powerset models, whose outputs are already
-    hard decisions), min_duration_on, min_duration_off."""
+    hard decisions), min_duration_on, min_duration_off.
+
+    A list of files goes through `apply_batch` (detection_batch.py): `pipeline(files, pack=True)` runs short files in
+    shared launches, with the Annotations of `apply`."""
 
     CACHED_SEGMENTATION = "cache/segmentation/inference"
 
@@ -73,6 +77,19 @@ class VoiceActivityDetection(Pipeline):
         self._binarize = Binarize(onset=self.onset, offset=self.offset,
                                   min_duration_on=self.min_duration_on,
                                   min_duration_off=self.min_duration_off)
+
+    def _packed_detector(self) -> Optional[dict]:
+        """what `apply_batch(pack=...)` runs for a group of files, None: the per-file loop.  The device rule is the
+        state-dependent one; the host `Binarize` of `apply` differs from it where offset > onset (see
+        tuning.DetectionTuner), so such a pipeline keeps the per-file loop."""
+        inference = self._segmentation
+        offset = self.offset or self.onset
+        if inference.pre_aggregation_hook is not any_speaker or offset > self.onset:
+            return None
+        specifications = inference.model.specifications
+        return {"any": True, "hard": bool(specifications.powerset) and not inference.skip_conversion,
+                "onset": self.onset, "offset": offset, "min_duration_on": self.min_duration_on,
+                "min_duration_off": self.min_duration_off, "classes": ["SPEECH"]}
 
     def apply(self, file: AudioFile, hook: Optional[Callable] = None) -> Annotation:
         """-> speech regions, every track labelled "SPEECH" (:161-203)"""
