@@ -1073,6 +1073,46 @@ int pa_permute_classes(const void* y2, long y2_batch_stride, long y2_frame_strid
                        const int32_t* perm, long perm_stride, int batch, int frames, int C1, int C2, void* out,
                        void* stream);
 
+/* ---- open-set speaker identification against an enrolled gallery (identification.py; csrc/identify.hip, DESIGN.md
+ *      section 33; no reference counterpart: the reference stops at DiarizeOutput.speaker_embeddings) ---- */
+
+/* Everything below is float64 on the device.  The distance of two rows is scipy.spatial.distance.cdist(., ., "cosine")
+ * bit for bit (the arithmetic of pa_cdist_cosine_f64), and the (rows, rows) matrix is never written: the second table is
+ * walked in tiles of pa_identify_tile() rows, whose values are merged into each row's running best.  The workspace holds
+ * of the two selecting calls holds the row norms of both tables and a transposed copy of the second one.
+ * Order of two values wherever one is selected: np.sort's -- by value, -0.0 equal to 0.0, NaN last -- and, among equal
+ * values, the lower row of the second table first (np.argsort(kind="stable")). */
+int pa_identify_tile(void);      /* rows of the second table per tile (256) */
+int pa_identify_max_top(void);   /* the largest K of pa_cohort_stats_f64 (512) */
+int pa_identify_max_k(void);     /* the largest k of pa_gallery_topk_f64 (64) */
+/* bytes of `workspace` of pa_cohort_stats_f64 (0: sizes it refuses) */
+size_t pa_cohort_stats_workspace_bytes(int M, int N, int D);
+/* The two statistics of adaptive score normalisation.  X (M, D), C (N, D) cohort rows.  Per row of X, with s[0..K) its K
+ * smallest distances to the cohort rows in ascending order:
+ *   mean[i] = (((s0 + s1) + s2) + ...) / K          stdev[i] = sqrt((((e0 + e1) + e2) + ...) / K), e = (s - mean) * (s - mean)
+ * -- np.cumsum(.)[-1], not np.sum: the additions run left to right and every operation is rounded on its own.
+ * 1 <= K <= min(N, pa_identify_max_top()): clipping K to the cohort is the caller's business.
+ * status (M) int32: 1 for a row of X whose norm is zero or not finite, whose mean and stdev are NaN; else 0.  A cohort
+ * row without a direction gives NaN distances, which sort last.  Four launches (norms, transposition, selection), no
+ * synchronisation. */
+int pa_cohort_stats_f64(const double* X, int M, const double* C, int N, int D, int K, double* mean, double* stdev,
+                        int32_t* status, void* workspace, size_t workspace_bytes, void* stream);
+/* bytes of `workspace` of pa_gallery_topk_f64 (0: sizes it refuses) */
+size_t pa_gallery_workspace_bytes(int M, int Ng, int D);
+/* Q (M, D) queries, G (Ng, D) gallery.  q_mean, q_std (M) and g_mean, g_std (Ng): all NULL or all given.  The value of
+ * pair (i, j) is its distance d without them and 0.5 * ((d - q_mean[i]) / q_std[i] + (d - g_mean[j]) / g_std[j]) with
+ * them, in that order of operations.  Per query: values (M, k) = the k smallest values, ascending, and indices (M, k)
+ * int32 = their gallery rows: np.argsort(row, kind="stable")[:k].  1 <= k <= min(Ng, pa_identify_max_k()). */
+int pa_gallery_topk_f64(const double* Q, int M, const double* G, int Ng, int D, const double* q_mean,
+                        const double* q_std, const double* g_mean, const double* g_std, int k, double* values,
+                        int32_t* indices, void* workspace, size_t workspace_bytes, void* stream);
+/* out[p] = the value of pair (iq[p], ig[p]) as pa_gallery_topk_f64 defines it, for P pairs; iq, ig (P) int32 on the
+ * device.  An index outside its table gives NaN.  One thread per pair takes the two norms and the dot product: one
+ * launch, no workspace. */
+int pa_gallery_pairs_f64(const double* Q, int M, const double* G, int Ng, int D, const double* q_mean,
+                         const double* q_std, const double* g_mean, const double* g_std, const int32_t* iq,
+                         const int32_t* ig, long P, double* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

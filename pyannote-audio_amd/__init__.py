@@ -24,5 +24,7 @@ from . import verification  # noqa: E402,F401
 from . import annotation_metrics  # noqa: E402,F401
 from . import evaluation  # noqa: E402,F401
 from . import tuning  # noqa: E402,F401
+from . import identification  # noqa: E402,F401
+from .identification import Gallery, SpeakerIdentification  # noqa: E402,F401
 from .metrics import (DiscreteDiarizationErrorRate, diarization_error_rate,  # noqa: E402,F401
                       discrete_diarization_error_rate, optimal_diarization_error_rate)

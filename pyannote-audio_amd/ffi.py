@@ -348,6 +348,17 @@ _OPTIONAL: list[tuple] = [
                        C.c_int, C.c_int, C.c_int, C.c_int, c_fp, c_fp], C.c_int),
     ("pa_permute_classes", [c_fp, C.c_long, C.c_long, C.c_long, C.c_int, c_fp, C.c_long, C.c_int, C.c_int, C.c_int,
                             C.c_int, c_fp, c_fp], C.c_int),
+    ("pa_identify_tile", [], C.c_int),
+    ("pa_identify_max_top", [], C.c_int),
+    ("pa_identify_max_k", [], C.c_int),
+    ("pa_cohort_stats_workspace_bytes", [C.c_int, C.c_int, C.c_int], C.c_size_t),
+    ("pa_cohort_stats_f64", [c_fp, C.c_int, c_fp, C.c_int, C.c_int, C.c_int, c_fp, c_fp, c_fp, c_fp, C.c_size_t, c_fp],
+     C.c_int),
+    ("pa_gallery_workspace_bytes", [C.c_int, C.c_int, C.c_int], C.c_size_t),
+    ("pa_gallery_topk_f64", [c_fp, C.c_int, c_fp, C.c_int, C.c_int, c_fp, c_fp, c_fp, c_fp, C.c_int, c_fp, c_fp, c_fp,
+                             C.c_size_t, c_fp], C.c_int),
+    ("pa_gallery_pairs_f64", [c_fp, C.c_int, c_fp, C.c_int, C.c_int, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, C.c_long, c_fp,
+                              c_fp], C.c_int),
 ]
 
 
