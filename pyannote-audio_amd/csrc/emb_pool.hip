@@ -32,14 +32,18 @@ __global__ __launch_bounds__(256) void k_stats_pool(const float* __restrict__ fe
   __syncthreads();
   if (threadIdx.x < S) {
     const int s = threadIdx.x;
-    float a = 0.f, q = 0.f;
+    // The weight sums in double: a sequential float32 sum of T' fractional weights is off by ~1e-6 of v1, and a channel
+    // whose offset is 1e5 times its spread turns that into a mean off by a tenth of the spread.  (One frame of weight 1:
+    // v1 rounds to 1, so mean = x and std = 0 exactly, as before.)
+    double a = 0.0, q = 0.0;
     for (int t = 0; t < Tp; ++t) {
-      a += ws[s][t];
-      q += ws[s][t] * ws[s][t];
+      const double w = (double)ws[s][t];
+      a += w;
+      q += w * w;
     }
-    const float v1 = a + 1e-8f;
-    v1s[s] = v1;
-    dens[s] = v1 - q / v1 + 1e-8f;
+    const double v1 = a + 1e-8;
+    v1s[s] = (float)v1;
+    dens[s] = (float)(v1 - q / v1 + 1e-8);
   }
   __syncthreads();
   if (c >= Cc) return;
@@ -127,15 +131,16 @@ __global__ __launch_bounds__(256) void k_stats_pool_rows(const float* __restrict
   __syncthreads();
   if (threadIdx.x < S) {
     const int s = threadIdx.x;
-    float a = 0.f, q = 0.f;
+    double a = 0.0, q = 0.0;   // in double, as in k_stats_pool
     for (int t = 0; t < Tp; ++t) {
-      a += ws[s][t];
-      q += ws[s][t] * ws[s][t];
+      const double w = (double)ws[s][t];
+      a += w;
+      q += w * w;
     }
     if (masks != nullptr) {
-      const float v1 = a + 1e-8f;
-      v1s[s] = v1;
-      dens[s] = v1 - q / v1 + 1e-8f;
+      const double v1 = a + 1e-8;
+      v1s[s] = (float)v1;
+      dens[s] = (float)(v1 - q / v1 + 1e-8);
     } else {
       v1s[s] = (float)Tp;
       dens[s] = (float)(Tp - 1);   // 0 for a single frame: std = NaN, as torch.std(correction=1)
@@ -151,14 +156,20 @@ __global__ __launch_bounds__(256) void k_stats_pool_rows(const float* __restrict
   // per-channel affine map applied on load (the eval-mode BatchNorm1d that precedes the pooling,
   // xvector.py:245: it cannot be folded past the pooling because an all-zero mask pools to 0, not to `shift`)
   const float sc = aff_scale != nullptr ? aff_scale[c] : 1.f, sh = aff_shift != nullptr ? aff_shift[c] : 0.f;
-  float m[POOL_MAXS];
+  // the weighted sum compensated as in k_stats_pool: `sh` puts an offset into every channel by construction
+  float m[POOL_MAXS], mc[POOL_MAXS];
 #pragma unroll
-  for (int s = 0; s < POOL_MAXS; ++s) m[s] = 0.f;
+  for (int s = 0; s < POOL_MAXS; ++s) m[s] = mc[s] = 0.f;
   for (int t = 0; t < Tp; ++t) {
     const float xv = fmaf(x[t * ts], sc, sh);
 #pragma unroll
     for (int s = 0; s < POOL_MAXS; ++s)
-      if (s < S) m[s] = fmaf(xv, ws[s][t], m[s]);
+      if (s < S) {
+        const float y = fmaf(xv, ws[s][t], -mc[s]);
+        const float u = m[s] + y;
+        mc[s] = (u - m[s]) - y;
+        m[s] = u;
+      }
   }
 #pragma unroll
   for (int s = 0; s < POOL_MAXS; ++s)
@@ -202,15 +213,16 @@ __global__ __launch_bounds__(256) void k_stats_pool_rows_long(const float* __res
   __syncthreads();
   if (threadIdx.x < S) {
     const int s = threadIdx.x;
-    float a = 0.f, q = 0.f;
+    double a = 0.0, q = 0.0;   // in double, as in k_stats_pool
     for (int t = 0; t < Tp; ++t) {
-      a += wl[s * Tp + t];
-      q += wl[s * Tp + t] * wl[s * Tp + t];
+      const double w = (double)wl[s * Tp + t];
+      a += w;
+      q += w * w;
     }
     if (masks != nullptr) {
-      const float v1 = a + 1e-8f;
-      v1s[s] = v1;
-      dens[s] = v1 - q / v1 + 1e-8f;
+      const double v1 = a + 1e-8;
+      v1s[s] = (float)v1;
+      dens[s] = (float)(v1 - q / v1 + 1e-8);
     } else {
       v1s[s] = (float)Tp;
       dens[s] = (float)(Tp - 1);
@@ -223,14 +235,20 @@ __global__ __launch_bounds__(256) void k_stats_pool_rows_long(const float* __res
   const float* x = feat + (((long)(b >> 4) * T0) * 16 + (b & 15)) * ld + c;
   const long ts = 16L * ld;
   const float sc = aff_scale != nullptr ? aff_scale[c] : 1.f, sh = aff_shift != nullptr ? aff_shift[c] : 0.f;
-  float m[POOL_MAXS];
+  // the weighted sum compensated as in k_stats_pool: `sh` puts an offset into every channel by construction
+  float m[POOL_MAXS], mc[POOL_MAXS];
 #pragma unroll
-  for (int s = 0; s < POOL_MAXS; ++s) m[s] = 0.f;
+  for (int s = 0; s < POOL_MAXS; ++s) m[s] = mc[s] = 0.f;
   for (int t = 0; t < Tp; ++t) {
     const float xv = fmaf(x[t * ts], sc, sh);
 #pragma unroll
     for (int s = 0; s < POOL_MAXS; ++s)
-      if (s < S) m[s] = fmaf(xv, wl[s * Tp + t], m[s]);
+      if (s < S) {
+        const float y = fmaf(xv, wl[s * Tp + t], -mc[s]);
+        const float u = m[s] + y;
+        mc[s] = (u - m[s]) - y;
+        m[s] = u;
+      }
   }
 #pragma unroll
   for (int s = 0; s < POOL_MAXS; ++s)

@@ -49,7 +49,8 @@ __global__ __launch_bounds__(256) void k_stats_pool_ragged(const float* __restri
   if (Tv > W) Tv = W;
   const float* x = feat + (((long)b * Fh + f) * W) * C + (c < C ? c : 0);
   const float* mrow = masks != nullptr ? masks + (long)b * ld_masks : nullptr;
-  float a = 0.f, q = 0.f, m = 0.f, mc = 0.f, v = 0.f;   // mc: Kahan compensation of m, as in k_stats_pool
+  double a = 0.0, q = 0.0;                    // the weight sums in double, as in k_stats_pool
+  float m = 0.f, mc = 0.f, v = 0.f;           // mc: Kahan compensation of m, as in k_stats_pool
   // pass 0: weighted sum (+ the weight sums, in column order as k_stats_pool adds them); pass 1: weighted squares
   for (int pass = 0; pass < 2; ++pass) {
     for (int t0 = 0; t0 < Tv; t0 += PR_TILE) {
@@ -59,8 +60,9 @@ __global__ __launch_bounds__(256) void k_stats_pool_ragged(const float* __restri
       __syncthreads();
       if (pass == 0 && threadIdx.x == 0)
         for (int t = 0; t < n; ++t) {
-          a += ws[t];
-          q += ws[t] * ws[t];
+          const double w = (double)ws[t];
+          a += w;
+          q += w * w;
         }
       if (c < C) {
         for (int u0 = 0; u0 < n; u0 += PR_LD) {
@@ -85,9 +87,9 @@ __global__ __launch_bounds__(256) void k_stats_pool_ragged(const float* __restri
     }
     if (pass == 0) {
       if (threadIdx.x == 0) {
-        const float v1 = a + 1e-8f;
-        v1s = v1;
-        dens = v1 - q / v1 + 1e-8f;
+        const double v1 = a + 1e-8;
+        v1s = (float)v1;
+        dens = (float)(v1 - q / v1 + 1e-8);
       }
       __syncthreads();
       m /= v1s;

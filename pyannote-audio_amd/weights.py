@@ -661,6 +661,13 @@ def mfcc_buffers(sd: dict, cfg: dict) -> tuple:
     return window.float(), fb.float(), dct.float()
 
 
+def mfcc_tables(state_dict: dict, hparams: dict) -> tuple:
+    """the float32 tables XVectorMFCCPack uploads for this checkpoint, on the CPU: (window (400), fb (201, n_mels),
+    dct_mat (n_mels, n_mfcc))"""
+    sd = {k: v.detach().float().cpu() for k, v in state_dict.items() if v.dtype.is_floating_point}
+    return mfcc_buffers(sd, mfcc_config(hparams))
+
+
 def fft_twiddles() -> torch.Tensor:
     """exp(-2 pi i m / 200), m < 200, then exp(-2 pi i k / 400), k <= 200, as (re, im) float32 pairs (the 200-point
     complex FFT and the real unpack of csrc/mfcc.hip), rounded once from float64"""

@@ -143,17 +143,30 @@ def test_stats_pool_refusals(gpu_device):
 
 
 def _rows_case(lib, ffi, dev, tag, B, T0, Tp, C, ld, S, Fm, ld_stats, affine, kinds, seed, masks_null=False,
-               expect_nan_std=False):
+               expect_nan_std=False, offset=0.0, spread=1.0, affine_values=None):
+    """`offset` + `spread` randn in the matrix; `affine_values` = (scale, shift): the same for every channel, in place
+    of random ones"""
     rng = torch.Generator().manual_seed(seed)
     ntiles = (B + 15) // 16
     mat = torch.full((ntiles, T0, 16, ld), float("nan"))
-    mat[..., :C] = torch.randn(ntiles, T0, 16, C, generator=rng)
+    mat[..., :C] = offset + spread * torch.randn(ntiles, T0, 16, C, generator=rng)
     x = mat.permute(0, 2, 1, 3).reshape(ntiles * 16, T0, ld)[:B, :Tp, :C]           # (B, Tp, C)
     scale = 0.5 + torch.rand(C, generator=rng) if affine else None
     shift = torch.randn(C, generator=rng) if affine else None
+    if affine_values is not None:
+        assert affine
+        scale, shift = torch.full((C,), affine_values[0]), torch.full((C,), affine_values[1])
     x64, x32 = x.double(), x
     if affine:
         x64, x32 = x64 * scale.double() + shift.double(), x * scale + shift
+    if affine_values is not None:
+        # A shift of 1e3 on a spread of 0.01 leaves float32 a grid of 6e-5 for the shifted values.  That rounding is no
+        # property of the pooling, and it is correlated with the data enough to move the std of 125 frames by 9e-4 of
+        # itself: against the unrounded float64 values, float32 torch is at 0.83 of the contract.  So the truth pools, in
+        # float64, the float32 values the kernel loads -- fma(x, scale, shift), rounded once (formed exactly enough in
+        # float64: the product is exact there).
+        x32 = (x.double() * scale.double() + shift.double()).float()
+        x64 = x32.double()
     if masks_null:
         S, masks, idx = 1, None, None
         truth = torch.cat([x64.mean(1), x64.std(1, correction=1)], -1).unsqueeze(1)
@@ -223,6 +236,69 @@ def test_stats_pool_rows(gpu_device):
     assert lib.pa_last_error().decode().strip() and out.untouched()
 
 
+@pytest.mark.parametrize("where", ["in_the_data", "in_aff_shift"])
+@pytest.mark.parametrize("offset", [1e2, 1e3])
+def test_stats_pool_rows_constant_offset(gpu_device, offset, where):
+    """the offset cases of test_stats_pool_constant_offset for the row form, whose input has an offset by construction
+    (the last BatchNorm's shift, applied on load): offset + 0.01 randn in the matrix, and randn in the matrix with
+    aff_scale = 0.01 and aff_shift = offset, which is how the offset arrives in production.  125, 293 and 640 frames, 64
+    channels in rows of 68, 17 chunks, ones / binary / fractional weights for every chunk (`small` left out for the
+    reason given there)."""
+    import pyannote_audio_amd.ffi as ffi
+    lib = ffi.load()
+    for i, Tp in enumerate((125, 293, 640)):
+        kw = dict(offset=offset, spread=0.01) if where == "in_the_data" else dict(affine_values=(0.01, offset))
+        _rows_case(lib, ffi, gpu_device, f"stats_pool_rows_offset{offset:g}_{where}_Tp{Tp}", 17, Tp + 3, Tp, 64, 68, 3, Tp,
+                   160, where == "in_aff_shift", ("ones", "binary", "fractional"), 9750 + i + SEED_OFFSET, **kw)
+
+
+#: running_mean (of either sign) of the last BatchNorm in test_stats_pool_rows_long_through_the_forward
+LONG_SHIFT = 0.03125
+
+
+def _long_pool_case(shift=LONG_SHIFT):
+    """(oracle, wav (2, 1, 160000), weights (2, 3, 787): fractional | binary | ones, float64 truth, float32 oracle) of a
+    seeded XVectorMFCC whose last BatchNorm has running_var = 1e-4 and running_mean = +-shift -- on the CPU"""
+    import xvector_mfcc_oracle as xo
+    oracle = xo.seeded_xvector_mfcc(seed=3579)
+    bn = oracle.tdnns[14]
+    g = torch.Generator().manual_seed(4300 + SEED_OFFSET)
+    with torch.no_grad():
+        sign = (torch.rand(bn.running_mean.shape, generator=g) < 0.5).float() * 2 - 1
+        bn.running_mean.copy_(shift * sign)
+        bn.running_var.fill_(1e-4)
+    B, N, Tp = 2, 160000, 787
+    wav = (0.1 * torch.randn(B, 1, N, generator=g)).clamp(-1, 1)
+    w = torch.stack([torch.rand(B, Tp, generator=g), (torch.rand(B, Tp, generator=g) < 0.6).float(),
+                     torch.ones(B, Tp)], dim=1)
+    exact = xo.as_float64(oracle)
+    with torch.inference_mode():
+        want64 = torch.stack([exact(wav.double(), weights=w[:, s].double()) for s in range(3)], dim=1)
+        want32 = torch.stack([oracle(wav, weights=w[:, s]) for s in range(3)], dim=1)
+    return oracle, wav, w, want64, want32
+
+
+def test_stats_pool_rows_long_through_the_forward(gpu_device):
+    """k_stats_pool_rows_long has no entry point of its own (pa_stats_pool_rows refuses 641 frames): 787 pool frames of
+    10 s chunks at hop 200 through pa_xvec_mfcc_forward, B = 2, S = 3, against the float64 oracle.  The last BatchNorm
+    has running_var = 1e-4 and running_mean = +-LONG_SHIFT: its shift on load is LONG_SHIFT / sqrt(1e-4 + 1e-5), about
+    95 x LONG_SHIFT, against a spread of 0.1 in the features it pools.  A running_mean of +-30 (a shift of 2860) is not
+    admissible end to end: the float32 oracle is then 0.86 of the contract away from float64, 4.7 at +-10, 1.8 at +-1,
+    0.68 at +-0.5, 0.34 to 0.62 at +-0.125 depending on the CPU -- the embedding layer sums 1500 means of either sign to
+    outputs near zero, which no float32 Linear holds to 1e-5 -- so the shift was shrunk until the float32 oracle is
+    within half the contract with room to spare (0.16): +-0.03125, a shift of 3 against a spread of 0.1.  (The large
+    offsets are held by test_stats_pool_rows_constant_offset, up to 640 frames.)"""
+    import xvector_mfcc_oracle as xo
+    import pyannote_audio_amd as pa
+    oracle, wav, w, want64, want32 = _long_pool_case()
+    model = pa.XVectorMFCC(oracle.state_dict(), xo.xvector_mfcc_hparams(oracle),
+                           pa.model.embedding_specifications()).to(gpu_device)
+    assert model.num_frames(wav.shape[-1]) == w.shape[-1] == 787 > 640
+    got = model(wav.to(gpu_device), w.to(gpu_device))
+    assert got.shape == want64.shape == (2, 3, 512)
+    assert_parity(f"stats_pool_rows_long_Tp787_shift{LONG_SHIFT:g}", got, want64, want32)
+
+
 def _columns(n, halvings):
     w = 1 + (n - 400) // 160
     for _ in range(halvings):
@@ -266,6 +342,38 @@ def test_stats_pool_ragged(gpu_device, with_masks):
                                        out.ptr, ffi.stream()), tag)
     got = out.check(None, tag).view(B, 2 * C * Fh)
     _compare_rows(tag, got, torch.stack(truth), torch.stack(ref32), torch.tensor(single))
+
+
+def test_stats_pool_ragged_constant_offset(gpu_device):
+    """pa_stats_pool_ragged has no limit on the width: features = 1e3 + 0.01 randn over 600 and 1025 valid columns (two
+    and three LDS tiles), fractional and binary weights; admissibility is ruled per utterance"""
+    import pyannote_audio_amd.ffi as ffi
+    lib = ffi.load()
+    rng = torch.Generator().manual_seed(10150 + SEED_OFFSET)
+    cases = [(400 + 160 * 8 * 599 + 77, "fractional"), (400 + 160 * 8 * 1024, "fractional"),
+             (400 + 160 * 8 * 599 + 77, "binary"), (400 + 160 * 8 * 1024, "binary")]
+    widths = [_columns(n, 3) for n, _ in cases]
+    assert widths == [600, 1025, 600, 1025]
+    B, Fh, C, W = len(cases), 3, 64, max(widths)
+    feat = torch.full((B, Fh, W, C), float("nan"))
+    ld_masks = W + 5
+    masks = torch.full((B, ld_masks), float("nan"))
+    truth, ref32 = [], []
+    for b, (wv, (_, kind)) in enumerate(zip(widths, cases)):
+        feat[b, :, :wv] = 1e3 + 0.01 * torch.randn(Fh, wv, C, generator=rng)
+        w = _weights(rng, kind, wv)
+        masks[b, :wv] = w
+        seq = feat[b, :, :wv].permute(2, 0, 1).reshape(C * Fh, wv)
+        truth.append(_pool(seq, w, torch.float64))
+        ref32.append(_pool(seq, w, torch.float32))
+    fd, md = feat.to(gpu_device), masks.to(gpu_device)
+    ld = torch.tensor([n for n, _ in cases], dtype=torch.int32, device=gpu_device)
+    out = Guarded(B * 2 * C * Fh, gpu_device)
+    ffi.check(lib.pa_stats_pool_ragged(dptr(fd), B, Fh, W, C, dptr(ld), 3, dptr(md), ld_masks, out.ptr, ffi.stream()),
+              "stats_pool_ragged_offset")
+    got = out.check(None, "stats_pool_ragged_offset").view(B, 2 * C * Fh)
+    for b, (wv, (_, kind)) in enumerate(zip(widths, cases)):
+        assert_parity(f"stats_pool_ragged_offset1000_W{wv}_{kind}", got[b], truth[b], ref32[b])
 
 
 @pytest.mark.parametrize("C", [4, 32, 256])
