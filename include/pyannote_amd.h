@@ -9,8 +9,17 @@
  * Conventions
  *   - every pointer is a DEVICE pointer to fp32 unless its name ends in `_host` or it is uint8;
  *     (`tensor.data_ptr()` of a contiguous torch-ROCm tensor is what callers pass)
- *   - `stream` is a hipStream_t (e.g. torch.cuda.current_stream().cuda_stream); nothing synchronises
- *   - no hidden allocation: scratch comes from the caller (`*_workspace_bytes`)
+ *   - `stream` is a hipStream_t (e.g. torch.cuda.current_stream().cuda_stream); nothing synchronises: a call enqueues
+ *     kernels on `stream` (zero fills included: csrc/fill.hip, no hipMemsetAsync), on no other stream, and returns --
+ *     so it can be captured into a graph and replayed (tests/test_stream_contract_gpu.py does that with every one).  The exceptions say so again in their own comment, wait
+ *     for `stream` before they return because a result or a table crosses the host, and cannot be captured:
+ *     pa_binarize_regions, pa_regions_sweep_count, pa_regions_sweep_emit, pa_binarize_regions_files_count,
+ *     pa_binarize_regions_files_emit, and pa_kmeans_f64 when round_iterations > 0
+ *   - no hidden allocation: scratch comes from the caller (`*_workspace_bytes`).  One exception, once per process and
+ *     device: the FIRST launch of a persistent 3x3 convolution kernel (the convolution entry points, and the embedding
+ *     forwards built on them) allocates the 256-KB pool of tile counters with hipMalloc, zeroes it on the null stream
+ *     and waits for the null stream.  That first launch must therefore not be made inside a stream capture: warm up
+ *     with one eager call per device; every later launch only takes a block of the pool
  *   - return 0 = OK, 1 = launch/runtime failure, 2 = out of memory, 3 = invalid argument;
  *     pa_last_error() returns a thread-local message.  Python maps 2 -> MemoryError, which is the
  *     convention of Inference.infer (core/inference.py:199-208).
@@ -20,7 +29,7 @@
  * Workspaces (every `workspace` / `ws` argument with its `*_workspace_bytes` query)
  *   - the contents on entry may be ANYTHING -- NaN, huge values, the left-over of another call or of a larger
  *     batch -- and are unspecified on return.  Every block a call reads, it has written before on the same stream (a
- *     kernel or a hipMemsetAsync), or the read cannot reach an output: DESIGN.md section 31 lists the blocks;
+ *     kernel, the fill kernel included), or the read cannot reach an output: DESIGN.md section 31 lists the blocks;
  *   - nothing outside [workspace, workspace + workspace_bytes) is touched, and a call given the bytes its query
  *     returned uses no more than those;
  *   - no output depends on the contents: the same arguments give the same output BYTES whatever the workspace held

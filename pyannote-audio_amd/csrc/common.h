@@ -56,6 +56,10 @@ PA_INTERNAL int lf_launch(const double* cond, int n, double* Z, const LfState& s
 
 void set_error(const char* fmt, ...);
 
+// every byte of [dst, dst + nbytes) <- value, by a kernel on `st` (csrc/fill.hip): the launchers' hipMemsetAsync.  A kernel
+// node of a captured graph replays with the arguments it was captured with; a memset node did not.
+hipError_t fill_async(void* dst, int value, size_t nbytes, hipStream_t st);
+
 // tile queue of the persistent convolution kernels: protocol in tile_queue.h, counter pool in pa_core.cpp
 int* tile_counters();  // a zeroed 16-int block in device memory of the current device (rotating pool)
 }  // namespace pa

@@ -356,7 +356,7 @@ int pa_emb_calibrate_winograd(const pa_emb_weights* w, const float* wav, int64_t
     pa::set_error("pa_emb_calibrate_winograd: BasicBlock networks only (Bottleneck blocks run F(2x2) / direct)");
     return 3;
   }
-  if (hipMemsetAsync(report, 0, sizeof(float) * 8 * PA_MAX_RES_BLOCKS, (hipStream_t)stream) != hipSuccess) return 1;
+  if (pa::fill_async(report, 0, sizeof(float) * 8 * PA_MAX_RES_BLOCKS, (hipStream_t)stream) != hipSuccess) return 1;
   return emb_forward_impl(w, wav, wav_len, chunk_stride, num_chunks, num_samples, nullptr, 1, 0, nullptr, emb,
                           workspace, workspace_bytes, stream, report);
 }

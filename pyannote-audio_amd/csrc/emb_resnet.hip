@@ -481,10 +481,12 @@ int pa_conv3x3(const float* X, int B, int H, int W, int cin, const float* Wg, co
   pa::ProfScope prof("k_conv3x3", stream, 2.0 * 9 * cin * cout * (double)B * Ho * Wo_,
                      4.0 * ((double)B * H * W * cin + (double)B * Ho * Wo_ * cout * (R ? 2 : 1) + 9.0 * cin * cout));
   if (stride == 1) {
-    if (cout == 32) pa::launch_conv<8, 1, 32>(X, B, H, W, cin, Wg, shift, R, Y, cout, relu, st);
-    else if (Ho >= 32) pa::launch_conv<8, 1, 64>(X, B, H, W, cin, Wg, shift, R, Y, cout, relu, st);
-    else if (Ho >= 16) pa::launch_conv<4, 2, 64>(X, B, H, W, cin, Wg, shift, R, Y, cout, relu, st);
-    else pa::launch_conv<2, 2, 64>(X, B, H, W, cin, Wg, shift, R, Y, cout, relu, st);
+    int rc;      // (2: no tile counters -- the message is set; a dropped code would read as "launched")
+    if (cout == 32) rc = pa::launch_conv<8, 1, 32>(X, B, H, W, cin, Wg, shift, R, Y, cout, relu, st);
+    else if (Ho >= 32) rc = pa::launch_conv<8, 1, 64>(X, B, H, W, cin, Wg, shift, R, Y, cout, relu, st);
+    else if (Ho >= 16) rc = pa::launch_conv<4, 2, 64>(X, B, H, W, cin, Wg, shift, R, Y, cout, relu, st);
+    else rc = pa::launch_conv<2, 2, 64>(X, B, H, W, cin, Wg, shift, R, Y, cout, relu, st);
+    if (rc != 0) return rc;
   } else if (stride == 2) {
     PA_REQUIRE(cout % 64 == 0, "pa_conv3x3: stride 2 needs cout %% 64 == 0");
     if (pa::launch_conv_s2(X, B, H, W, cin, Wg, shift, R, Y, cout, relu, st) != 0) return 2;

@@ -664,9 +664,13 @@ int pa_conv3x3_wino_rows(const float* X, int B, int H, int W, int cin, const flo
     const int rc = R != nullptr ? pa::launch_wino32<true>(X, B, H, W, U, shift, R, Y, relu, st)
                                 : pa::launch_wino32<false>(X, B, H, W, U, shift, R, Y, relu, st);
     if (rc != 0) return rc;
-  } else if (a41 <= a22 && a41 <= a14) pa::launch_wino<4, 1>(X, B, H, W, cin, U, shift, R, Y, cout, relu, y_first, st);
-  else if (a22 <= a14) pa::launch_wino<2, 2>(X, B, H, W, cin, U, shift, R, Y, cout, relu, y_first, st);
-  else pa::launch_wino<1, 4>(X, B, H, W, cin, U, shift, R, Y, cout, relu, y_first, st);
+  } else {
+    const int rc = (a41 <= a22 && a41 <= a14)
+                       ? pa::launch_wino<4, 1>(X, B, H, W, cin, U, shift, R, Y, cout, relu, y_first, st)
+                       : a22 <= a14 ? pa::launch_wino<2, 2>(X, B, H, W, cin, U, shift, R, Y, cout, relu, y_first, st)
+                                    : pa::launch_wino<1, 4>(X, B, H, W, cin, U, shift, R, Y, cout, relu, y_first, st);
+    if (rc != 0) return rc;      // (2: no tile counters; dropped before, the call then answered 0 with nothing launched)
+  }
   PA_CHECK_LAUNCH("pa_conv3x3_wino");
   return 0;
 }

@@ -303,7 +303,7 @@ int pa_speaker_count(const uint8_t* seg, int C, int F, int S, const int32_t* sta
   if (T <= 0) return 0;
   hipStream_t st = (hipStream_t)stream;
   pa::ProfScope prof("k_speaker_count", stream, 1.0 * C * F * S, (double)C * F * S + 9.0 * T);
-  if (hipMemsetAsync(scratch, 0, sizeof(int32_t) * 2 * (size_t)T, st) != hipSuccess) {
+  if (pa::fill_async(scratch, 0, sizeof(int32_t) * 2 * (size_t)T, st) != hipSuccess) {
     pa::set_error("pa_speaker_count: memset failed");
     return 1;
   }
@@ -320,7 +320,7 @@ int pa_cluster_activations(const uint8_t* seg, int C, int F, int S, const int32_
   if (T <= 0 || K <= 0) return 0;
   hipStream_t st = (hipStream_t)stream;
   pa::ProfScope prof("k_cluster_scatter", stream, 1.0 * C * F * S, (double)C * F * S + 4.0 * T * K);
-  if (hipMemsetAsync(act, 0, sizeof(int32_t) * (size_t)T * K, st) != hipSuccess) {
+  if (pa::fill_async(act, 0, sizeof(int32_t) * (size_t)T * K, st) != hipSuccess) {
     pa::set_error("pa_cluster_activations: memset failed");
     return 1;
   }

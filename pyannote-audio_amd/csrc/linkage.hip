@@ -471,7 +471,7 @@ int pa_linkage_centroid_f64(double* D, int n, double* Z, void* workspace, size_t
   hipStream_t st = (hipStream_t)stream;
   // the merge loop is O(N^2) memory traffic in total; algorithmic bytes ~ 3 rows of 8*N per merge
   pa::ProfScope prof("k_linkage_centroid", stream, 9.0 * n * (double)n, 24.0 * n * (double)n);
-  if (hipMemsetAsync(s.stats, 0, 128, st) != hipSuccess) return 1;
+  if (pa::fill_async(s.stats, 0, 128, st) != hipSuccess) return 1;
   // ---- the heap-free merge first (linkage_fast.hip); its status word gates the exact heap replay below
   int* gate = nullptr;
   if (s.fast) {

@@ -378,7 +378,7 @@ int pa_pdist_cosine_f64(const double* X, int N, int D, double* out, double* norm
 int pa_nonfinite_flag_f64(const double* v, long count, int* flag, void* stream) {
   PA_REQUIRE(count >= 0 && flag && (count == 0 || v), "pa_nonfinite_flag_f64: null array");
   hipStream_t st = (hipStream_t)stream;
-  if (hipMemsetAsync(flag, 0, sizeof(int), st) != hipSuccess) return 1;
+  if (pa::fill_async(flag, 0, sizeof(int), st) != hipSuccess) return 1;
   if (count == 0) return 0;
   const long blocks = (count + 256L * 8 - 1) / (256L * 8);
   hipLaunchKernelGGL(pa::k_lc_nonfinite, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(256), 0, st, v, count,
@@ -410,7 +410,7 @@ int pa_linkage_chain_f64(const double* D, int n, int method, double* raw, void* 
   // ~3 row scans + 1 update (2 rows in, row + column out) per merge
   pa::ProfScope prof("k_linkage_chain", stream, 4.0 * n * (double)n, 8.0 * 7.0 * n * (double)n);
   // the status word stays non-zero unless the merge kernel runs to its end
-  if (hipMemsetAsync(s.status, 0xFF, 256, st) != hipSuccess) return 1;
+  if (pa::fill_async(s.status, 0xFF, 256, st) != hipSuccess) return 1;
   pa_square_from_condensed(D, n, ld, s.S, stream);
   PA_CHECK_LAUNCH("pa_linkage_chain_f64 (square copy)");
   const size_t lds_bytes = pa::lc_smem_bytes(n, method);

@@ -721,8 +721,8 @@ static long long lf_poll_limit_ticks() {
 // kernel (0 after the kernel = Z is complete).  `stats`: 8 int64 of development counters.
 int lf_launch(const double* cond, int n, double* Z, const LfState& s, long long* stats, hipStream_t st) {
   const long ld = square_ld(n);
-  if (hipMemsetAsync(s.mail, 0, LF_MAIL_GRANULES * 8, st) != hipSuccess) return 1;
-  if (hipMemsetAsync(s.status, 0xff, sizeof(int), st) != hipSuccess) return 1;   // "not run" = take the heap
+  if (pa::fill_async(s.mail, 0, LF_MAIL_GRANULES * 8, st) != hipSuccess) return 1;
+  if (pa::fill_async(s.status, 0xff, sizeof(int), st) != hipSuccess) return 1;   // "not run" = take the heap
   pa_square_from_condensed(cond, n, ld, s.S, st);
   hipLaunchKernelGGL(k_lf_row_nearest, dim3(cdiv(n - 1, 4)), dim3(256), 0, st, cond, n, s.nb0, s.mind0);
   const int G = lf_num_workgroups(n);

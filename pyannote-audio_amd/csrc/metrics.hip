@@ -297,8 +297,8 @@ int pa_der_counts(const uint8_t* ref, const uint8_t* hyp, const uint8_t* keep, l
   PA_REQUIRE(out && (T == 0 || (ref && hyp)), "pa_der_counts: null array");
   hipStream_t s = (hipStream_t)stream;
   const size_t n = (size_t)Sr * Sh + Sr + Sh + 4;
-  if (hipMemsetAsync(out, 0, sizeof(int64_t) * n, s) != hipSuccess) {
-    pa::set_error("pa_der_counts: hipMemsetAsync failed");
+  if (pa::fill_async(out, 0, sizeof(int64_t) * n, s) != hipSuccess) {
+    pa::set_error("pa_der_counts: the fill launch failed");
     return 1;
   }
   if (T == 0) return 0;
@@ -348,8 +348,8 @@ int pa_der_chunks_sum(const int32_t* counts, const int32_t* total, int B, int Q,
   PA_REQUIRE(out && (B == 0 || (counts && total)), "pa_der_chunks_sum: null array");
   hipStream_t s = (hipStream_t)stream;
   const int ncols = 3 * Q;
-  if (hipMemsetAsync(out, 0, sizeof(int64_t) * (ncols + 1), s) != hipSuccess) {
-    pa::set_error("pa_der_chunks_sum: hipMemsetAsync failed");
+  if (pa::fill_async(out, 0, sizeof(int64_t) * (ncols + 1), s) != hipSuccess) {
+    pa::set_error("pa_der_chunks_sum: the fill launch failed");
     return 1;
   }
   if (B == 0) return 0;

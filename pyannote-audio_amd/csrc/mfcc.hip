@@ -209,8 +209,8 @@ PA_INTERNAL int pa_mfcc_frontend(const float* wav, long wav_len, long chunk_stri
   {
     pa::ProfScope prof("k_mfcc_mel", stream, (double)B * T * (5.0 * 400 * 8 + 8.0 * 201 + 2.0 * 201 * 2),
                        4.0 * B * N + 4.0 * B * T * nmel);
-    if (!log_mels && hipMemsetAsync(chunk_max, 0, sizeof(unsigned int) * B, st) != hipSuccess) {
-      pa::set_error("pa_mfcc: hipMemsetAsync failed");
+    if (!log_mels && pa::fill_async(chunk_max, 0, sizeof(unsigned int) * B, st) != hipSuccess) {
+      pa::set_error("pa_mfcc: the fill launch failed");
       return 1;
     }
     hipLaunchKernelGGL(pa::k_mfcc_mel, dim3(pa::cdiv(T, pa::MF_FPB), B), dim3(256), 0, st, wav, wav_len,

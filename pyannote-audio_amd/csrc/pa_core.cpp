@@ -24,6 +24,10 @@ void set_error(const char* fmt, ...) {
 // Pool of self-resetting tile-counter blocks (common.h): 4096 blocks of 16 ints per device, handed out in
 // rotation -- on one stream a block is always free again when its turn comes (launches are ordered), and
 // across streams 4096 launches would have to be in flight at once for two to meet.
+// First use on a device (the one exception to "no hidden allocation" and "nothing synchronises", stated in the
+// Conventions of pyannote_amd.h): the pool is allocated, zeroed on the null stream, and the null stream is waited for.
+// The wait is what orders the zeroing before the caller's kernel: a non-blocking stream does not synchronise with
+// the null stream, and whether hipMemset itself returns only after the fill is nowhere promised for device memory.
 int* tile_counters() {
   constexpr int MAXDEV = 16, BLOCKS = 4096;
   static std::mutex mu;
@@ -35,7 +39,11 @@ int* tile_counters() {
   std::lock_guard<std::mutex> lock(mu);
   if (pool[dev] == nullptr) {
     if (hipMalloc((void**)&pool[dev], sizeof(int) * 16 * BLOCKS) != hipSuccess) return nullptr;
-    (void)hipMemset(pool[dev], 0, sizeof(int) * 16 * BLOCKS);
+    if (hipMemset(pool[dev], 0, sizeof(int) * 16 * BLOCKS) != hipSuccess || hipStreamSynchronize(nullptr) != hipSuccess) {
+      (void)hipFree(pool[dev]);
+      pool[dev] = nullptr;
+      return nullptr;
+    }
   }
   return pool[dev] + 16 * (next[dev]++ % BLOCKS);
 }

@@ -105,8 +105,8 @@ int pa_binarize_regions(const float* scores, int T, int K, const float* onset, c
              "pa_binarize_regions: null parameter array");
   hipStream_t s = (hipStream_t)stream;
   if (T < 2) {   // the reference has no defined result for fewer than two frames
-    if (hipMemsetAsync(counts, 0, sizeof(int32_t) * K, s) != hipSuccess) {
-      pa::set_error("pa_binarize_regions: hipMemsetAsync failed");
+    if (pa::fill_async(counts, 0, sizeof(int32_t) * K, s) != hipSuccess) {
+      pa::set_error("pa_binarize_regions: the fill launch failed");
       return 1;
     }
     return 0;

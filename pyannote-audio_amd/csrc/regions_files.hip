@@ -339,8 +339,8 @@ int pa_binarize_regions_files_emit(const float* scores, int K, int num_files, co
   hipStream_t s = (hipStream_t)stream;
   const int lists = num_files * K;
   if (u.rows == 0 || lists == 0) {
-    if (hipMemsetAsync(list_off, 0, sizeof(int32_t) * ((size_t)lists + 1), s) != hipSuccess) {
-      pa::set_error("%s: hipMemsetAsync failed", who);
+    if (pa::fill_async(list_off, 0, sizeof(int32_t) * ((size_t)lists + 1), s) != hipSuccess) {
+      pa::set_error("%s: the fill launch failed", who);
       return 1;
     }
     return 0;

@@ -370,8 +370,8 @@ int pa_regions_sweep_emit(const float* scores, int T, int K, int L, const int32_
   }
   hipStream_t s = (hipStream_t)stream;
   if (T < 2 || L == 0 || M == 0) {
-    if (hipMemsetAsync(job_off, 0, sizeof(int32_t) * ((size_t)M + 1), s) != hipSuccess) {
-      pa::set_error("%s: hipMemsetAsync failed", who);
+    if (pa::fill_async(job_off, 0, sizeof(int32_t) * ((size_t)M + 1), s) != hipSuccess) {
+      pa::set_error("%s: the fill launch failed", who);
       return 1;
     }
     return 0;

@@ -114,7 +114,7 @@ int pa_sser_forward(const pa_sser_weights* w, const float* wav, int64_t wav_len,
   const int ln_mode = w->extractor_layer_norm;
   PA_RUN(pa_w2v_conv0(wav, wav_len, chunk_stride, B, p.N, p.Tl[0], p.Pl[0], w->conv_channels[0], w->conv_kernel[0],
                       w->conv_stride[0], w->conv_w[0], w->conv_b[0], cb[0], stream));
-  if (hipMemsetAsync(cb[0] + (size_t)B * p.Pl[0] * w->conv_channels[0], 0,
+  if (pa::fill_async(cb[0] + (size_t)B * p.Pl[0] * w->conv_channels[0], 0,
                      sizeof(float) * SLACK * w->conv_channels[0], st) != hipSuccess) return 1;
   if (ln_mode)
     PA_RUN(pa_w2v_layernorm(cb[0], cb[0], (long)B * p.Pl[0], w->conv_channels[0], w->conv_norm_g[0], w->conv_norm_b[0],
@@ -127,7 +127,7 @@ int pa_sser_forward(const pa_sser_weights* w, const float* wav, int64_t wav_len,
     const float* in = cb[(l - 1) & 1];
     float* out = cb[l & 1];
     const long rows = (long)B * p.Pl[l];
-    if (hipMemsetAsync(out + (size_t)rows * cout, 0, sizeof(float) * SLACK * cout, st) != hipSuccess) return 1;
+    if (pa::fill_async(out + (size_t)rows * cout, 0, sizeof(float) * SLACK * cout, st) != hipSuccess) return 1;
     PA_RUN(pa_gemm_tn_ex(in, s * cin, w->conv_w[l], k * cin, w->conv_b[l], nullptr, out, cout, (int)rows, cout, k * cin,
                          ln_mode ? 0 : 3, 0, stream));
     if (ln_mode) PA_RUN(pa_w2v_layernorm(out, out, rows, cout, w->conv_norm_g[l], w->conv_norm_b[l], 1, stream));
@@ -147,8 +147,8 @@ int pa_sser_forward(const pa_sser_weights* w, const float* wav, int64_t wav_len,
   // pre-LN model it follows the last layer in `forward`, which `extract_features` (the call of SSeRiouSS.py:289-296)
   // never reaches.
   if (!w->layer_norm_first) PA_RUN(pa_w2v_layernorm(x, x, M, D, w->enc_ln_g, w->enc_ln_b, 0, stream));
-  if (hipMemsetAsync(ws + p.vt, 0, sizeof(float) * (size_t)B * D * Tp, st) != hipSuccess) return 1;
-  if (hipMemsetAsync(ws + p.o, 0, sizeof(float) * (size_t)M * D, st) != hipSuccess) return 1;
+  if (pa::fill_async(ws + p.vt, 0, sizeof(float) * (size_t)B * D * Tp, st) != hipSuccess) return 1;
+  if (pa::fill_async(ws + p.o, 0, sizeof(float) * (size_t)M * D, st) != hipSuccess) return 1;
 
   // ---- transformer layers (components.EncoderLayer, SelfAttention / WavLMSelfAttention, FeedForward)
   const int use_layer = w->use_layer < 0 ? -1 : (w->use_layer < 1 ? 1 : w->use_layer);

@@ -401,10 +401,10 @@ int pa_det_curve_f64(const double* sorted_keys, const uint8_t* labels, long T, i
   hipStream_t s = (hipStream_t)stream;
   pa::DetHeader* head = l.head;
   // header: counts 0, first_cross (and its padding) all ones; status: all 0
-  if (hipMemsetAsync(head, 0, offsetof(pa::DetHeader, first_cross), s) != hipSuccess ||
-      hipMemsetAsync(&head->first_cross, 0xff, 8, s) != hipSuccess ||
-      hipMemsetAsync(status, 0, sizeof(int64_t) * 8, s) != hipSuccess) {
-    pa::set_error("pa_det_curve_f64: hipMemsetAsync failed");
+  if (pa::fill_async(head, 0, offsetof(pa::DetHeader, first_cross), s) != hipSuccess ||
+      pa::fill_async(&head->first_cross, 0xff, 8, s) != hipSuccess ||
+      pa::fill_async(status, 0, sizeof(int64_t) * 8, s) != hipSuccess) {
+    pa::set_error("pa_det_curve_f64: the fill launch failed");
     return 1;
   }
   pa::ProfScope prof("k_det_curve_f64", stream, 0.0, 2.0 * 9.0 * (double)T + 16.0 * (double)T);

@@ -67,7 +67,7 @@ int xvec_tail(const TdnnTail& w, const TdnnPlan& p, float* ws, int B, const floa
   for (int l = 0; l < PA_XVEC_TDNN; ++l) {
     const int cout = w.channels[l], k = w.kernel[l], d = w.dilation[l];
     float* out = buf[l & 1];
-    if (hipMemsetAsync(out + (size_t)p.M * cout, 0, sizeof(float) * SLACK_ROWS * cout, st) != hipSuccess) return 1;
+    if (pa::fill_async(out + (size_t)p.M * cout, 0, sizeof(float) * SLACK_ROWS * cout, st) != hipSuccess) return 1;
     for (int j = 0; j < k; ++j) {
       // tap j: rows shifted by j * d time steps = 16 j d rows; W_j = tdnn_w[l] + j * cout * cin
       PA_RUN(pa_gemm_tn_ex(in + (size_t)16 * j * d * cin, cin, w.w[l] + (size_t)j * cout * cin, cin,
@@ -88,7 +88,7 @@ int xvec_tail(const TdnnTail& w, const TdnnPlan& p, float* ws, int B, const floa
 
 // the zero rows past the last tile of x0 that the taps of the last frames read
 int zero_x0_slack(const TdnnPlan& p, float* ws, void* stream) {
-  return hipMemsetAsync(ws + p.x0 + (size_t)p.M * 64, 0, sizeof(float) * SLACK_ROWS * 64, (hipStream_t)stream) !=
+  return pa::fill_async(ws + p.x0 + (size_t)p.M * 64, 0, sizeof(float) * SLACK_ROWS * 64, (hipStream_t)stream) !=
                  hipSuccess ? 1 : 0;
 }
 
