@@ -10,6 +10,7 @@ PKG_DIR = Path(__file__).resolve().parent
 CSRC = PKG_DIR / "csrc"
 LIB_PATH = PKG_DIR / "libpyannote_amd.so"
 ARCH = "gfx950"
+PUBLIC_HEADERS = [PKG_DIR.parent / "include" / "pyannote_amd.h", PKG_DIR.parent / "include" / "pyannote_amd_online.h"]
 
 
 def sources() -> list[Path]:
@@ -20,7 +21,7 @@ def _stale() -> bool:
     if not LIB_PATH.exists():
         return True
     t = LIB_PATH.stat().st_mtime
-    deps = sources() + list(CSRC.glob("*.h")) + [PKG_DIR.parent / "include" / "pyannote_amd.h"]
+    deps = sources() + list(CSRC.glob("*.h")) + PUBLIC_HEADERS
     return any(p.stat().st_mtime > t for p in deps)
 
 
@@ -41,7 +42,7 @@ def build_library(force: bool = False, verbose: bool = False) -> Path:
         objs.append(obj)
         if not force and obj.exists() and obj.stat().st_mtime > max(
                 src.stat().st_mtime, *(h.stat().st_mtime for h in CSRC.glob("*.h")),
-                (PKG_DIR.parent / "include" / "pyannote_amd.h").stat().st_mtime):
+                *(h.stat().st_mtime for h in PUBLIC_HEADERS)):
             continue
         extra = []
         for line in src.read_text().splitlines():

@@ -24,6 +24,21 @@ __device__ __forceinline__ double dot2way(const double* __restrict__ u, const do
   return t;
 }
 
+// dot2way of rows kept in other types (float32 embeddings against float64 sums: online.hip): every element is
+// converted to double first, which is exact, then the same products and sums in the same order
+template <typename TU, typename TV>
+__device__ __forceinline__ double dot2way_as_f64(const TU* __restrict__ u, const TV* __restrict__ v, int D) {
+  double s0 = 0.0, s1 = 0.0;
+  const int m = D & ~1;
+  for (int k = 0; k < m; k += 2) {
+    s0 = s0 + (double)u[k] * (double)v[k];
+    s1 = s1 + (double)u[k + 1] * (double)v[k + 1];
+  }
+  double t = s0 + s1;
+  if (D & 1) t = t + (double)u[D - 1] * (double)v[D - 1];
+  return t;
+}
+
 // |x| of one row, as _row_norms takes it
 __device__ __forceinline__ double row_norm_f64(const double* __restrict__ x, int D) {
   return __dsqrt_rn(dot2way(x, x, D));

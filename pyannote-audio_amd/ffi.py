@@ -359,6 +359,12 @@ _OPTIONAL: list[tuple] = [
                              C.c_size_t, c_fp], C.c_int),
     ("pa_gallery_pairs_f64", [c_fp, C.c_int, c_fp, C.c_int, C.c_int, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, C.c_long, c_fp,
                               c_fp], C.c_int),
+    # include/pyannote_amd_online.h (csrc/online.hip); `*_host` tables travel as host addresses
+    ("pao_cluster_step_limits", [C.POINTER(C.c_int), C.POINTER(C.c_int)], C.c_int),
+    ("pao_cluster_step", [c_fp, C.c_void_p, C.c_int, C.c_int, c_fp, c_fp, c_fp, C.c_int, C.c_int, C.c_int, C.c_int,
+                          C.c_int, C.c_double, c_fp, c_fp, c_fp, c_fp], C.c_int),
+    ("pao_emit", [c_fp, C.c_void_p, C.c_int, C.c_int, c_fp, C.c_int, C.c_int, c_fp, c_fp, c_fp, c_fp, C.c_void_p,
+                  C.c_int, C.c_int, C.c_int, c_fp, c_fp, c_fp, c_fp], C.c_int),
 ]
 
 
