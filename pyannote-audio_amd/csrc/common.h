@@ -28,6 +28,14 @@ PA_INTERNAL int pa_mfcc_frontend(const float* wav, long wav_len, long chunk_stri
 PA_INTERNAL int pa_stats_pool_rows_any(const float* feat, int B, int T0, int Tp, int C, int ld, const float* masks,
                                        int S, int Fm, const int* nearest_idx, float* stats, int ld_stats,
                                        const float* aff_scale, const float* aff_shift, void* stream);
+// csrc/emb_fbank.hip, csrc/emb_resnet.hip -> csrc/emb_forward.cpp: the fbank frames of a span of overlapping chunks,
+// computed once, + the mean of every chunk; the stem that reads chunk b as frames[b * fps + t] - mean[b] (mean = NULL:
+// nothing is subtracted; fps = T: pa_resnet_stem)
+PA_INTERNAL int pa_fbank_shared(const float* wav, long wav_len, int fps, int B, int N, const float* window,
+                                const float* tw256, const float* tw512, const float* mel_w, const int* mel_lo,
+                                const int* mel_hi, int nmel, float* frames, float* mean, void* stream);
+PA_INTERNAL int pa_resnet_stem_frames(const float* frames, int fps, const float* mean, int B, int T, int F,
+                                      const float* w9, const float* shift, float* out, void* stream);
 // csrc/cluster.hip -> csrc/linkage_fast.hip, csrc/linkage_chain.hip, csrc/verification.hip
 // S (n x ld, symmetric, zero diagonal) from the condensed matrix `cond` in pa_pdist_f64's order
 PA_INTERNAL void pa_square_from_condensed(const double* cond, int n, long ld, double* S, void* stream);

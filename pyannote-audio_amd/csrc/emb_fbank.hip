@@ -7,6 +7,7 @@
 //                    real FFT as a 256-point complex radix-4 Stockham FFT in LDS + real unpack, power,
 //                    sparse mel projection, log(max(., eps)).
 //   k_fbank_center   subtract the per-chunk mean over frames (wespeaker/__init__.py:138-139).
+//   k_fbank_chunk_mean    that mean alone, for chunks that share the frames of one span (pa_fbank_shared).
 //   k_fbank_center_span   subtract the running mean of K frames (wespeaker/__init__.py:141-157).
 #include "common.h"
 
@@ -200,6 +201,18 @@ __global__ __launch_bounds__(320) void k_fbank_center(float* __restrict__ fb, in
     for (int t = p; t < T; t += 4) x[(long)t * nmel + m] -= mean;
 }
 
+// The means alone, for chunks that SHARE their frames: chunk b is the frames b * fps .. b * fps + T - 1 of one
+// [frames][nmel] array (pa_fbank_shared), mean[b][m] is what k_fbank_center would subtract from that chunk's own copy --
+// the same sums in the same order, so the same bits.  The subtraction is the reader's (k_stem).  grid = B, block = 320
+__global__ __launch_bounds__(320) void k_fbank_chunk_mean(const float* __restrict__ frames, int fps, int T, int nmel,
+                                                          float* __restrict__ mean) {
+  __shared__ double part[4][80];
+  const int b = blockIdx.x;
+  const int m = threadIdx.x % 80, p = threadIdx.x / 80;
+  const float v = fbank_frame_mean(frames + (long)b * fps * nmel, T, nmel, m, p, part);
+  if (m < nmel) mean[(long)b * nmel + m] = v;
+}
+
 // k_fbank_center of a ragged batch: the mean over utterance b's own T_b frames is subtracted from them, and frames
 // T_b .. T - 1 are written as zero (the padding every later 3x3 convolution must see as zero, emb_forward.cpp).  The
 // sums run in the order of k_fbank_center, so each utterance is centred exactly as it is alone.
@@ -250,6 +263,35 @@ __global__ __launch_bounds__(256) void k_fbank_center_span(const float* __restri
 }
 
 }  // namespace pa
+
+// pa_fbank with centring for B chunks of N samples that overlap by whole frame shifts (chunk_stride = fps * 160): frame t
+// of chunk b covers the samples of frame b * fps + t of the span, and everything k_fbank does is per frame, so the span's
+// (B - 1) * fps + T frames are computed ONCE, by the kernel pa_fbank launches with one "chunk" of that many frames ->
+// frames[(B - 1) * fps + T][nmel], uncentred, and mean[B][nmel], the mean of every chunk over its own T frames.
+// (A one-hour file in 10 s chunks every second: 359 998 frames instead of 3 583 818.)
+int pa_fbank_shared(const float* wav, long wav_len, int fps, int B, int N, const float* window, const float* tw256,
+                    const float* tw512, const float* mel_w, const int* mel_lo, const int* mel_hi, int nmel,
+                    float* frames, float* mean, void* stream) {
+  PA_REQUIRE(nmel <= 80, "pa_fbank_shared: at most 80 mel bins are built (got %d)", nmel);
+  if (B <= 0) return 0;
+  PA_REQUIRE(N >= pa::FB_WIN && fps >= 1, "pa_fbank_shared: %d samples every %d frames", N, fps);
+  const int T = 1 + (N - pa::FB_WIN) / pa::FB_SHIFT;
+  const long Ff = (long)(B - 1) * fps + T;
+  PA_REQUIRE(Ff <= 0x7fffffffL, "pa_fbank_shared: %ld frames in one launch", Ff);
+  hipStream_t st = (hipStream_t)stream;
+  {
+    pa::ProfScope prof("k_fbank", stream, (double)Ff * (5.0 * 512 * 9 + 2.0 * 257 * 3 + 2.0 * 257 * 2),
+                       4.0 * ((double)(Ff - 1) * pa::FB_SHIFT + pa::FB_WIN) + 4.0 * Ff * nmel);
+    hipLaunchKernelGGL(pa::k_fbank<false>, dim3(pa::cdiv(Ff, pa::FB_FPB), 1), dim3(256), 0, st, wav, wav_len, 0L,
+                       (int)Ff, 32768.0f, 0.97f, window, (const float2*)tw256, (const float2*)tw512, mel_w, mel_lo,
+                       mel_hi, nmel, 1.1920928955078125e-07f, frames, (const int64_t*)nullptr, (const int*)nullptr);
+    PA_CHECK_LAUNCH("pa_fbank_shared");
+  }
+  pa::ProfScope prof("k_fbank_chunk_mean", stream, (double)B * T * nmel, 4.0 * B * T * nmel + 4.0 * B * nmel);
+  hipLaunchKernelGGL(pa::k_fbank_chunk_mean, dim3(B), dim3(320), 0, st, (const float*)frames, fps, T, nmel, mean);
+  PA_CHECK_LAUNCH("pa_fbank_chunk_mean");
+  return 0;
+}
 
 extern "C" {
 

@@ -17,6 +17,13 @@ inline bool s2_fold_wanted() {
   return fold;
 }
 
+// PA_EMB_SHARED_FBANK=0 (environment) computes the fbank frames of overlapping chunks per chunk, as before they were
+// shared, for an A/B; read on every call, so that one process can run both
+inline bool shared_fbank_wanted() {
+  const char* e = getenv("PA_EMB_SHARED_FBANK");
+  return e == nullptr || atoi(e) != 0;
+}
+
 // Winograd F(4x4,3x3) (pa_conv3x3_wino4: units of 4 x 64 output pixels) or F(2x2,3x3) (pa_conv3x3_wino: 8 x 32,
 // 4 x 64 or 2 x 128 per workgroup) for an H x W map, both weight images being available.  Per USEFUL pixel F(4x4) is
 // 1.02x / 1.12x / 1.29x as fast on the 64 / 128 / 256-channel layers (B = 512 launches on MI355X,
@@ -154,7 +161,21 @@ static int emb_forward_impl(const pa_emb_weights* w, const float* wav, int64_t w
     pa::set_error("pa_emb_forward_ragged: fbank_centering_span checkpoints run one launch sequence per length");
     return 3;
   }
-  if (ragged)
+  // Chunks that overlap by whole frame shifts (the sliding window of a pipeline: 10 s every second) share their frames:
+  // the span's (B - 1) * fps + T frames are computed once, uncentred, the per-chunk means go behind them, and the stem
+  // subtracts while it stages (pa_fbank_shared) -- bit for bit what the per-chunk copy holds after k_fbank_center.  Both
+  // arrays live in the fbank region of the plan, so they must fit it: chunks that overlap by one frame or not at all
+  // (the compact copy of a pipeline's inactive-chunk skip among them) take the per-chunk sequence by themselves.
+  const int64_t fps = chunk_stride > 0 && chunk_stride % 160 == 0 ? chunk_stride / 160 : 0;
+  const size_t span_frames = (size_t)(B - 1) * (size_t)fps + p.T;
+  const bool shared = !ragged && span == 0 && fps > 0 && B >= 2 && shared_fbank_wanted() &&
+                      fps < p.T /* (so span_frames has not wrapped) */ &&
+                      (span_frames + B) * p.F <= (size_t)B * p.T * p.F;
+  if (shared)
+    PA_RUN(pa_fbank_shared(wav, wav_len, (int)fps, B, p.N, w->fb_window, w->fb_tw256, w->fb_tw512, w->fb_mel_w,
+                           w->fb_mel_lo, w->fb_mel_hi, w->num_mel, ws + p.fbank, ws + p.fbank + span_frames * p.F,
+                           stream));
+  else if (ragged)
     PA_RUN(pa_fbank_ragged(wav, wav_len, offsets, lengths, B, p.N, w->fb_window, w->fb_tw256, w->fb_tw512, w->fb_mel_w,
                            w->fb_mel_lo, w->fb_mel_hi, w->num_mel, ws + p.fbank, stream));
   else
@@ -172,7 +193,11 @@ static int emb_forward_impl(const pa_emb_weights* w, const float* wav, int64_t w
     PA_RUN(pa_fbank_center_span(ws + p.fbank, B, p.T, p.F, span, f1, stream));
     feats = f1;
   }
-  PA_RUN(pa_resnet_stem(feats, B, p.T, p.F, w->stem_w, w->stem_shift, cur, stream));
+  if (shared)
+    PA_RUN(pa_resnet_stem_frames(feats, (int)fps, feats + span_frames * p.F, B, p.T, p.F, w->stem_w, w->stem_shift, cur,
+                                 stream));
+  else
+    PA_RUN(pa_resnet_stem(feats, B, p.T, p.F, w->stem_w, w->stem_shift, cur, stream));
   if (!w->bottleneck) PA_RUN(zero_tail(cur, 0, w->planes[0]));
 
   // a stride-1 3x3 convolution (+ shift, residual R, ReLU) of a BasicBlock: F(4x4) where it pays, else F(2x2), else

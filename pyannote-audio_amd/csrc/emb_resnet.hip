@@ -26,7 +26,13 @@ namespace pa {
 constexpr int STEM_TS = 64;             // time steps per workgroup
 constexpr int STEM_LD = STEM_TS + 3;    // LDS row stride (odd: the transposing stores spread over the banks)
 
-__global__ __launch_bounds__(256) void k_stem(const float* __restrict__ fb, int T, int F,
+// Chunk b is the frames b * fps .. b * fps + T - 1 of `fb` (fps = T: one block of T frames per chunk; fps < T: the
+// chunks overlap and share the frames of one span, pa_fbank_shared).  kCentred: fb is uncentred and mean[b][ff] is
+// subtracted while staging -- the one float subtraction k_fbank_center does in place.  The zero padding of the
+// convolution is that of the CENTRED chunk: outside [0, T) the staged value is 0, never a neighbour's frame.
+template <bool kCentred>
+__global__ __launch_bounds__(256) void k_stem(const float* __restrict__ fb, int fps, const float* __restrict__ mean,
+                                              int T, int F,
                                               const float* __restrict__ w9,   // [9][32] tap-major
                                               const float* __restrict__ shift,  // [32]
                                               float* __restrict__ out) {
@@ -38,16 +44,20 @@ __global__ __launch_bounds__(256) void k_stem(const float* __restrict__ fb, int 
   const int n = (STEM_TS + 2) * F;
   for (int i0 = 0; i0 < n; i0 += 8 * 256) {
     float v[8];
+    [[maybe_unused]] float mu[8];
 #pragma unroll
-    for (int k = 0; k < 8; ++k) {       // 8 loads in flight per thread
+    for (int k = 0; k < 8; ++k) {       // 8 loads (kCentred: + 8 of the mean) in flight per thread
       const int i = i0 + tid + 256 * k;
       const int tt = i / F, ff = i - tt * F, t = t0 + tt - 1;
-      v[k] = (i < n && t >= 0 && t < T) ? fb[((long)b * T + t) * F + ff] : 0.f;
+      const bool in = i < n && t >= 0 && t < T;
+      v[k] = in ? fb[((long)b * fps + t) * F + ff] : 0.f;
+      if constexpr (kCentred) mu[k] = in ? mean[(long)b * F + ff] : 0.f;   // (padding: 0 - 0)
     }
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
       const int i = i0 + tid + 256 * k;
       const int tt = i / F, ff = i - tt * F;
+      if constexpr (kCentred) v[k] -= mu[k];
       if (i < n) xs[(ff + 1) * STEM_LD + tt] = v[k];
     }
   }
@@ -456,18 +466,32 @@ static int launch_conv(const float* X, int B, int H, int W, int CIN, const float
 
 }  // namespace pa
 
+// the stem over chunks given as frames b * fps .. b * fps + T - 1 of `frames`, less mean[b] where one is given (k_stem)
+int pa_resnet_stem_frames(const float* frames, int fps, const float* mean, int B, int T, int F, const float* w9,
+                          const float* shift, float* out, void* stream) {
+  if (B <= 0) return 0;
+  // read: the distinct frames (+ the means); written: 32 channels per pixel
+  const double read = mean != nullptr ? ((double)(B - 1) * fps + T + B) * F : (double)B * T * F;
+  pa::ProfScope prof("k_stem", stream, 2.0 * B * T * F * 9 * 32, 4.0 * (read + 32.0 * B * T * F));
+  PA_REQUIRE(F >= 1 && (size_t)(F + 2) * pa::STEM_LD * 4 <= 64 * 1024, "pa_resnet_stem: %d mel bins do not fit LDS", F);
+  const dim3 grid(pa::cdiv(T, pa::STEM_TS), B);
+  const size_t lds = (size_t)(F + 2) * pa::STEM_LD * 4;
+  if (mean != nullptr)
+    hipLaunchKernelGGL(pa::k_stem<true>, grid, dim3(256), lds, (hipStream_t)stream, frames, fps, mean, T, F, w9, shift,
+                       out);
+  else
+    hipLaunchKernelGGL(pa::k_stem<false>, grid, dim3(256), lds, (hipStream_t)stream, frames, fps, mean, T, F, w9, shift,
+                       out);
+  PA_CHECK_LAUNCH("pa_resnet_stem");
+  return 0;
+}
+
 extern "C" {
 
 // conv1 + bn1 + relu of ResNet.forward (resnet.py:413-415), reading the (B,T,F) fbank directly
 int pa_resnet_stem(const float* fbank, int B, int T, int F, const float* w9, const float* shift,
                    float* out, void* stream) {
-  if (B <= 0) return 0;
-  pa::ProfScope prof("k_stem", stream, 2.0 * B * T * F * 9 * 32, 4.0 * B * T * F * 33);
-  PA_REQUIRE(F >= 1 && (size_t)(F + 2) * pa::STEM_LD * 4 <= 64 * 1024, "pa_resnet_stem: %d mel bins do not fit LDS", F);
-  hipLaunchKernelGGL(pa::k_stem, dim3(pa::cdiv(T, pa::STEM_TS), B), dim3(256), (size_t)(F + 2) * pa::STEM_LD * 4,
-                     (hipStream_t)stream, fbank, T, F, w9, shift, out);
-  PA_CHECK_LAUNCH("pa_resnet_stem");
-  return 0;
+  return pa_resnet_stem_frames(fbank, T, nullptr, B, T, F, w9, shift, out, stream);
 }
 
 // BasicBlock convolutions (resnet.py:84-145): Y = [relu]( conv3x3_s(X) + shift [+ R] )
