@@ -78,6 +78,48 @@ int pao_emit(const int32_t* slots, const int32_t* slots_host, int M, int N, cons
              const int64_t* frames_host, int R, int K, int E, int32_t* acc_sum, int32_t* acc_cnt, uint8_t* out,
              void* stream);
 
+/* Replay of recorded files through the rule above: J jobs in ONE launch, one workgroup per job, no host in the loop.
+ * A job is a file and a threshold triple; files of a list and candidates of a tuning grid are jobs of one launch.
+ * The front ends of the files are concatenated along the chunk axis:
+ *   emb (num_chunks, S, D) float32; active, clean (num_chunks, S) int32; seg (num_chunks, F, S) uint8
+ *   files (num_files, 4) int64: per file its chunk offset, its chunk count C, its schedule offset (in rows) and its
+ *     frame total
+ *   sched (num_sched, 3) int64: rows of (start_frame, emit_from, emit_to); a file owns C + 1 consecutive rows, row c
+ *     for chunk c and the FLUSH row last
+ *   jobs (J, 3) int32: per job its file, min_active_frames, min_update_frames; delta_new (J) float64
+ *   offsets (J, 2) int64: per job its first row of `map` and its first row of `out`
+ *   files_host, sched_host, jobs_host, offsets_host: the same tables on the host.  They are REQUIRED (a NULL one is
+ *     refused with 3): the loop bounds come from them.  This is the one departure from "NULL = the caller vouches".
+ * State, in / out, one row per JOB (not per file): centroid_sum (J, K, D) float64, centroid_n (J, K) int32,
+ * acc_sum (J, R, K) int32, acc_cnt (J, R) int32.  The contents on entry are the state -- a fresh replay passes
+ * zeros, a continued one what an earlier call left -- and on return they hold the final state.
+ * For c = 0 .. C - 1 a job applies items 1-8 of pao_cluster_step to chunk c with its own thresholds, then the
+ * overlap-add, emission and ring clearing of pao_emit with schedule row c; then pao_emit with the flush row (nothing
+ * is added).  The arithmetic is that of the two calls -- the same device functions -- so the result is what they give
+ * called once per chunk, bit for bit.
+ *   -> map (map_rows, S) int32: rows [offset, offset + C) of a job hold the maps of its chunks
+ *   -> out (out_rows, K) uint8: rows [offset, offset + frame total) of a job; row g - (emit_from of the file's first
+ *      schedule row) holds frame g.
+ * Every row a job owns is written whatever it held; rows no job owns are not touched.
+ * 3 (nothing written) if S > 4, K > 32, D < 1, F < 1 or R < F; a NULL host table; a file whose chunks or schedule
+ * rows run past num_chunks / num_sched or whose frame total exceeds INT_MAX / 32; a job whose file is outside
+ * [0, num_files); a job whose rows run past map_rows / out_rows or overlap another job's; a schedule that is
+ * inconsistent: every row has 0 <= emit_from <= emit_to and, unless start_frame < 0, start_frame + F - emit_from <= R;
+ * each emit_from equals the previous row's emit_to; the last row has start_frame < 0; the last emit_to minus the first
+ * emit_from equals the file's frame total.
+ * The device checks the same conditions again: a job whose rows cannot be located (file out of range, rows past the
+ * totals or under another job's) writes nothing; a job with an inconsistent schedule leaves its state alone and
+ * writes zero rows and -1 maps.
+ * One kernel on `stream`, no other stream, no synchronisation, no allocation on the device, no workspace: it can be
+ * captured into a graph and replayed. */
+int pao_replay(const float* emb, const int32_t* active, const int32_t* clean, const uint8_t* seg, int64_t num_chunks,
+               int F, int S, int D, const int64_t* files, const int64_t* files_host, int num_files,
+               const int64_t* sched, const int64_t* sched_host, int64_t num_sched, const int32_t* jobs,
+               const int32_t* jobs_host, const double* delta_new, const int64_t* offsets,
+               const int64_t* offsets_host, int J, int64_t map_rows, int64_t out_rows, int K, int R,
+               double* centroid_sum, int32_t* centroid_n, int32_t* acc_sum, int32_t* acc_cnt, int32_t* map,
+               uint8_t* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

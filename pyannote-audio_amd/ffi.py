@@ -365,6 +365,9 @@ _OPTIONAL: list[tuple] = [
                           C.c_int, C.c_double, c_fp, c_fp, c_fp, c_fp], C.c_int),
     ("pao_emit", [c_fp, C.c_void_p, C.c_int, C.c_int, c_fp, C.c_int, C.c_int, c_fp, c_fp, c_fp, c_fp, C.c_void_p,
                   C.c_int, C.c_int, C.c_int, c_fp, c_fp, c_fp, c_fp], C.c_int),
+    ("pao_replay", [c_fp, c_fp, c_fp, c_fp, C.c_int64, C.c_int, C.c_int, C.c_int, c_fp, C.c_void_p, C.c_int, c_fp,
+                    C.c_void_p, C.c_int64, c_fp, C.c_void_p, c_fp, c_fp, C.c_void_p, C.c_int, C.c_int64, C.c_int64,
+                    C.c_int, C.c_int, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp], C.c_int),
 ]
 
 

@@ -8,7 +8,12 @@ download.  Centroids and the overlap-add ring stay on the device between pushes.
 The clustering is the incremental rule of Coria et al., "Overlap-aware low-latency online speaker diarization based on
 end-to-end local segmentation" (ASRU 2021), stated in full in the header; it is not part of the reference library and
 is held to a numpy model of its own definition (tests/online_model.py).  There is no host implementation behind these
-calls."""
+calls.
+
+A recorded file does not have to arrive slowly: `StreamBank.front_end` runs the two networks over all its chunks at
+once, and `StreamBank.replay` (`replay_jobs`, `pao_replay`, csrc/online_replay.hip) walks the chunks through the same
+rule on the device, one workgroup per (file, threshold triple) -- the route of `apply(file, replay=True)` and of
+`tuning.OnlineTuner`."""
 from __future__ import annotations
 
 import math
@@ -103,6 +108,57 @@ def emit(slots: Sequence[int], seg: torch.Tensor, map: torch.Tensor, start_frame
     return out
 
 
+@ffi.on_device(lambda emb, *a, **k: emb.device)
+def replay_jobs(emb: torch.Tensor, active: torch.Tensor, clean: torch.Tensor, seg: torch.Tensor, files, sched, jobs,
+                delta_new, offsets, centroid_sum: torch.Tensor, centroid_n: torch.Tensor, acc_sum: torch.Tensor,
+                acc_cnt: torch.Tensor, map_rows: Optional[int] = None, out_rows: Optional[int] = None
+                ) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Recorded files through the online rule, every job in ONE launch (`pao_replay`; the header has the tables).
+    emb (chunks, S, D) float32, active / clean (chunks, S) int32, seg (chunks, F, S) uint8: the concatenated front
+    ends; files (files, 4) and sched (rows, 3) int64, jobs (J, 3) int32, delta_new (J) float64, offsets (J, 2) int64:
+    host tables; the state -- centroid_sum (J, K, D) float64, centroid_n (J, K), acc_sum (J, R, K), acc_cnt (J, R)
+    int32, one row per job -- is updated in place -> (map (map_rows, S) int32, out (out_rows, K) uint8) on the device.
+    `map_rows` / `out_rows` default to what the offsets reach; rows no job owns come back zero."""
+    files = np.ascontiguousarray(files, dtype=np.int64).reshape(-1, 4)
+    sched = np.ascontiguousarray(sched, dtype=np.int64).reshape(-1, 3)
+    jobs = np.ascontiguousarray(jobs, dtype=np.int32).reshape(-1, 3)
+    offsets = np.ascontiguousarray(offsets, dtype=np.int64).reshape(-1, 2)
+    delta_new = np.ascontiguousarray(delta_new, dtype=np.float64).reshape(-1)
+    C, S, D = emb.shape
+    F = seg.shape[1]
+    J, K, _ = centroid_sum.shape
+    R = acc_sum.shape[1]
+    if not (emb.dtype == torch.float32 and active.dtype == torch.int32 and clean.dtype == torch.int32
+            and seg.dtype == torch.uint8 and centroid_sum.dtype == torch.float64 and centroid_n.dtype == torch.int32
+            and acc_sum.dtype == torch.int32 and acc_cnt.dtype == torch.int32):
+        raise ValueError("replay_jobs: emb float32, seg uint8, centroid_sum float64, everything else int32")
+    if tuple(active.shape) != (C, S) or tuple(clean.shape) != (C, S) or seg.shape[0] != C or seg.shape[2] != S \
+            or len(jobs) != J or len(delta_new) != J or len(offsets) != J or centroid_sum.shape[2] != D \
+            or tuple(centroid_n.shape) != (J, K) or tuple(acc_sum.shape) != (J, R, K) or tuple(acc_cnt.shape) != (J, R):
+        raise ValueError("replay_jobs: one row of active, clean and seg per chunk; one row of the job table, of "
+                         "delta_new, of the offsets and of every state tensor per job")
+    dev = emb.device
+    if map_rows is None or out_rows is None:
+        inside = (jobs[:, 0] >= 0) & (jobs[:, 0] < len(files))
+        rows = files[jobs[inside, 0]] if inside.any() else np.zeros((0, 4), np.int64)
+        reach = offsets[inside] + rows[:, [1, 3]] if inside.any() else np.zeros((0, 2), np.int64)
+        map_rows = int(reach[:, 0].max(initial=0)) if map_rows is None else map_rows
+        out_rows = int(reach[:, 1].max(initial=0)) if out_rows is None else out_rows
+    mp = torch.zeros((max(int(map_rows), 0), S), dtype=torch.int32, device=dev)
+    out = torch.zeros((max(int(out_rows), 0), K), dtype=torch.uint8, device=dev)
+    wide = torch.from_numpy(np.concatenate([files.reshape(-1), sched.reshape(-1), offsets.reshape(-1),
+                                            delta_new.view(np.int64)])).to(dev)
+    d_files, d_sched, d_offsets, d_delta = torch.split(wide, [files.size, sched.size, offsets.size, delta_new.size])
+    d_jobs = torch.from_numpy(jobs.reshape(-1)).to(dev)
+    ffi.check(_lib().pao_replay(
+        ffi.ptr(emb), ffi.ptr(active), ffi.ptr(clean), ffi.ptr(seg), C, F, S, D, ffi.ptr(d_files), files.ctypes.data,
+        len(files), ffi.ptr(d_sched), sched.ctypes.data, len(sched), ffi.ptr(d_jobs), jobs.ctypes.data,
+        ffi.ptr(d_delta), ffi.ptr(d_offsets), offsets.ctypes.data, J, int(map_rows), int(out_rows), K, R,
+        ffi.ptr(centroid_sum), ffi.ptr(centroid_n), ffi.ptr(acc_sum), ffi.ptr(acc_cnt), ffi.ptr(mp), ffi.ptr(out),
+        ffi.stream()), "pao_replay")
+    return mp, out
+
+
 # ------------------------------------------------------------------------------------------------- frame arithmetic
 def frame_of_time(t: float, frames: SlidingWindow) -> int:
     """the frame a chunk starting at time t starts on: `frames.frame_geometry`'s float64 formula for one value (chunks
@@ -137,6 +193,59 @@ def stream_num_frames(num_samples: int, window: int, step_samples: int, sample_r
     return max(int(num_frames), 0)
 
 
+def file_schedule(num_samples: int, *, window: int, step_samples: int, sample_rate: int, duration: float, step: float,
+                  latency: float, frames: SlidingWindow, F: int) -> Tuple[int, np.ndarray, int]:
+    """What a recording of `num_samples` samples goes through when it is streamed, without a bank: -> (C chunks,
+    schedule (C + 1, 3) int64 of (start_frame, emit_from, emit_to), total frames).  The host arithmetic of `push`,
+    `_run` and `close`: chunks come from whole steps, the tail is zero-padded to one step, a file shorter than one chunk
+    gets one zero-padded chunk, the `limit = total` clamp applies on a closing chunk only, and the flush row
+    (start_frame = -1) comes last.  Chunk c is `padded[c * step_samples : c * step_samples + window]`."""
+    num_samples = max(int(num_samples), 0)
+    total = stream_num_frames(num_samples, window, step_samples, sample_rate, duration, step, frames)
+    steps_per_window = window // step_samples
+    blocks = num_samples // step_samples + (1 if num_samples % step_samples else 0)
+    if num_samples == 0:
+        C, closing = 0, -1
+    elif blocks < steps_per_window:
+        C, closing = 1, 0
+    else:
+        C = blocks - steps_per_window + 1
+        closing = C - 1 if num_samples % step_samples else -1
+    rows = np.empty((C + 1, 3), dtype=np.int64)
+    emitted = 0
+    for c in range(C):
+        start = start_frame(c, step, frames)
+        bound = min(emit_bound(c, step, duration, latency, frames), start + F)
+        if c == closing:
+            bound = min(bound, total)
+        rows[c] = (start, emitted, max(bound, emitted))
+        emitted = int(rows[c, 2])
+    rows[C] = (-1, emitted, max(total, emitted))
+    return C, rows, total
+
+
+class FrontEnd:
+    """everything of a recording the online rule reads, on the device: seg (C, F, S) uint8, active / clean (C, S)
+    int32, emb (C, S, D) float32; its `schedule` (C + 1, 3) int64 on the host and its `total` frames"""
+    __slots__ = ("seg", "active", "clean", "emb", "schedule", "total")
+
+    def __init__(self, seg, active, clean, emb, schedule, total):
+        self.seg, self.active, self.clean, self.emb, self.schedule, self.total = seg, active, clean, emb, schedule, total
+
+    @property
+    def num_chunks(self) -> int:
+        return int(self.seg.shape[0])
+
+
+class Replayed:
+    """one replayed job: `decisions` (total, K) uint8, `maps` (C, S) int32, `centroids` (K, D) float64 -- what
+    `decisions(slot)`, the maps of every step and `centroids(slot)` give after streaming"""
+    __slots__ = ("decisions", "maps", "centroids")
+
+    def __init__(self, decisions, maps, centroids):
+        self.decisions, self.maps, self.centroids = decisions, maps, centroids
+
+
 def _architecture(model) -> str:
     return str(getattr(type(model), "ARCHITECTURE", ("", type(model).__name__))[1])
 
@@ -163,11 +272,20 @@ class StreamBank:
 
     `delta_new` (a local speaker farther than this cosine distance from its centroid founds a new one), `min_active`
     and `min_update` (seconds a local speaker must be on / on alone to count / to move a centroid) are UNTUNED
-    defaults: no trained checkpoint is available offline to tune them with (a `ClusteringTuner` leg is future
-    work).
+    defaults: no trained checkpoint is available offline to tune them with.  `tuning.OnlineTuner` tunes the three
+    on a corpus.
 
     open() -> slot; push(blocks, slots) -> {slot: (first_frame, decisions)}; close(slot, tail) -> (first_frame,
-    decisions); annotation(slot); centroids(slot)."""
+    decisions); annotation(slot); centroids(slot).
+
+    A RECORDED file need not be streamed: `front_end(waveform)` computes what the rule reads for every chunk at
+    once and `replay(front_ends, params)` walks the chunks on the device, every (file, threshold triple) a job of one
+    launch (`pao_replay`) -- the decisions, maps and centroids streaming the file through a fresh slot gives."""
+
+    #: bound on the bytes of the gathered windows of one front-end group
+    front_end_bytes: int = 64 << 20
+    #: bound on the bytes of the outputs and the state of one replay launch
+    replay_bytes: int = 1 << 30
 
     def __init__(self, segmentation, embedding, num_slots: int, *, step: float = 0.5, latency: Optional[float] = None,
                  max_speakers: int = 20, delta_new: float = 1.0, min_active: float = 0.25, min_update: float = 1.0,
@@ -395,8 +513,11 @@ class StreamBank:
     def annotation(self, slot: int, uri: Optional[str] = None) -> Annotation:
         """the turns emitted so far: runs of every column of `decisions(slot)`, labelled SPEAKER_%02d by global
         speaker, with the frame middles `to_annotation` gives them"""
+        return self.annotation_of(self.decisions(slot), uri)
+
+    def annotation_of(self, rows: np.ndarray, uri: Optional[str] = None) -> Annotation:
+        """the turns of decisions (frames, K) uint8 from frame 0, as `annotation` gives them"""
         from .diarization import to_annotation
-        rows = self.decisions(slot)
         used = [k for k in range(self.K) if rows[:, k].any()]
         feature = SlidingWindowFeature(rows[:, used].astype(np.float32),
                                        SlidingWindow(start=0.0, duration=self.frames.duration, step=self.frames.step))
@@ -412,13 +533,158 @@ class StreamBank:
         n = self.centroid_n[slot].to(torch.float64)[:, None]
         return (self.centroid_sum[slot] / n).cpu().numpy()
 
+    # ---------------------------------------------------------------------------------------------- recorded files
+    def schedule(self, num_samples: int) -> Tuple[int, np.ndarray, int]:
+        """`file_schedule` with the geometry of this bank"""
+        return file_schedule(num_samples, window=self.window, step_samples=self.step_samples,
+                             sample_rate=self.sample_rate, duration=self.duration, step=self.step,
+                             latency=self.latency, frames=self.frames, F=self.F)
+
+    def threshold_frames(self, min_active: float, min_update: float) -> Tuple[int, int]:
+        """(min_active_frames, min_update_frames) of thresholds in seconds, rounded as the constructor rounds them"""
+        return max(1, int(np.rint(min_active / self.frames.step))), int(np.rint(min_update / self.frames.step))
+
+    def front_ends(self, waveforms: Sequence[torch.Tensor]) -> List[FrontEnd]:
+        """`front_end` of several recordings; consecutive recordings share launch groups"""
+        ffi.require_gpu()
+        from . import frames as frame_ops
+        dev = self.device
+        plans, windows = [], []             # per file (C, schedule, total); per file a (C, window) strided view
+        for waveform in waveforms:
+            wav = torch.as_tensor(waveform).reshape(-1).to(dev, torch.float32)
+            C, rows, total = self.schedule(wav.numel())
+            padded = torch.zeros(self.window + max(C - 1, 0) * self.step_samples, dtype=torch.float32, device=dev)
+            padded[:wav.numel()] = wav
+            plans.append((C, rows, total))
+            windows.append(padded.unfold(0, self.window, self.step_samples)[:C])
+        per_group = max(1, self.front_end_bytes // (4 * self.window))
+        parts = {i: [] for i in range(len(plans))}
+        group, size = [], 0
+
+        def run(group):
+            with torch.cuda.device(dev):
+                flat = torch.cat([windows[i][a:b] for i, a, b in group]).contiguous().view(-1)
+                M = flat.numel() // self.window
+                _, seg = self.seg_model.engine.forward_strided(flat, self.window, M, self.window, want_logp=False,
+                                                               want_multilabel=True)
+                active, clean = frame_ops.chunk_stats(seg)
+                masks = frame_ops.embedding_masks(seg, clean, self.exclude_overlap, self._min_num_frames())
+                emb = self.emb_model.engine.forward_strided(flat, self.window, M, self.window, masks)
+            at = 0
+            for i, a, b in group:
+                parts[i].append(tuple(t[at:at + b - a] for t in (seg, active, clean, emb)))
+                at += b - a
+
+        for i, (C, _, _) in enumerate(plans):            # greedy: a group takes chunks of consecutive files
+            a = 0
+            while a < C:
+                b = min(C, a + per_group - size)
+                group.append((i, a, b))
+                size += b - a
+                a = b
+                if size == per_group:
+                    run(group)
+                    group, size = [], 0
+        if group:
+            run(group)
+        out = []
+        for i, (C, rows, total) in enumerate(plans):
+            if C:
+                seg, active, clean, emb = (torch.cat(t) if len(t) > 1 else t[0] for t in zip(*parts[i]))
+            else:
+                seg = torch.zeros((0, self.F, self.S), dtype=torch.uint8, device=dev)
+                active = clean = torch.zeros((0, self.S), dtype=torch.int32, device=dev)
+                emb = torch.zeros((0, self.S, self.D), dtype=torch.float32, device=dev)
+            out.append(FrontEnd(seg.contiguous(), active.contiguous(), clean.contiguous(), emb.contiguous(), rows, total))
+        (self.stage_hook or (lambda name: None))("front_end")
+        return out
+
+    def front_end(self, waveform: torch.Tensor) -> FrontEnd:
+        """Everything the rule reads for a whole recording (1-D float32): the engine calls `push` makes for one chunk,
+        made on GATHERED contiguous windows (M, window) -- chunk c is `padded[c step_samples : c step_samples +
+        window]` -- in groups of at most `front_end_bytes`.  A window's result does not depend on the M it is batched
+        with, so these are the bits streaming gives."""
+        return self.front_ends([waveform])[0]
+
+    def replay(self, front_ends, params: Optional[Sequence[Tuple[float, float, float]]] = None):
+        """Recorded files through the rule without streaming them.  `front_ends`: a `FrontEnd` or a list of them;
+        `params`: a list of (delta_new, min_active, min_update) in seconds, default the bank's own triple.  Every
+        (file, triple) is a job; jobs are split over launches by `replay_bytes`.  -> per file (a list input) per triple
+        (a `params` input) one `Replayed`: a single FrontEnd without `params` gives one `Replayed`, a list of files
+        with `params` gives results[file][triple]."""
+        single = isinstance(front_ends, FrontEnd)
+        fes = [front_ends] if single else list(front_ends)
+        if params is None:
+            triples = [(self.delta_new, self.min_active_frames, self.min_update_frames)]
+        else:
+            triples = [(float(d), *self.threshold_frames(a, u)) for d, a, u in params]
+        pairs = [(f, t) for f in range(len(fes)) for t in range(len(triples))]
+        flat = self.replay_pairs(fes, triples, pairs)
+        nested = [[flat[f * len(triples) + t] for t in range(len(triples))] for f in range(len(fes))]
+        if params is None:
+            nested = [row[0] for row in nested]
+        return nested[0] if single else nested
+
+    def replay_pairs(self, fes: Sequence[FrontEnd], triples: Sequence[Tuple[float, int, int]],
+                     pairs: Sequence[Tuple[int, int]]) -> List[Replayed]:
+        """the jobs `pairs` = (index into `fes`, index into `triples` of (delta_new, min_active_frames,
+        min_update_frames)) -> one `Replayed` each, in order"""
+        ffi.require_gpu()
+        dev = self.device
+        if not pairs:
+            return []
+        counts = np.array([fe.num_chunks for fe in fes], dtype=np.int64)
+        chunk_off = np.concatenate([[0], np.cumsum(counts)])
+        sched_off = np.concatenate([[0], np.cumsum(counts + 1)])
+        files = np.stack([chunk_off[:-1], counts, sched_off[:-1], [fe.total for fe in fes]], axis=1).astype(np.int64)
+        sched = np.concatenate([fe.schedule for fe in fes]).astype(np.int64)
+        emb, active, clean, seg = (torch.cat([getattr(fe, name) for fe in fes]) if len(fes) > 1 else getattr(fes[0], name)
+                                   for name in ("emb", "active", "clean", "seg"))
+        state = 8 * self.K * self.D + 4 * self.K + 4 * self.R * (self.K + 1)
+        results: List[Replayed] = []
+        stage = self.stage_hook or (lambda name: None)
+        at = 0
+        while at < len(pairs):
+            batch, used = [], 0
+            while at + len(batch) < len(pairs) and len(batch) < 65535:
+                f = pairs[at + len(batch)][0]
+                need = state + int(fes[f].total) * self.K + 4 * int(counts[f]) * self.S
+                if batch and used + need > self.replay_bytes:
+                    break
+                batch.append(pairs[at + len(batch)])
+                used += need
+            at += len(batch)
+            J = len(batch)
+            jobs = np.array([[f, triples[t][1], triples[t][2]] for f, t in batch], dtype=np.int32)
+            delta = np.array([triples[t][0] for _, t in batch], dtype=np.float64)
+            rows = np.array([[counts[f], fes[f].total] for f, _ in batch], dtype=np.int64)
+            offsets = np.concatenate([np.zeros((1, 2), np.int64), np.cumsum(rows, axis=0)])
+            with torch.cuda.device(dev):
+                csum = torch.zeros((J, self.K, self.D), dtype=torch.float64, device=dev)
+                cn = torch.zeros((J, self.K), dtype=torch.int32, device=dev)
+                acc_sum = torch.zeros((J, self.R, self.K), dtype=torch.int32, device=dev)
+                acc_cnt = torch.zeros((J, self.R), dtype=torch.int32, device=dev)
+                stage("replay_state")
+                mp, out = replay_jobs(emb, active, clean, seg, files, sched, jobs, delta, offsets[:-1], csum, cn,
+                                      acc_sum, acc_cnt, map_rows=int(offsets[-1, 0]), out_rows=int(offsets[-1, 1]))
+                stage("replay")
+                centroids = (csum / cn.to(torch.float64)[:, :, None]).cpu().numpy()
+                mp, out = mp.cpu().numpy(), out.cpu().numpy()
+                stage("download")
+            for j in range(J):
+                results.append(Replayed(np.ascontiguousarray(out[offsets[j, 1]:offsets[j + 1, 1]]),
+                                        np.ascontiguousarray(mp[offsets[j, 0]:offsets[j + 1, 0]]), centroids[j]))
+        return results
+
 
 class OnlineSpeakerDiarization(Pipeline):
     """Diarizes files as if they were streamed: `step` seconds at a time through a `StreamBank`, every decision made
     with the audio up to `latency` seconds later and never revised.  `apply(file)` streams one file through a bank of
     one; `apply_batch(files, num_slots=None)` streams many concurrently (files of different lengths end at different
     steps, and waiting files take the freed slots).  Both return `Annotation`s; a file's Annotation does not depend on
-    the files it shared the bank with.  The thresholds are the UNTUNED defaults of `StreamBank`."""
+    the files it shared the bank with.  With `replay=True` both skip the streaming loop: the files are recorded, so
+    every chunk's front end is computed at once and the rule is replayed on the device (`StreamBank.replay`), with the
+    same turns.  The thresholds are the UNTUNED defaults of `StreamBank`; `tuning.OnlineTuner` tunes them on a corpus."""
 
     def __init__(self, segmentation=None, embedding=None, step: float = 0.5, latency: Optional[float] = None,
                  max_speakers: int = 20, delta_new: float = 1.0, min_active: float = 0.25, min_update: float = 1.0,
@@ -459,17 +725,25 @@ class OnlineSpeakerDiarization(Pipeline):
                                "pipeline.to(torch.device('cuda')) -- there is no CPU fallback")
         return StreamBank(self.segmentation_model, self.embedding_model, num_slots, device=device, **self.bank_options)
 
-    def apply(self, file, **kwargs) -> Annotation:
-        return self.apply_batch([file], num_slots=1)[0]
+    def apply(self, file, replay: bool = False, **kwargs) -> Annotation:
+        return self.apply_batch([file], num_slots=1, replay=replay)[0]
 
     def _apply_batch(self, files: list, **kwargs):
         return zip(files, self.apply_batch(files, **kwargs))
 
-    def apply_batch(self, files: Iterable, num_slots: Optional[int] = None) -> List[Annotation]:
+    def apply_batch(self, files: Iterable, num_slots: Optional[int] = None, replay: bool = False) -> List[Annotation]:
+        """`replay=True`: the files are recorded, so nothing has to arrive slowly -- the front ends of all files at
+        once (`StreamBank.front_ends`), then ONE replay with the files as jobs (`StreamBank.replay`): the same turns
+        without one push per step.  The default is the streaming loop."""
         from .audio import Audio
         files = [Audio.validate_file(f) for f in files]
         if not files:
             return []
+        if replay:
+            bank = self.bank(1)
+            audio = Audio(sample_rate=bank.sample_rate, mono="downmix")
+            replayed = bank.replay(bank.front_ends([audio(f)[0].reshape(-1) for f in files]))
+            return [bank.annotation_of(r.decisions, uri=f["uri"]) for f, r in zip(files, replayed)]
         bank = self.bank(min(len(files), 64) if num_slots is None else int(num_slots))
         audio = Audio(sample_rate=bank.sample_rate, mono="downmix")
         step = bank.step_samples

@@ -1,5 +1,6 @@
 """Tuning on a corpus.  `DetectionTuner` (below `ClusteringTuner`, after `candidate_counts`, the counts of all its
-candidates on a file) tunes the thresholds of the detection pipelines; `ClusteringTuner` the clustering of a
+candidates on a file) tunes the thresholds of the detection pipelines; `OnlineTuner` (last) the three thresholds of
+the online rule, every (file, candidate) a job of one `pao_replay` launch; `ClusteringTuner` the clustering of a
 `SpeakerDiarization` pipeline: the search the reference's `optimize` command runs
 (src/pyannote/audio/__main__.py:116-283 -- the pipeline applied to every development file again for every candidate
 `clustering.threshold` / `min_cluster_size`), organised so that a candidate only pays for what depends on it.
@@ -786,6 +787,110 @@ class DetectionTuner:
             if len(seen) > 1 and any(a & b for i, a in enumerate(seen) for b in seen[i + 1:]):
                 flagged.add(e)
         return flagged
+
+
+# ----------------------------------------------------------------------------------- online thresholds
+class OnlineTuner:
+    """`OnlineTuner(pipeline).prepare(files).sweep(delta_news, min_actives, min_updates)` for an
+    `online.OnlineSpeakerDiarization`: the three thresholds of the online rule act only inside the clustering step, so
+    a file's front end (`StreamBank.front_end`: segmentation, statistics, masks, embeddings of every chunk) is computed
+    ONCE by `prepare`, and a candidate is a replay of the same (chunks x speakers) embeddings through the rule with
+    other numbers.  `evaluate(candidates)` -- dicts with "delta_new", "min_active", "min_update" -- makes every
+    (file, distinct triple) a job of `StreamBank.replay_pairs` (`pao_replay`: one workgroup per job, launches split
+    by `StreamBank.replay_bytes`).  Distinct means distinct (min_active_frames, min_update_frames, delta_new): two
+    candidates whose seconds round to the same frame counts share a job.  Equal decision arrays of a file share the
+    Annotation and its metric components.
+
+    -> {"entries": [{"params", "loss"}], "best": the first minimum, "evaluations": candidates x files,
+    "shared_evaluations": the (candidate, file) pairs that reused another candidate's job or hypothesis}.  The loss of
+    a candidate is what a fresh pipeline with its three values, streaming `apply` per file and
+    `metric(file["annotation"], hypothesis, uem=file.get("annotated"))` give.  `apply_best(result)` writes the three
+    values into `pipeline.bank_options`; they are constructor arguments, not `Parameter`s, so there is no
+    `write_config` leg."""
+
+    NAMES = ("delta_new", "min_active", "min_update")
+
+    def __init__(self, pipeline, metric: Optional[Callable] = None):
+        self.pipeline = pipeline
+        self.metric = metric if metric is not None else pipeline.get_metric
+        self.bank = None
+        self.files: list = []
+        self.front_ends: list = []
+        self.shared_evaluations = 0
+        self.evaluations = 0
+        #: per candidate, per file: the speaker diarization that was scored
+        self.hypotheses: list = []
+        #: of the last `evaluate`: jobs replayed (distinct triples x files)
+        self.jobs = 0
+
+    def prepare(self, files: Iterable) -> "OnlineTuner":
+        """runs every file's front end once, consecutive files sharing launch groups"""
+        from .audio import Audio
+        self.files = [Audio.validate_file(f) for f in files]
+        self.bank = self.pipeline.bank(1)
+        audio = Audio(sample_rate=self.bank.sample_rate, mono="downmix")
+        self.front_ends = self.bank.front_ends([audio(f)[0].reshape(-1) for f in self.files])
+        return self
+
+    def candidates(self, delta_news, min_actives, min_updates) -> list:
+        return [{"delta_new": float(d), "min_active": float(a), "min_update": float(u)}
+                for d in delta_news for a in min_actives for u in min_updates]
+
+    def sweep(self, delta_news, min_actives, min_updates) -> dict:
+        """the grid, `delta_news` outermost"""
+        return self.evaluate(self.candidates(delta_news, min_actives, min_updates))
+
+    def evaluate(self, candidates: list) -> dict:
+        if self.bank is None:
+            raise RuntimeError("OnlineTuner: call prepare(files) first")
+        bank = self.bank
+        triples, job_of = {}, []
+        for params in candidates:
+            active, update = bank.threshold_frames(params["min_active"], params["min_update"])
+            job_of.append(triples.setdefault((float(params["delta_new"]), active, update), len(triples)))
+        triples = list(triples)
+        pairs = [(f, t) for f in range(len(self.files)) for t in range(len(triples))]
+        replayed = bank.replay_pairs(self.front_ends, triples, pairs)
+        self.jobs = len(pairs)
+        self.shared_evaluations = self.evaluations = 0
+        self.hypotheses = []
+        # per file: hypothesis and metric components of every distinct decision array, and which a job gave
+        known = [dict() for _ in self.files]
+        of_job = [dict() for _ in self.files]
+        entries = []
+        for c, params in enumerate(candidates):
+            metric = self.metric()
+            row = []
+            for f, file in enumerate(self.files):
+                self.evaluations += 1
+                t = job_of[c]
+                key = of_job[f].get(t)
+                if key is None:
+                    rows = replayed[f * len(triples) + t].decisions
+                    key = of_job[f][t] = rows.tobytes()
+                    fresh = key not in known[f]
+                    if fresh:
+                        known[f][key] = [bank.annotation_of(rows, uri=file.get("uri")), None]
+                else:
+                    fresh = False
+                hypothesis, components = known[f][key]
+                if fresh or components is None:
+                    known[f][key][1] = ClusteringTuner._score(metric, file, hypothesis)
+                else:
+                    self.shared_evaluations += 1
+                    ClusteringTuner._score(metric, file, hypothesis, components)
+                row.append(hypothesis)
+            self.hypotheses.append(row)
+            entries.append({"params": params, "loss": abs(metric)})
+        direction = self.pipeline.get_direction() if hasattr(self.pipeline, "get_direction") else "minimize"
+        return {"entries": entries, "best": best_entry(entries, direction),
+                "shared_evaluations": self.shared_evaluations, "evaluations": self.evaluations}
+
+    def apply_best(self, result: dict) -> dict:
+        """writes the best candidate's three values into `pipeline.bank_options` -> those values"""
+        best = {name: float(result["best"]["params"][name]) for name in self.NAMES}
+        self.pipeline.bank_options.update(best)
+        return best
 
 
 def write_config(config_yml, result: dict, name: str) -> Path:
