@@ -43,6 +43,7 @@ PA_INTERNAL void pa_square_from_condensed(const double* cond, int n, long ld, do
 PA_INTERNAL void pa_row_norms_f64(const double* X, int N, int D, double* nrm, void* stream);
 
 #include "workspace.h"
+#include "launch_state.h"
 namespace pa {
 
 // The square symmetric copy the linkage kernels merge on (csrc/cluster.hip): its leading dimension, a multiple of 8
@@ -69,7 +70,23 @@ void set_error(const char* fmt, ...);
 hipError_t fill_async(void* dst, int value, size_t nbytes, hipStream_t st);
 
 // tile queue of the persistent convolution kernels: protocol in tile_queue.h, counter pool in pa_core.cpp
-int* tile_counters();  // a zeroed 16-int block in device memory of the current device (rotating pool)
+int* tile_counters(const char* entry);   // a zeroed 16-int block of the current device; null: refused, message set
+int xcd_ranges_wanted(bool by_default);   // tile order of those kernels (emb_winograd4.hip)
+// Per-device launch state (launch_state.h) with this library's answers.  "Allow `kernel` (a constant: the grant is
+// remembered per kernel and device, whichever sites ask) `bytes` of dynamic LDS on the current device"; refused: rc 3
+int lds_refused(const char* entry, long answer, size_t bytes);   // the message names the entry, bytes and limit
+#define PA_ALLOW_LDS(entry, kernel, bytes)                                                                        \
+  do {                                                                                                            \
+    const pa::LdsAnswer a__ = pa::allow_lds(pa::kernel_cell<(kernel)>(), (const void*)(kernel), (long)(bytes));   \
+    if (a__ != pa::LDS_OK) return pa::lds_refused(entry, a__, bytes);                                             \
+  } while (0)
+// the one line of a persistent launcher (one function per kernel, so its static is per kernel): -> resident, counters
+#define PA_PERSISTENT(entry, kernel, threads, lds, per_cu)                                                            \
+  static pa::DeviceCell cell__;                                                                                       \
+  const long resident = pa::resident_workgroups(cell__, (const void*)(kernel), threads, (long)(lds), per_cu);         \
+  if (resident <= 0) return pa::lds_refused(entry, -resident, lds);                                                   \
+  int* const counters = pa::tile_counters(entry);                                                                     \
+  if (counters == nullptr) return 2
 }  // namespace pa
 #include "tile_queue.h"
 namespace pa {

@@ -447,8 +447,6 @@ __global__ __launch_bounds__(256, 2) void k_conv3x3_s2(const float* __restrict__
   if (tid == 0) tq_done(tq, gridDim.x);
 }
 
-int xcd_ranges_wanted(bool by_default);   // emb_winograd4.hip
-
 template <int TH, int TWT, bool HAS_R, int SC = 0>
 static int launch_conv_s2_r(const float* X, int B, int H, int W, int CIN, const float* Wg, const float* shift,
                             const float* R, float* Y, int COUT, int relu, hipStream_t st, const float* Wsc = nullptr,
@@ -457,27 +455,10 @@ static int launch_conv_s2_r(const float* X, int B, int H, int W, int CIN, const 
   const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
   const int tiles_w = cdiv(Wo, G::TW), tiles_h = cdiv(Ho, TH);
   const size_t lds = (size_t)G::LDS_BYTES + 16;   // + the mailbox
-  constexpr int MAXDEV = 16;
-  static int resident_of[MAXDEV] = {0};
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  if (dev < 0 || dev >= MAXDEV) dev = 0;
-  if (!resident_of[dev]) {
-    (void)hipFuncSetAttribute((const void*)k_conv3x3_s2<TH, TWT, HAS_R, SC>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)lds);
-    int cus = 256;
-    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    resident_of[dev] = cus;   // one workgroup per CU: LDS-bound
-  }
-  const int resident = resident_of[dev] & ~7;
+  PA_PERSISTENT("pa_conv3x3", (k_conv3x3_s2<TH, TWT, HAS_R, SC>), 256, lds, 1);   // one workgroup per CU: LDS-bound
   const int tiles_hw = tiles_w * tiles_h, n_tiles = COUT / CS2_BN;
   const long total = (long)tiles_hw * n_tiles * B;
-  const int grid = (int)(total < resident ? total : resident);
-  int* counters = tile_counters();
-  if (counters == nullptr) {
-    set_error("pa_conv3x3: cannot allocate the tile counters");
-    return 2;
-  }
+  const int grid = persistent_grid(total, resident);
   hipLaunchKernelGGL((k_conv3x3_s2<TH, TWT, HAS_R, SC>), dim3(grid), dim3(256), lds, st, X, H, W, CIN, Wg, shift, R, Y,
                      Ho, Wo, COUT, relu, tiles_w, tiles_hw, n_tiles, (int)total, xcd_ranges_wanted(true), counters, Wsc,
                      shift_sc, Ysc);

@@ -308,12 +308,7 @@ int pa_fbank_center_span(const float* fb, int B, int T, int nmel, int kernel, fl
              "pa_fbank_center_span: a running mean over %d frames of a %d-frame chunk needs more than the LDS holds "
              "(at most %d frames)", kernel, T, pa::FC_KMAX);
   const size_t lds = (size_t)(pa::FC_TT + kernel - 1) * pa::FC_MG * sizeof(float);
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute((const void*)pa::k_fbank_center_span, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)((pa::FC_TT + pa::FC_KMAX - 1) * pa::FC_MG * sizeof(float)));
-    attr_set = true;
-  }
+  PA_ALLOW_LDS("pa_fbank_center_span", pa::k_fbank_center_span, (pa::FC_TT + pa::FC_KMAX - 1) * pa::FC_MG * sizeof(float));
   hipLaunchKernelGGL(pa::k_fbank_center_span, dim3(pa::cdiv(T, pa::FC_TT), pa::cdiv(nmel, pa::FC_MG), B), dim3(256), lds,
                      (hipStream_t)stream, fb, T, nmel, kernel, out);
   PA_CHECK_LAUNCH("pa_fbank_center_span");

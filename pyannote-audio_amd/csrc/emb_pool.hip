@@ -332,12 +332,7 @@ PA_INTERNAL int pa_stats_pool_rows_any(const float* feat, int B, int T0, int Tp,
   PA_REQUIRE(S >= 1 && S <= pa::POOL_MAXS && lds <= (size_t)pa::POOLR_LONG_LDS && ld_stats >= 2 * C,
              "pa_stats_pool_rows: S <= %d, S x T' <= %d and ld_stats >= 2 C required (got %d, %d)", pa::POOL_MAXS,
              pa::POOLR_LONG_LDS / 4, S, Tp);
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute((const void*)pa::k_stats_pool_rows_long, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              pa::POOLR_LONG_LDS);
-    attr_set = true;
-  }
+  PA_ALLOW_LDS("pa_stats_pool_rows", pa::k_stats_pool_rows_long, (size_t)pa::POOLR_LONG_LDS);
   pa::ProfScope prof("k_stats_pool_rows_long", stream, 6.0 * B * S * C * Tp, 4.0 * B * C * Tp + 8.0 * B * S * C);
   hipLaunchKernelGGL(pa::k_stats_pool_rows_long, dim3(pa::cdiv(C, 256), B), dim3(256), lds, (hipStream_t)stream,
                      feat, T0, Tp, C, ld, masks, S, Fm, nearest_idx, stats, ld_stats, aff_scale, aff_shift);

@@ -406,7 +406,6 @@ __global__ __launch_bounds__(256, 2) void k_conv3x3(const float* __restrict__ X,
   if (tid == 0) tq_done(tq, gridDim.x);
 }
 
-int xcd_ranges_wanted(bool by_default);   // emb_winograd4.hip
 // stride 2 (emb_conv_s2.hip: k_conv3x3_s2)
 int launch_conv_s2(const float* X, int B, int H, int W, int CIN, const float* Wg, const float* shift, const float* R,
                    float* Y, int COUT, int relu, hipStream_t st);
@@ -423,33 +422,11 @@ static int launch_conv_r(const float* X, int B, int H, int W, int CIN, const flo
   const int Ho = H, Wo = W;
   const int tiles_w = cdiv(Wo, G::TW), tiles_h = cdiv(Ho, TH);
   const size_t lds = (size_t)(G::PATCH + 9 * BN * CLD) * sizeof(float);
-  // workgroups the chip holds at once (2 per CU: LDS- and VGPR-bound); per DEVICE, like the attribute
-  constexpr int MAXDEV = 16;
-  static int resident_of[MAXDEV] = {0}, per_cu_of[MAXDEV] = {0};
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  if (dev < 0 || dev >= MAXDEV) dev = 0;
-  if (!resident_of[dev]) {
-    (void)hipFuncSetAttribute((const void*)k_conv3x3<TH, TWT, BN, HAS_R>,
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    int cus = 256, per_cu = 2;
-    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_conv3x3<TH, TWT, BN, HAS_R>, 256, lds) !=
-            hipSuccess || per_cu < 1)
-      per_cu = 2;
-    resident_of[dev] = cus * per_cu;
-    per_cu_of[dev] = per_cu;
-  }
+  PA_PERSISTENT("pa_conv3x3", (k_conv3x3<TH, TWT, BN, HAS_R>), 256, lds, PER_CU_ASK);   // (2 per CU: LDS and VGPRs)
   // every resident workgroup is launched; tiles are claimed at run time (common.h: TileQueue)
-  const int resident = resident_of[dev] & ~7;
   const int tiles_hw = tiles_w * tiles_h, n_tiles = COUT / BN;
   const long total = (long)tiles_hw * n_tiles * B;
-  const int grid = (int)(total < resident ? total : resident);
-  int* counters = tile_counters();
-  if (counters == nullptr) {
-    set_error("pa_conv3x3: cannot allocate the tile counters");
-    return 2;
-  }
+  const int grid = persistent_grid(total, resident);
   hipLaunchKernelGGL((k_conv3x3<TH, TWT, BN, HAS_R>), dim3(grid), dim3(256), lds, st, X, H, W, CIN, Wg,
                      shift, R, Y, Ho, Wo, COUT, relu, tiles_w, tiles_hw, n_tiles, (int)total, xcd_ranges_wanted(true),
                      counters);

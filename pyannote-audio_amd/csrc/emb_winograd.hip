@@ -416,8 +416,6 @@ __global__ __launch_bounds__(256, 2) void k_conv3x3_wino(
   if (tid == 0) tq_done(tq, gridDim.x);
 }
 
-int xcd_ranges_wanted(bool by_default);   // emb_winograd4.hip
-
 template <int TR, int TCG, bool HAS_R>
 static int launch_wino_r(const float* X, int B, int H, int W, int CIN, const float* U, const float* shift,
                          const float* R, float* Y, int COUT, int relu, int y_first, hipStream_t st) {
@@ -427,34 +425,13 @@ static int launch_wino_r(const float* X, int B, int H, int W, int CIN, const flo
   const size_t lds = (size_t)G::LDS_FLOATS * sizeof(float) + 16 +
                      ((HAS_R && TCG == 1) ? 4 * 4096 : (HAS_R && TCG == 4 ? 4 * 256 : 0));
   auto kernel = k_conv3x3_wino<TR, TCG, HAS_R>;
-  // per-device launch state (the attribute and the CU count belong to a device, not to the process)
-  constexpr int MAXDEV = 16;
-  static int resident_of[MAXDEV] = {0}, per_cu_of[MAXDEV] = {0};
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  if (dev < 0 || dev >= MAXDEV) dev = 0;
-  if (!resident_of[dev]) {
-    (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    int cus = 256, per_cu = 2;
-    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, 256, lds) !=
-            hipSuccess || per_cu < 1)
-      per_cu = 2;
-    resident_of[dev] = cus * per_cu;
-    per_cu_of[dev] = per_cu;
-  }
+  PA_PERSISTENT("pa_conv3x3_wino", kernel, 256, lds, PER_CU_ASK);   // (per-device launch state: launch_state.h)
   const int tiles_hw = tiles_w * tiles_h, n_tiles = COUT / W_BN;
   const long num_pb = (long)tiles_hw * B;                    // (pixel tile, image) pairs
   const long total = ((num_pb + 7) / 8) * 8 * n_tiles;       // padded to whole XCD stripes
   // every resident workgroup is launched whatever else runs on the chip: tiles are claimed at run time, so
   // a workgroup that is placed late (a foreign kernel holds its CU) costs nothing but its own absence
-  const int resident = resident_of[dev] & ~7;
-  const int grid = (int)(total < resident ? total : resident);
-  int* counters = tile_counters();
-  if (counters == nullptr) {
-    set_error("pa_conv3x3_wino: cannot allocate the tile counters");
-    return 2;
-  }
+  const int grid = persistent_grid(total, resident);
   hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), lds, st, X, H, W, CIN, U, shift, R, Y, COUT, relu, tiles_w,
                      tiles_hw, n_tiles, (int)total, (int)num_pb, y_first, xcd_ranges_wanted(true), counters);
   return 0;
@@ -588,28 +565,11 @@ static int launch_wino32(const float* X, int B, int H, int W, const float* U, co
   const int tiles_w = cdiv(W, 32), tiles_h = cdiv(H, 8);
   const size_t lds = (size_t)(2 * G::USLAB + 4 * G::PATCH) * sizeof(float) + 32;
   auto kernel = k_conv3x3_wino32<HAS_R>;
-  constexpr int MAXDEV = 16;
-  static int cus_of[MAXDEV] = {0};
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  if (dev < 0 || dev >= MAXDEV) dev = 0;
-  if (!cus_of[dev]) {
-    (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    int cus = 256;
-    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    cus_of[dev] = cus;
-  }
+  PA_PERSISTENT("pa_conv3x3_wino", kernel, 512, lds, 1);   // one workgroup (two halves) per CU
   const int tiles_hw = tiles_w * tiles_h;
   const long num_pb = (long)tiles_hw * B;
   const long total = ((num_pb + 7) / 8) * 8;
-  const int resident = cus_of[dev] & ~7;            // one workgroup (two halves) per CU
-  const long want = (total + 1) / 2;
-  const int grid = (int)(want < resident ? ((want + 7) & ~7L) : resident);
-  int* counters = tile_counters();
-  if (counters == nullptr) {
-    set_error("pa_conv3x3_wino: cannot allocate the tile counters");
-    return 2;
-  }
+  const int grid = persistent_grid(total, resident, true);
   hipLaunchKernelGGL(kernel, dim3(grid), dim3(512), lds, st, X, H, W, U, shift, R, Y, relu, tiles_w, tiles_hw,
                      (int)total, (int)num_pb, xcd_ranges_wanted(true), counters);
   return 0;

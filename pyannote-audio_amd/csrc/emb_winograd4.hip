@@ -804,29 +804,13 @@ static int launch_wino4(const float* X, int B, int H, int W, int CIN, const floa
   const int cgroups = LIN ? cdiv(W, 4) : cdiv(W, Wino4Geom::TW), trows = cdiv(rows, 4);
   const size_t lds = (size_t)G::LDS_BYTES + 16;
   auto kernel = k_conv3x3_wino4<HAS_R, MODE>;
-  constexpr int MAXDEV = 16;
-  static int cus_of[MAXDEV] = {0};
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  if (dev < 0 || dev >= MAXDEV) dev = 0;
-  if (!cus_of[dev]) {
-    (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    int cus = 256;
-    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    cus_of[dev] = cus;
-  }
+  PA_PERSISTENT("pa_conv3x3_wino4", kernel, 256, lds, 1);   // one workgroup per CU
   const int n_tiles = COUT / W_BN;
   const long total_tiles = (long)cgroups * trows * B;                       // (LIN)
   const long num_units = LIN ? (total_tiles + 15) / 16 : (long)cgroups * trows * B;
   const long num_groups = (num_units + 3) / 4;
   const long total = ((num_groups + 7) / 8) * 8 * n_tiles;   // padded to whole XCD stripes
-  const int resident = cus_of[dev] & ~7;                      // one workgroup per CU
-  const int grid = (int)(total < resident ? total : resident);
-  int* counters = tile_counters();
-  if (counters == nullptr) {
-    set_error("pa_conv3x3_wino4: cannot allocate the tile counters");
-    return 2;
-  }
+  const int grid = persistent_grid(total, resident);
   // (tile-linear: the kernel's `num_units` argument carries the number of TILES)
   hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), lds, st, X, H, W, CIN, U, shift, R, Y, COUT, relu, cgroups, trows,
                      (int)(LIN ? total_tiles : num_units), (int)num_groups, n_tiles, (int)total, B,

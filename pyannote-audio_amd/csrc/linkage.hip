@@ -475,26 +475,21 @@ int pa_linkage_centroid_f64(double* D, int n, double* Z, void* workspace, size_t
   // ---- the heap-free merge first (linkage_fast.hip); its status word gates the exact heap replay below
   int* gate = nullptr;
   if (s.fast) {
-    if (pa::lf_launch(D, n, Z, s.lf, s.stats + 8, st) != 0) return 1;
+    if (const int rc = pa::lf_launch(D, n, Z, s.lf, s.stats + 8, st)) return rc;
     gate = s.lf.status;
     PA_CHECK_LAUNCH("pa_linkage_centroid_f64 (fast path)");
   }
-  // `big_lds`: the instantiation keeps its heap in dynamic LDS beyond the default limit (the attribute is set on
-  // every call: it belongs to the current device, not to the process)
-  auto launch = [&](auto kernel, size_t lds, bool big_lds) {
-    if (big_lds)
-      (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)pa::LK_LDS_MAX);
+  auto launch = [&](auto kernel, size_t lds) {
     hipLaunchKernelGGL(kernel, dim3(1), dim3(pa::LK_T), lds, st, D, n, Z, s.size, s.cid, s.hv, s.kbi, s.ibk, s.nb,
                        s.stats, gate);
   };
   // 16-bit keys: heap values, kbi, ibk and neighbours (14 bytes per row) + the candidate bitmap in LDS
   const size_t cand_bytes = pa::lk_cand_bytes(n);
   const size_t lds16 = (((size_t)(n - 1) * 14 + 15) & ~(size_t)15) + cand_bytes;
-  if (n <= 65535 && lds16 <= pa::LK_LDS_MAX)
-    launch(pa::k_linkage_centroid<unsigned short, true>, lds16, true);
-  else
-    launch(pa::k_linkage_centroid<int, false>, cand_bytes, false);
+  const bool in_lds = n <= 65535 && lds16 <= pa::LK_LDS_MAX;   // the heap in dynamic LDS beyond the default limit
+  if (in_lds) PA_ALLOW_LDS("pa_linkage_centroid_f64", (pa::k_linkage_centroid<unsigned short, true>), pa::LK_LDS_MAX);
+  if (in_lds) launch(pa::k_linkage_centroid<unsigned short, true>, lds16);
+  else launch(pa::k_linkage_centroid<int, false>, cand_bytes);
   PA_CHECK_LAUNCH("pa_linkage_centroid_f64");
   return 0;
 }

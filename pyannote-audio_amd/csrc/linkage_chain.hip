@@ -415,17 +415,17 @@ int pa_linkage_chain_f64(const double* D, int n, int method, double* raw, void* 
   PA_CHECK_LAUNCH("pa_linkage_chain_f64 (square copy)");
   const size_t lds_bytes = pa::lc_smem_bytes(n, method);
   const bool lds = lds_bytes != 0;
-  // one workgroup; `state`: the chain (nn_chain) or Dmin (single linkage).  (The attribute is set on every call: it
-  // belongs to the current device, not to the process.)
-  auto launch = [&](auto kernel, auto* state) {
-    if (lds)
-      (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pa::LC_LDS_MAX);
-    hipLaunchKernelGGL(kernel, dim3(1), dim3(pa::LC_T), lds_bytes, st, s.S, n, ld, raw, s.size, state, s.status);
-  };
-#define PA_LC_CHAIN(M)                                          \
-  case M:                                                       \
-    if (lds) launch(pa::k_lc_nn_chain<M, true>, s.chain);       \
-    else launch(pa::k_lc_nn_chain<M, false>, s.chain);          \
+  // one workgroup; `state`: the chain (nn_chain) or Dmin (single linkage).  The LDS grant is per KERNEL (launch_state.h):
+  // the nn-chain kernels share one signature, so a generic lambda would give them one static between them.
+#define PA_LC_LAUNCH(LDS, kernel, state)                                                                              \
+  do {                                                                                                                \
+    if (LDS) PA_ALLOW_LDS("pa_linkage_chain_f64", kernel, pa::LC_LDS_MAX);                                            \
+    hipLaunchKernelGGL(kernel, dim3(1), dim3(pa::LC_T), lds_bytes, st, s.S, n, ld, raw, s.size, state, s.status);     \
+  } while (0)
+#define PA_LC_CHAIN(M)                                                  \
+  case M:                                                               \
+    if (lds) PA_LC_LAUNCH(true, (pa::k_lc_nn_chain<M, true>), s.chain); \
+    else PA_LC_LAUNCH(false, (pa::k_lc_nn_chain<M, false>), s.chain);   \
     break;
   switch (method) {
     PA_LC_CHAIN(PA_LINKAGE_COMPLETE)
@@ -433,10 +433,11 @@ int pa_linkage_chain_f64(const double* D, int n, int method, double* raw, void* 
     PA_LC_CHAIN(PA_LINKAGE_WEIGHTED)
     PA_LC_CHAIN(PA_LINKAGE_WARD)
     default:
-      if (lds) launch(pa::k_lc_mst_single<true>, s.dmin);
-      else launch(pa::k_lc_mst_single<false>, s.dmin);
+      if (lds) PA_LC_LAUNCH(true, (pa::k_lc_mst_single<true>), s.dmin);
+      else PA_LC_LAUNCH(false, (pa::k_lc_mst_single<false>), s.dmin);
   }
 #undef PA_LC_CHAIN
+#undef PA_LC_LAUNCH
   PA_CHECK_LAUNCH("pa_linkage_chain_f64");
   return 0;
 }

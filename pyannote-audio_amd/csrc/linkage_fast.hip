@@ -708,10 +708,7 @@ static int lf_num_workgroups(int n) {
 // bound of a mailbox poll: 2 s of the constant-rate clock wall_clock64() reads (hipDeviceAttributeWallClockRate, kHz;
 // 100 MHz on this chip); PA_LINKAGE_POLL_MS overrides (tests force a give-up with it)
 static long long lf_poll_limit_ticks() {
-  int dev = 0, khz = 0;
-  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, dev) != hipSuccess ||
-      khz <= 0)
-    khz = 100000;
+  const long khz = device_attribute(devq::WALL_CLOCK_KHZ, devq::current(), 100000);
   const char* e = getenv("PA_LINKAGE_POLL_MS");
   const double ms = (e != nullptr && atof(e) > 0) ? atof(e) : 2000.0;
   return (long long)(ms * (double)khz);
@@ -730,15 +727,13 @@ int lf_launch(const double* cond, int n, double* Z, const LfState& s, long long*
   const long long poll_limit = lf_poll_limit_ticks();
   if (G == 1) {
     const size_t lds = (size_t)SL * LF_T * 14;
-    (void)hipFuncSetAttribute((const void*)k_linkage_fast<unsigned short, false>,
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)LF_LDS_MAX);
+    PA_ALLOW_LDS("pa_linkage_centroid_f64 (fast path)", (k_linkage_fast<unsigned short, false>), LF_LDS_MAX);
     hipLaunchKernelGGL((k_linkage_fast<unsigned short, false>), dim3(1), dim3(LF_T), lds, st, s.S, ld, n, Z, s.nb0,
                        s.mind0, s.g_size, s.g_cid, s.mail, 1, SL, poll_limit, s.status, stats);
   } else {
     const size_t lds = (size_t)SL * LF_T * 16;
     if (lds > LF_LDS_MAX) return 0;   // (status stays "not run": the heap kernel does the work)
-    (void)hipFuncSetAttribute((const void*)k_linkage_fast<unsigned int, true>,
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)LF_LDS_MAX);
+    PA_ALLOW_LDS("pa_linkage_centroid_f64 (fast path)", (k_linkage_fast<unsigned int, true>), LF_LDS_MAX);
     hipLaunchKernelGGL((k_linkage_fast<unsigned int, true>), dim3(8 * G), dim3(LF_T), lds, st, s.S, ld, n, Z, s.nb0,
                        s.mind0, s.g_size, s.g_cid, s.mail, G, SL, poll_limit, s.status, stats);
   }

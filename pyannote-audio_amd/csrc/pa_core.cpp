@@ -21,6 +21,30 @@ void set_error(const char* fmt, ...) {
   va_end(ap);
 }
 
+// The device queries behind launch_state.h: the only calls of these HIP functions in the library.
+namespace devq {
+int current() { int dev = 0; return hipGetDevice(&dev) == hipSuccess ? dev : 0; }
+long attribute(int dev, Attr which) {
+  static const hipDeviceAttribute_t attr[] = {hipDeviceAttributeMultiprocessorCount,   // in the order of devq::Attr
+                                              hipDeviceAttributeMaxSharedMemoryPerBlock, hipDeviceAttributeWallClockRate};
+  int v = 0;
+  return hipDeviceGetAttribute(&v, attr[which], dev) == hipSuccess ? v : 0;
+}
+bool set_dynamic_lds(const void* kernel, long bytes) {
+  return hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) == hipSuccess;
+}
+int blocks_per_cu(const void* kernel, int threads, long lds) {
+  int n = 0;
+  return hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, kernel, threads, (size_t)lds) == hipSuccess ? n : 0;
+}
+}  // namespace devq
+int lds_refused(const char* entry, long answer, size_t bytes) {
+  set_error(answer == LDS_OVER_LIMIT ? "%s: needs %zu bytes of LDS per workgroup, this device offers %ld"
+                                     : "%s: cannot reserve %zu bytes of dynamic LDS (this device offers %ld)",
+            entry, bytes, lds_limit(devq::current()));
+  return 3;
+}
+
 // Pool of self-resetting tile-counter blocks (common.h): 4096 blocks of 16 ints per device, handed out in
 // rotation -- on one stream a block is always free again when its turn comes (launches are ordered), and
 // across streams 4096 launches would have to be in flight at once for two to meet.
@@ -28,20 +52,23 @@ void set_error(const char* fmt, ...) {
 // Conventions of pyannote_amd.h): the pool is allocated, zeroed on the null stream, and the null stream is waited for.
 // The wait is what orders the zeroing before the caller's kernel: a non-blocking stream does not synchronise with
 // the null stream, and whether hipMemset itself returns only after the fill is nowhere promised for device memory.
-int* tile_counters() {
-  constexpr int MAXDEV = 16, BLOCKS = 4096;
+int* tile_counters(const char* entry) {
+  constexpr int BLOCKS = 4096;
   static std::mutex mu;
   static int* pool[MAXDEV] = {nullptr};
   static unsigned next[MAXDEV] = {0};
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  if (dev < 0 || dev >= MAXDEV) dev = 0;
+  const int dev = devq::current();
+  if (!DeviceCell::holds(dev)) {
+    set_error("%s: no tile counters for device %d (the table of launch_state.h ends at %d)", entry, dev, MAXDEV - 1);
+    return nullptr;
+  }
   std::lock_guard<std::mutex> lock(mu);
   if (pool[dev] == nullptr) {
-    if (hipMalloc((void**)&pool[dev], sizeof(int) * 16 * BLOCKS) != hipSuccess) return nullptr;
-    if (hipMemset(pool[dev], 0, sizeof(int) * 16 * BLOCKS) != hipSuccess || hipStreamSynchronize(nullptr) != hipSuccess) {
+    if (hipMalloc((void**)&pool[dev], sizeof(int) * 16 * BLOCKS) != hipSuccess ||
+        hipMemset(pool[dev], 0, sizeof(int) * 16 * BLOCKS) != hipSuccess || hipStreamSynchronize(nullptr) != hipSuccess) {
       (void)hipFree(pool[dev]);
       pool[dev] = nullptr;
+      set_error("%s: cannot allocate the tile counters", entry);
       return nullptr;
     }
   }

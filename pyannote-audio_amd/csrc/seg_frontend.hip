@@ -360,9 +360,7 @@ int pa_sinc_fir_pool(const float* wav, long wav_len, long chunk_stride, int B, i
 #define PA_SINC_LAUNCH(S)                                                                                          \
   do {                                                                                                             \
     const size_t lds = (size_t)(3 * (S) * pa::SINC_PT + 256 + 80 * pa::SINC_OS) * sizeof(float);                     \
-    /* (set on every call: the attribute belongs to the current device, not to the process) */                     \
-    (void)hipFuncSetAttribute((const void*)pa::k_sinc_fir_pool<false, S>, hipFuncAttributeMaxDynamicSharedMemorySize, \
-                              (int)lds);                                                                           \
+    PA_ALLOW_LDS("pa_sinc_fir_pool", (pa::k_sinc_fir_pool<false, S>), lds);                                        \
     hipLaunchKernelGGL((pa::k_sinc_fir_pool<false, S>), dim3(pa::cdiv(P, pa::SINC_PT), B), dim3(pa::SINC_T), lds,  \
                        (hipStream_t)stream, wav, wav_len, chunk_stride, N, stride, P, mean, rstd, gamma, beta,      \
                        filt_packed, out, 0);                                                                       \
@@ -394,8 +392,7 @@ static int sinc_fir_span(const float* wav, long wav_len, long span, const float*
   PA_REQUIRE(span <= 0x7fffffffL, "pa_sinc_fir_span: span of %ld samples is too long", span);
   const int Pc = (int)((span - 251) / 10 + 1);
   const size_t lds = (pa::SINC_XS + 80 * pa::SINC_OS) * sizeof(float);
-  (void)hipFuncSetAttribute((const void*)pa::k_sinc_fir_pool<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)lds);
+  PA_ALLOW_LDS("pa_sinc_fir_span", pa::k_sinc_fir_pool<true>, lds);
   pa::ProfScope prof("k_sinc_fir_span", stream, 2.0 * 80 * 251 * (double)Pc, 4.0 * span + 4.0 * 80 * Pc);
   hipLaunchKernelGGL(pa::k_sinc_fir_pool<true>, dim3(pa::cdiv(Pc, pa::SINC_PT), 1), dim3(pa::SINC_T), lds,
                      (hipStream_t)stream, wav, wav_len, 0L, (int)span, 10, Pc, mean0, rstd0, 1.f, 0.f, filt_packed, S,
@@ -442,8 +439,7 @@ int pa_sinc_fix_pool_centred(const float* S, long Pc, int positions_per_chunk_st
                      positions_per_chunk_step, P, mean, rstd, gamma, beta, (const float*)tap_sums, out, 1);
   {
     const size_t lds = (pa::SINC_XS + 80 * pa::SINC_OS) * sizeof(float);
-    (void)hipFuncSetAttribute((const void*)pa::k_sinc_fir_pool<false, 10>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)lds);
+    PA_ALLOW_LDS("pa_sinc_fix_pool_centred", (pa::k_sinc_fir_pool<false, 10>), lds);
     hipLaunchKernelGGL((pa::k_sinc_fir_pool<false, 10>), dim3(pa::cdiv(P, pa::SINC_PT), B), dim3(pa::SINC_T), lds,
                        (hipStream_t)stream, wav, wav_len, 10L * positions_per_chunk_step, N, 10, P, mean, rstd, gamma,
                        beta, filt_packed, out, 1);

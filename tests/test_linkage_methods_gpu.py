@@ -105,6 +105,19 @@ def test_linkage_chain_equals_scipy(gpu_device, case, metric, monkeypatch):
         assert_same_dendrogram(got, linkage(y, method), f"{case}, {method}, {metric}")
 
 
+def test_two_methods_above_the_default_lds_in_one_process(gpu_device):
+    """n = 8200: the nn-chain kernels keep 8 n = 65 600 bytes in dynamic LDS, above the 64 KB a launch gets without
+    asking.  The grant is remembered per kernel and device (csrc/launch_state.h), and the kernels of the four methods
+    have one signature: every method's own kernel must have been granted its LDS, whichever ran first in the process.
+    complete, then average, each equal to SciPy row for row (about 2 s of SciPy each)."""
+    from pyannote_audio_amd import distance
+    X = clustered(8200, 8, 8200)
+    y = pdist(X, "euclidean")
+    for method in ("complete", "average"):
+        got = distance.linkage_chain(X.copy(), method, "euclidean", gpu_device)
+        assert_same_dendrogram(got, linkage(y, method), f"n8200, {method}")
+
+
 @pytest.mark.parametrize("lds", ["1", "0"])
 @pytest.mark.parametrize("method", METHODS)
 def test_raw_merges_equal_the_model_and_stay_in_bounds(gpu_device, method, lds, monkeypatch):

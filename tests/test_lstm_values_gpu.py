@@ -6,52 +6,10 @@ Rules of the comparison: tests/kernel_parity.py."""
 import pytest
 import torch
 
-from kernel_parity import SEED_OFFSET, Guarded, assert_parity, dptr
+from kernel_parity import SEED_OFFSET, assert_parity
+from lstm_cases import recurrence, run_kernel, saturating_case
 
 pytestmark = pytest.mark.gpu
-
-
-def _recurrence(pre, whh, dtype):
-    """pre (B, T, ndir, 4H) gate pre-activations in torch's order i, f, g, o; whh: ndir matrices (4H, H); direction 1
-    runs backwards in time.  Returns h (B, T, ndir * H), computed step by step in `dtype`."""
-    B, T, ndir, H4 = pre.shape
-    H = H4 // 4
-    out = torch.zeros(B, T, ndir * H, dtype=dtype)
-    for d in range(ndir):
-        w = whh[d].to(dtype).T.contiguous()
-        x = pre[:, :, d].to(dtype)
-        h = torch.zeros(B, H, dtype=dtype)
-        c = torch.zeros(B, H, dtype=dtype)
-        for t in (range(T - 1, -1, -1) if d else range(T)):
-            z = x[:, t] + h @ w
-            i, f = torch.sigmoid(z[:, :H]), torch.sigmoid(z[:, H:2 * H])
-            g, o = torch.tanh(z[:, 2 * H:3 * H]), torch.sigmoid(z[:, 3 * H:])
-            c = f * c + i * g
-            h = o * torch.tanh(c)
-            out[:, t, d * H:(d + 1) * H] = h
-    return out
-
-
-def _run_kernel(pre, whh, device, tag):
-    """pa_lstm_rec_h on `pre` (B, T, ndir, 4H) / `whh`: operand images of weights.py, output inside guards"""
-    import pyannote_audio_amd.ffi as ffi
-    from pyannote_audio_amd.weights import (_lstm_row_perm, _lstm_row_perm_gen, _lstm_whh_image, _lstm_whh_image_gen)
-    lib = ffi.load()
-    B, T, ndir, H4 = pre.shape
-    H = H4 // 4
-    fast = H == 128 and ndir == 2
-    perm = _lstm_row_perm() if fast else _lstm_row_perm_gen(H)
-    image = _lstm_whh_image if fast else _lstm_whh_image_gen
-    ntiles = (B + 15) // 16
-    padded = torch.zeros(ntiles * 16, T, ndir, H4)
-    padded[:B] = pre[..., perm]
-    # [tile][t][ndir * 4H][16]
-    xproj = padded.view(ntiles, 16, T, ndir * H4).permute(0, 2, 3, 1).contiguous().to(device)
-    wd = torch.cat([image(w.float().contiguous()) for w in whh]).to(device)
-    out = Guarded(ntiles * T * 16 * ndir * H, device)
-    ffi.check(lib.pa_lstm_rec_h(dptr(xproj), dptr(wd), out.ptr, ntiles, ndir, T, H, ffi.stream()), tag)
-    got = out.check(None, tag)       # (the chunks that pad the last tile are computed and stored like the others)
-    return got.view(ntiles, T, 16, ndir * H).permute(0, 2, 1, 3).reshape(ntiles * 16, T, ndir * H)[:B]
 
 
 def _gate_grid():
@@ -90,10 +48,10 @@ def test_gate_functions_alone(gpu_device, H, ndir, T):
             pre[:, t, d] = units[order].view(B, H, 4).permute(0, 2, 1)
     pre = pre.view(B, T, ndir, 4 * H)
     whh = [torch.zeros(4 * H, H) for _ in range(ndir)]
-    truth = _recurrence(pre, whh, torch.float64)
-    ref32 = _recurrence(pre, whh, torch.float32)
+    truth = recurrence(pre, whh, torch.float64)
+    ref32 = recurrence(pre, whh, torch.float32)
     assert torch.isfinite(truth).all()
-    got = _run_kernel(pre, whh, gpu_device, f"gates H{H} T{T}")
+    got = run_kernel(pre, whh, gpu_device, f"gates H{H} T{T}")
     assert torch.isfinite(got).all()
     assert_parity(f"lstm_gates_alone_H{H}_d{ndir}_T{T}", got, truth, ref32)
 
@@ -115,30 +73,30 @@ SATURATING = [
 ]
 
 
-def _saturating_case(H, ndir, T, scale, fb, xs, B, seed):
-    torch.manual_seed(700 + seed + SEED_OFFSET)
-    lstm = torch.nn.LSTM(64, H, 1, bidirectional=ndir == 2, batch_first=True).double()
-    x = xs * torch.randn(B, T, 64, dtype=torch.float64)
-    sd = lstm.state_dict()
-    pre, whh = [], []
-    for d in range(ndir):
-        sfx = "_reverse" if d else ""
-        bias = scale * (sd["bias_ih_l0" + sfx] + sd["bias_hh_l0" + sfx])
-        bias[H:2 * H] += fb
-        pre.append(x @ (scale * sd["weight_ih_l0" + sfx]).T + bias)
-        whh.append((scale * sd["weight_hh_l0" + sfx]).float())          # the kernel's operands are float32 ...
-    pre = torch.stack(pre, 2).float()                                    # ... and so are its gate inputs
-    return pre, whh
-
-
 @pytest.mark.parametrize("H,ndir,T,scale,fb,xs,B,seed", SATURATING)
 def test_saturating_layers(gpu_device, H, ndir, T, scale, fb, xs, B, seed):
     """a whole chunk (589 / 300 steps) of a layer whose gates saturate: weights x scale, forget bias + fb, input x xs"""
-    pre, whh = _saturating_case(H, ndir, T, scale, fb, xs, B, seed)
-    truth = _recurrence(pre, whh, torch.float64)
-    ref32 = _recurrence(pre, whh, torch.float32)
+    pre, whh = saturating_case(H, ndir, T, scale, fb, xs, B, seed)
+    truth = recurrence(pre, whh, torch.float64)
+    ref32 = recurrence(pre, whh, torch.float32)
     tag = f"lstm_saturating_H{H}_d{ndir}_T{T}_scale{scale:g}_fb{fb:g}_xs{xs:g}_B{B}"
     beyond6 = (pre.abs() > 6).float().mean().item()
     print(f"{tag}: max |pre-activation of the input| = {pre.abs().max().item():.1f}, {100 * beyond6:.0f} % beyond 6")
-    got = _run_kernel(pre, whh, gpu_device, tag)
+    got = run_kernel(pre, whh, gpu_device, tag)
     assert_parity(tag, got, truth, ref32)
+
+
+def test_lds_grant_follows_the_hidden_size(gpu_device):
+    """k_lstm_rec_gen asks for dynamic LDS by hidden size (66.5 KB at H = 256, 132 KB at H = 512) and the grant is
+    remembered per device as the largest one given (csrc/launch_state.h): H = 256, 512, 256 in one process, one tile of
+    16 chunks, 4 steps, one direction.  A grant that shrank or was skipped shows as a failed launch or as other values:
+    every result is held to the float64 recurrence, and the third is the first bit for bit."""
+    got = {}
+    for call, H in enumerate((256, 512, 256)):
+        pre, whh = saturating_case(H, 1, 4, 1.0, 0.0, 1.0, 16, 0)
+        truth = recurrence(pre, whh, torch.float64)
+        ref32 = recurrence(pre, whh, torch.float32)
+        tag = f"lstm_lds_grant_call{call}_H{H}"
+        got[call] = run_kernel(pre, whh, gpu_device, tag)
+        assert_parity(tag, got[call], truth, ref32)
+    assert torch.equal(got[2], got[0])
