@@ -120,6 +120,83 @@ int pao_replay(const float* emb, const int32_t* active, const int32_t* clean, co
                double* centroid_sum, int32_t* centroid_n, int32_t* acc_sum, int32_t* acc_cnt, int32_t* map,
                uint8_t* out, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------------------
+ * Online DETECTION (voice activity, multi-label events): csrc/online_detect.hip.  No embeddings and no clustering; the
+ * arithmetic of the OFFLINE detection path carried across pushes, so that a stream's regions at full latency are bit
+ * for bit those of pa_aggregate_files + pa_binarize_regions on the same samples.
+ *
+ * limits of pao_detect_step: *max_classes = 16 classes (K, and score columns S); *max_emit_values = the most E * K one
+ * emission may hold (the workgroup keeps it in LDS) */
+int pao_detect_limits(int* max_classes_host, int* max_emit_values_host);
+
+/* One detection step of M streams of an N-slot bank in one launch, one workgroup per stream.
+ *   slots (M) int32 distinct, in [0, N); slots_host: the same on the host, or NULL
+ *   scores (M, F, S): float32, or with scores_uint8 the uint8 hard decisions (0 -> 0.f, anything else -> 1.f, as
+ *     pa_aggregate_files reads them; with any = 1 only, else 3)
+ *   any: K = 1 and the value of a frame is the maximum of its S columns, NaN if one of them is (np.max); else K = S
+ *   window, warm (F) float64 on the device; epsilon, missing: as pa_aggregate
+ *   start_frame, emit_from, emit_to, closing (M) int64 on the device; frames_host (4, M) int64 = those four rows on
+ *     the host, or NULL.  Consistent as for pao_emit: 0 <= emit_from <= emit_to, emit_to - emit_from <= E and, unless
+ *     start_frame < 0, start_frame + F - emit_from <= R; closing is 0 or 1
+ *   start, duration, step: the frame grid (the time of frame g is 0.5 * (s + (s + duration)), s = start + g * step)
+ *   onset_host, offset_host (K) float32, min_duration_on_host, min_duration_off_host (K) float64: host arrays, read
+ *     before the call returns and handed to the kernel by value; one set for the whole bank
+ * State, in / out, touched for the listed slots only; zeros are a fresh stream:
+ *   acc, cnt (N, R, K) float32   ring over the global frame index g mod R: weighted sum of scores, sum of weights
+ *   msk (N, R, K) uint8          ring: a chunk gave the frame a value that is not NaN
+ *   on (N, K) uint8              hysteresis state behind the last emitted frame
+ *   open_start (N, K) float64    where the open region started (meaningful while `on`)
+ *   pend (N, K, 2) float64, has_pend (N, K) uint8   the last merged region, not final yet
+ *   n_merged (N, K) int32        merged regions so far, the pending one included
+ * Per stream, in this order:
+ *   1. OVERLAP-ADD.  For f in [0, F), g = start_frame + f, g >= emit_from (a frame below emit_from was emitted by an
+ *      earlier call), x the frame's value, m = 0 if x is NaN else 1, row g mod R of the ring:
+ *        acc = (float)((double)acc + (((double)(m ? x : 0) * m) * window[f]) * warm[f])
+ *        cnt = (float)((double)cnt + ((double)m * window[f]) * warm[f]),   msk = max(msk, m)
+ *      -- pa_aggregate's expressions, one chunk per call in ascending chunk order.  start_frame < 0 adds nothing: a
+ *      flush at the end of a stream.
+ *   2. EMISSION.  For g in [emit_from, emit_to): v = acc / fmaxf(cnt, epsilon), v = missing where msk == 0;
+ *      values[g - emit_from] = v and the ring row is cleared.
+ *   3. HYSTERESIS on the emitted values, float32 comparisons, continuing from `on`: frame 0 of the stream finds the
+ *      state inactive whatever `on` held; inactive -> active iff v > onset, active -> inactive iff v < offset (NaN
+ *      changes nothing; offset > onset is legal).  active[g - emit_from] = the state behind frame g.  Going active at
+ *      frame g sets open_start = t(g); going inactive at frame g closes the raw region (open_start, t(g)).
+ *   4. A raw region (s, e) that closes is dropped unless e - s > 1e-6.  Otherwise, with d(a, b) = b - a if that is
+ *      > 1e-6 else 0 (pyannote.core's Segment.duration): if a region is pending, min_off > 0 and d(pend.e, s) <
+ *      min_off, it is merged (pend.e = e); else the pending region, if any, is FINALISED and (s, e) becomes the pending
+ *      region, n_merged += 1.  Without min_off > 0 nothing ever merges and the pending region is finalised at once.
+ *      A pending region is also finalised when the stream goes active at a time t with not d(pend.e, t) < min_off: no
+ *      later region can merge with it.  FINALISE: the region is written to this call's list unless min_on > 0 and
+ *      d(pend.s, pend.e) < min_on; its track is n_merged - 1 (its index among the merged regions, counted whether or
+ *      not they were written) when min_off > 0, else 0.
+ *   5. CLOSING (closing = 1, the last call of a stream).  Behind the emitted frames a region still open closes at
+ *      t(emit_to - 1) by item 4, the state becomes inactive, and the pending region is finalised.
+ *   -> values (M, E, K) float32, active (M, E, K) uint8: rows behind emit_to - emit_from are NaN / 0
+ *   -> counts (M, K) int32, regions (M, K, cap, 2) float64, tracks (M, K, cap) int32: the regions this call finalised,
+ *      in time order; rows behind a count are NaN / -1.  Every output is written whole.
+ * Why the regions of a whole stream are pa_binarize_regions' on the concatenated values (T frames): items 3 - 4 are
+ * its rule frame by frame -- the same comparisons, the same t(g), empty regions dropped before merging, merging before
+ * the min_on deletion, tracks numbered over the merged list -- and a merged region is final exactly when no later raw
+ * region can extend it, which is what the finality conditions of item 4 say.  Offline, the LAST frame is special: it
+ * closes what is open and opens nothing.  Item 5 gives the same list: a region open before frame T - 1 closes at
+ * t(T - 1) whether frame T - 1 switched it off (item 3 closed it there) or not (item 5 does); a region that item 3
+ * opens AT frame T - 1 is closed by item 5 at its own start and dropped as empty; T = 1 is that case and T = 0 has no
+ * frame, so T < 2 gives no region.
+ * 3 (nothing launched, nothing written) if S or K is outside 1..16, F < 1, E < 1, R < F + E, E * K exceeds
+ * pao_detect_limits, cap < E / 2 + 2 (an emission of E frames finalises at most E / 2 + 1 regions that close in it and
+ * the one pending on entry), uint8 scores without `any`, a NaN threshold, duration or grid value, duplicate or
+ * out-of-range slots_host, or an inconsistent entry of frames_host.  On the device a stream whose slot or frames are
+ * inconsistent gets NaN values, zero states, zero counts, NaN / -1 region rows and keeps its state.
+ * One kernel on `stream`, no synchronisation, no allocation, no workspace: it can be captured into a graph. */
+int pao_detect_step(const int32_t* slots, const int32_t* slots_host, int M, int N, const void* scores,
+                    int scores_uint8, int F, int S, int any, const double* window, const double* warm, float epsilon,
+                    float missing, const int64_t* start_frame, const int64_t* emit_from, const int64_t* emit_to,
+                    const int64_t* closing, const int64_t* frames_host, double start, double duration, double step,
+                    const float* onset_host, const float* offset_host, const double* min_duration_on_host,
+                    const double* min_duration_off_host, int R, int E, int cap, float* acc, float* cnt, uint8_t* msk,
+                    uint8_t* on, double* open_start, double* pend, uint8_t* has_pend, int32_t* n_merged, float* values,
+                    uint8_t* active, int32_t* counts, double* regions, int32_t* tracks, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -19,6 +19,7 @@ from .speaker_diarization import SpeakerDiarization, DiarizeOutput  # noqa: E402
 from .voice_activity_detection import VoiceActivityDetection  # noqa: E402,F401
 from .multilabel import MultiLabelSegmentation  # noqa: E402,F401
 from .online import OnlineSpeakerDiarization, StreamBank  # noqa: E402,F401
+from .online_detection import DetectionBank, OnlineVoiceActivityDetection  # noqa: E402,F401
 from .hook import ArtifactHook, Hooks, ProgressHook, TimingHook  # noqa: E402,F401
 from . import metrics  # noqa: E402,F401
 from . import verification  # noqa: E402,F401

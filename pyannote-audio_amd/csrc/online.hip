@@ -47,19 +47,6 @@ __global__ __launch_bounds__(ON_T) void k_online_emit(
                   acc_cnt + (long)slot * R, o);
 }
 
-// slots_host: distinct and inside [0, N)
-static int check_slots(const char* who, const int32_t* slots_host, int M, int N) {
-  if (slots_host == nullptr) return 0;
-  for (int i = 0; i < M; ++i) {
-    PA_REQUIRE(slots_host[i] >= 0 && slots_host[i] < N, "%s: slot %d (entry %d) outside the bank of %d", who,
-               (int)slots_host[i], i, N);
-    for (int j = 0; j < i; ++j)   // (a step lists a few hundred slots at most)
-      PA_REQUIRE(slots_host[i] != slots_host[j], "%s: duplicate slot %d (entries %d and %d): one workgroup owns one "
-                 "stream", who, (int)slots_host[i], j, i);
-  }
-  return 0;
-}
-
 }  // namespace pa
 
 extern "C" {

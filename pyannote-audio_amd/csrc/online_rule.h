@@ -212,6 +212,19 @@ __device__ __forceinline__ void online_cluster_step_one(OnlineStepShared& sh, co
   }
 }
 
+// slots_host of an entry point that lists streams of a bank: distinct and inside [0, N) (NULL: the caller vouches)
+inline int check_slots(const char* who, const int32_t* slots_host, int M, int N) {
+  if (slots_host == nullptr) return 0;
+  for (int i = 0; i < M; ++i) {
+    PA_REQUIRE(slots_host[i] >= 0 && slots_host[i] < N, "%s: slot %d (entry %d) outside the bank of %d", who,
+               (int)slots_host[i], i, N);
+    for (int j = 0; j < i; ++j)   // (a step lists a few hundred slots at most)
+      PA_REQUIRE(slots_host[i] != slots_host[j], "%s: duplicate slot %d (entries %d and %d): one workgroup owns one "
+                 "stream", who, (int)slots_host[i], j, i);
+  }
+  return 0;
+}
+
 // the frames of one emission are consistent: nothing the overlap-add or the emission touches leaves the ring of R
 // frames or the E rows of the output (the same conditions on the host and on the device)
 __host__ __device__ __forceinline__ bool online_frames_valid(long long g0, long long ga, long long gb, int F, int R,

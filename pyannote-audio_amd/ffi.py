@@ -368,6 +368,12 @@ _OPTIONAL: list[tuple] = [
     ("pao_replay", [c_fp, c_fp, c_fp, c_fp, C.c_int64, C.c_int, C.c_int, C.c_int, c_fp, C.c_void_p, C.c_int, c_fp,
                     C.c_void_p, C.c_int64, c_fp, C.c_void_p, c_fp, c_fp, C.c_void_p, C.c_int, C.c_int64, C.c_int64,
                     C.c_int, C.c_int, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp], C.c_int),
+    # csrc/online_detect.hip
+    ("pao_detect_limits", [C.POINTER(C.c_int), C.POINTER(C.c_int)], C.c_int),
+    ("pao_detect_step", [c_fp, C.c_void_p, C.c_int, C.c_int, c_fp, C.c_int, C.c_int, C.c_int, C.c_int, c_fp, c_fp,
+                         C.c_float, C.c_float, c_fp, c_fp, c_fp, c_fp, C.c_void_p, C.c_double, C.c_double, C.c_double,
+                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, c_fp, c_fp, c_fp,
+                         c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp, c_fp], C.c_int),
 ]
 
 

@@ -85,6 +85,9 @@ def get_class_by_name(class_name: str, default_module_name: Optional[str] = None
     if class_name.startswith("pyannote.audio.pipelines") and tokens[-1] == "OnlineSpeakerDiarization":
         from .online import OnlineSpeakerDiarization
         return OnlineSpeakerDiarization
+    if class_name.startswith("pyannote.audio.pipelines") and tokens[-1] == "OnlineVoiceActivityDetection":
+        from .online_detection import OnlineVoiceActivityDetection
+        return OnlineVoiceActivityDetection
     if len(tokens) == 1:
         if default_module_name is None:
             raise ValueError(f"cannot resolve class {class_name!r} without a module name")
